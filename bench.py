@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 160x160 lip-sync frames/sec through the MI355X engine.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (``Model.forward``) over one batch of synthetic
 frames per GPU.  Workload = BASELINE.json configs[1]: batch 64 per GPU, 160x160 fp32,
@@ -14,11 +14,15 @@ the ranks (``python -m torch.distributed.run ... bench.py --gpus N``: RANK/WORLD
 environment) or ``python bench.py --gpus N`` starts them itself, as fresh child processes, BEFORE the
 parent touches the GPU.  Frames are independent, so the batch is sharded with no data-path
 collective ("weak" scaling: 64 frames per GPU); the only collective is ONE broadcast of the packed,
-BN-folded weight buffer from rank 0 at start-up.  At N > 1 the line also carries the
-BASELINE configs[3] split (4096 frames over the ranks) beside the weak point.
+BN-folded weight buffer from rank 0 at start-up.
 
-Prints one JSON line (rank 0) with the whole-job frames/sec, the roofline of the dominant
-kernel (live HIP-event timing) and, at N=1, the CPU oracle timed on the host cores.
+A plain run sets up, warms up, times the --steps steps and prints one JSON line (rank 0) with the
+whole-job frames/sec (`value`) and `ms_per_step`, the wall time of one timed step.  --dump-outputs DIR
+also writes what the last timed step returned (the whole job's frames) to DIR/out.npy.  Everything else
+is measured only with --full: the roofline of the dominant kernel and the whole-net fractions (serialised
+replays with live HIP-event timing), at N=1 the `secondary` block (other batches / precisions, the device
+frame loop) and the CPU oracle timed on the host cores, and at N > 1 the BASELINE configs[3] split (4096
+frames over the ranks) beside the weak point.
 """
 from __future__ import annotations
 
@@ -53,11 +57,17 @@ def parse():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="strong scaling as the headline: a FIXED number of frames per step split over the ranks "
                          "(SURVEY 8d: 4096); default 0 = weak scaling, --batch frames per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel roofline and whole-net fractions, "
+                         "at N=1 the secondary block and the CPU baseline, at N > 1 the configs[3] strong-scaling split")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/out.npy (float32, at most 64 MB: past that a fixed, "
+                         "seeded sample of whole frames)")
     ap.add_argument("--strong-frames", type=int, default=4096,
-                    help="N > 1 only: frames of the configs[3] split timed beside the weak point (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="N > 1, --full only: frames of the configs[3] split timed beside the weak point (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle leg")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the CPU-oracle leg")
-    ap.add_argument("--kernel-table", action="store_true", help="print the per-launch table to stderr")
+    ap.add_argument("--kernel-table", action="store_true", help="print the per-launch table to stderr (runs the per-kernel pass of --full)")
     ap.add_argument("--replay-only", action="store_true",
                     help="skip the timed region; run --steps isolated replays (the mode rocprofv3 / PMC passes "
                          "are collected in, so their per-kernel figures match the roofline block)")
@@ -65,9 +75,14 @@ def parse():
                     help="also time the device frame loop (process_batch: crop+resize -> forward -> paste-back "
                          "blend on synthetic 1080p frames, one D2H per batch) and report it in config.e2e")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the `secondary` block (N=1, default f32 run only: bf16 B=512 = configs[2], the device "
+                    help="--full without the `secondary` block (N=1, default f32 run only: bf16 B=512 = configs[2], the device "
                          "frame loop, the reference's own B=8 benchmark shape; ~20 s)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.replay_only:
+        ap.error("--dump-outputs needs the timed forwards; --replay-only runs none")
+    return args
 
 
 def host_cores() -> int:
@@ -278,7 +293,7 @@ def strong_leg(net, x, a, total_frames, rank, world, steps, sync, max_over_ranks
 
 
 def secondary_block(net, packed, x, a, dev, src_hash):
-    """Figures next to the headline that the driver's plain `bench.py` run would otherwise never produce
+    """--full: figures next to the headline that no other `bench.py` configuration produces
     (N = 1 only; ~20 s): the reference's own benchmark shape (B=8 fp32), BASELINE configs[2] (bf16, B=512, with its
     own roofline) and the device frame loop.  None of them replaces `value`."""
     import torch
@@ -358,6 +373,138 @@ def secondary_block(net, packed, x, a, dev, src_hash):
     del net16, x16, a16
     torch.cuda.empty_cache()
     return sec
+
+
+def per_kernel_pass(net, x, a, args, B, per_gpu):
+    """--full: the roofline of the dominant kernel and the whole-net fractions (rank 0).  -> (roofline, whole_net)"""
+    from calipsync_amd import arch
+    per = {}
+    reps = args.steps if args.replay_only else 3
+    # The timed region overlaps the sub-batch lanes (and the audio streams) on the GPU, so
+    # per-kernel durations there are not separable.  The roofline pass replays the SAME launches
+    # (same lanes, hence the same kernels, tile choices and grids) serialised on one stream with
+    # an event pair around each (casync_profile_forward).
+    # every launch is timed `reps` times; its figure is the MEDIAN of those (one slow launch -- a cold instruction
+    # cache, a clock dip -- otherwise moves a whole kernel family's average), counted `reps` times so that the
+    # sums below keep their meaning
+    runs = [net.profile(x, a) for _ in range(reps)]
+    for i, row in enumerate(runs[0]):
+        ms = sorted(r[i]["ms"] for r in runs)[reps // 2]
+        c = per.setdefault(row["kernel"], {"ms": 0.0, "flops": 0.0, "bytes": 0.0, "n": 0})
+        c["ms"] += ms * reps; c["flops"] += row["flops"] * reps; c["bytes"] += row["bytes"] * reps; c["n"] += reps
+    if args.kernel_table:
+        tot = sum(c["ms"] for c in per.values())
+        for k, c in sorted(per.items(), key=lambda kv: -kv[1]["ms"]):
+            print(f"{k:40s} {c['n'] // reps:4d} launches {c['ms'] / reps:9.3f} ms {100 * c['ms'] / tot:5.1f}%  "
+                  f"{c['flops'] / c['ms'] / 1e9:8.1f} TFLOP/s {c['bytes'] / c['ms'] / 1e6:8.1f} GB/s", file=sys.stderr)
+        for r in runs[-1]:
+            print(f"  {r['name']:48s} {r['kernel']:38s} {r['ms']:8.3f} ms {r['flops'] / max(r['ms'], 1e-6) / 1e9:8.1f} TF "
+                  f"{r['bytes'] / max(r['ms'], 1e-6) / 1e6:8.1f} GB/s", file=sys.stderr)
+    dom_name, dom = max(per.items(), key=lambda kv: kv[1]["ms"])
+    dom_raw = sum(sorted(r[i]["ms_raw"] for r in runs)[reps // 2] * reps for i, row in enumerate(runs[0]) if row["kernel"] == dom_name)
+    executed_flops = sum(c["flops"] for c in per.values()) / reps      # of one B-frame forward, as launched
+    tf = dom["flops"] / dom["ms"] / 1e9
+    gbs = dom["bytes"] / dom["ms"] / 1e6
+    mfma_peak = MFMA_F32_PEAK_TF if args.dtype == "f32" else MFMA_BF16_PEAK_TF
+    mfma_bound = dom_name.startswith(("pw_gemm", "ir_fused")) and tf / mfma_peak >= gbs / HBM_PEAK_GBS
+    tag = f"{PROFILE_TAG}_{'f32_b64' if args.dtype == 'f32' else 'bf16_b512'}"
+    roofline = {
+        "kernel": dom_name,
+        "bound": "mfma" if mfma_bound else "hbm",
+        "achieved": round(tf if mfma_bound else gbs, 2),
+        "peak": mfma_peak if mfma_bound else HBM_PEAK_GBS,
+        "unit": "TFLOP/s" if mfma_bound else "GB/s",
+        "frac": round((tf / mfma_peak) if mfma_bound else (gbs / HBM_PEAK_GBS), 4),
+        "traffic": None,
+        "algorithmic_bytes_per_launch": round(dom["bytes"] / dom["n"]),
+        "algorithmic_gflop_per_launch": round(dom["flops"] / dom["n"] / 1e9, 3),
+        "launches_per_step": dom["n"] // reps,
+        "avg_launch_ms": round(dom["ms"] / dom["n"], 4),
+        # share of the SERIALISED replay's kernel time (the timed two-lane step overlaps kernels, so it is shorter
+        # than the replay and a kernel runs slower inside it)
+        "share_of_replay": round(dom["ms"] / sum(c["ms"] for c in per.values()), 3),
+        "avg_launch_ms_raw": round(dom_raw / dom["n"], 4),     # the event pairs as measured (ADVICE r3: both are printed)
+        "measured": "HIP events around every launch (minus the calibrated cost of an empty event pair); the timed "
+                    "run's own launches (same lanes, tiles, grids) serialised on one stream; "
+                    f"profiles/{tag}_kernel_stats_replay.csv is rocprofv3 --kernel-trace --stats of `bench.py --replay-only`",
+    }
+    # HBM-side bytes and MFMA-busy of that kernel from the committed PMC passes (tools/collect_profiles.sh
+    # with --replay-only, i.e. these same launches; the counters are per launch, so they do not depend on
+    # the step count).  Only for the two configurations the passes were collected on.
+    # They are quoted only when they were collected from THIS version of the kernels (source_hash), else null + why.
+    from calipsync_amd import build as _build
+    src_hash = _build.source_hash()
+    roofline["source_hash"] = src_hash
+    default_cfg = (args.dtype == "f32" and B == 64) or (args.dtype == "bf16" and B == 512)
+    moved_per_frame = moved_missing = None
+    if default_cfg:
+        pmc, why = load_profile_json("pmc_traffic" if args.dtype == "f32" else "pmc_traffic_bf16_b512", src_hash)
+        if pmc and dom_name in pmc["kernels"]:
+            roofline["traffic"] = pmc["kernels"][dom_name]["hbm_bytes_per_launch"]
+            roofline["traffic_source"] = pmc["source"]
+        else:
+            roofline["traffic_source"] = why or f"{dom_name} not in the PMC summary"
+        if pmc:
+            moved_per_frame, moved_missing = hbm_moved_per_frame(pmc, {k: c["n"] // reps for k, c in per.items()}, B)
+        busy, why = load_profile_json("mfma_busy" if args.dtype == "f32" else "mfma_busy_bf16_b512", src_hash)
+        if busy and dom_name in busy["kernels"]:
+            # the matrix pipes' busy cycles over the kernel's duration in the TRACE pass at the clock the peak is quoted at
+            # (>= achieved / peak by construction); the PMC pass itself runs the kernel slower: both are printed
+            bk = busy["kernels"][dom_name]
+            roofline["mfma_busy"] = bk.get("mfma_busy_of_trace_time", bk["mfma_busy_of_kernel_time"])
+            roofline["mfma_busy_pmc_pass"] = bk["mfma_busy_of_kernel_time"]
+            roofline["pmc_pass_slowdown"] = bk.get("pmc_pass_slowdown")
+            roofline["mfma_busy_source"] = busy["source"]
+        else:
+            roofline["mfma_busy"] = None
+            roofline["mfma_busy_source"] = why or f"{dom_name} not in the PMC summary"
+        avg_us, why = rocprof_avg_us(tag, dom_name, src_hash)
+        roofline["avg_kernel_us_rocprof"] = avg_us
+        if avg_us is None:
+            roofline["avg_kernel_us_rocprof_source"] = why
+        else:
+            roofline["frac_rocprof"] = round(dom["flops"] / dom["n"] / (avg_us * 1e-6) / 1e12 / mfma_peak, 4) if mfma_bound \
+                else round(dom["bytes"] / dom["n"] / (avg_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
+    work = arch.work_per_frame()
+    canon_bytes = work["canonical_bytes_f32"] // (1 if args.dtype == "f32" else 2)
+    stage = arch.stagewise_bound(mfma_peak * 1e12, HBM_PEAK_GBS * 1e9, 4 if args.dtype == "f32" else 2)
+    whole_net = {"mfma_frac": round(per_gpu * work["flops"] / (mfma_peak * 1e12), 4),
+                 "hbm_frac_canonical": round(per_gpu * canon_bytes / (HBM_PEAK_GBS * 1e9), 4),
+                 "gflop_per_frame": round(work["flops"] / 1e9, 3),
+                 # mfma_frac is quoted on the REFERENCE's flops (SURVEY 8d).  The engine executes fewer: with
+                 # ups_commute the upsampled half of every Up block's expand conv runs at a quarter of the pixels
+                 # (up(W1a.lo) = W1a.up(lo)).  What the matrix pipes actually did:
+                 "executed_gflop_per_frame": round(executed_flops / B / 1e9, 3),
+                 "mfma_frac_executed": round(per_gpu * executed_flops / B / (mfma_peak * 1e12), 4),
+                 # the granularity the kernels implement (SURVEY 8d): HBM bytes the fused engine really moves per
+                 # frame (PMC, hash-gated like roofline.traffic) and the share of the HBM roof that is; the
+                 # canonical figures around it are quoted on UN-FUSED conv-granularity bytes (context only)
+                 "hbm_bytes_moved_per_frame": None if moved_per_frame is None else round(moved_per_frame),
+                 "hbm_frac_moved": None if moved_per_frame is None else
+                 round(per_gpu * moved_per_frame / (HBM_PEAK_GBS * 1e9), 4),
+                 **({"hbm_moved_missing_kernels": moved_missing} if moved_missing else {}),
+                 "canonical_mb_per_frame": round(canon_bytes / 1e6, 2),
+                 # SURVEY 8(d): per stage max(canonical bytes / 8 TB/s, flops / matrix peak), summed
+                 "stagewise_bound_fps_per_gpu": round(stage["frames_per_s"], 1),
+                 "frac_of_stagewise_bound": round(per_gpu / stage["frames_per_s"], 4)}
+    return roofline, whole_net
+
+
+DUMP_BUDGET_BYTES = 60_000_000       # --dump-outputs writes at most 64 MB
+
+
+def dump_outputs(out_dir: str, out) -> None:
+    """--dump-outputs: `out` is what the timed path returned in its last step, the whole job's [N, 3, 160, 160] fp32
+    frames.  Written to out_dir/out.npy in float32; an output above the budget is replaced by a fixed, seeded sample
+    of whole frames (numpy default_rng(0), kept in frame order), so that two builds given the same arguments write the
+    same frames."""
+    import numpy as np
+    arr = out.detach().float().cpu().numpy()
+    if arr.nbytes > DUMP_BUDGET_BYTES:
+        keep = DUMP_BUDGET_BYTES // arr[0].nbytes
+        arr = arr[np.sort(np.random.default_rng(0).choice(arr.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "out.npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def main():
@@ -483,15 +630,24 @@ def main():
         dt = max_over_ranks(time.perf_counter() - t0)
         assert torch.isfinite(out).all()
 
-    # ---- N > 1: BASELINE configs[3] beside the weak point -- a fixed 4096-frame job split over the
+    # ---- what the timed path returned in its last step: the whole job's frames (gathered from the ranks)
+    if args.dump_outputs:
+        if world > 1:
+            mine = out.cpu() if shared else out
+            parts = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(parts, mine)
+            out = torch.cat(parts)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, out)
+
+    # ---- --full, N > 1: BASELINE configs[3] beside the weak point -- a fixed 4096-frame job split over the
     #      ranks, each rank walking its contiguous shard in chunks of <= 512 frames (the per-GPU size
     #      configs[3] names; one arena serves every chunk).  Same timing contract: barrier + sync on
     #      both sides, max over ranks.  Inputs are the weak leg's frames tiled (timing is data-blind).
     strong = None
-    if world > 1 and args.strong_frames and not args.global_batch and not args.replay_only:
+    if args.full and world > 1 and args.strong_frames and not args.global_batch and not args.replay_only:
         strong = strong_leg(net, x, a, args.strong_frames, rank, world, max(2, args.steps // 4), sync, max_over_ranks, args.dtype)
 
-    # ---- per-kernel timing with HIP events on the launch stream (rank 0)
     result = None
     lanes = net.get_option("lanes")
     plan16 = net.get_option("bf16_plan")
@@ -499,98 +655,8 @@ def main():
         lanes = 3                   # the bf16 engine's large-batch plan (engine.hip run_forward): three lanes, gemm_ring128, overlap 0
     trunk_lanes = net.get_option("trunk_lanes")
     if rank == 0:
-        per = {}
-        reps = args.steps if args.replay_only else 3
-        # The timed region overlaps the sub-batch lanes (and the audio streams) on the GPU, so
-        # per-kernel durations there are not separable.  The roofline pass replays the SAME launches
-        # (same lanes, hence the same kernels, tile choices and grids) serialised on one stream with
-        # an event pair around each (casync_profile_forward).
-        # every launch is timed `reps` times; its figure is the MEDIAN of those (one slow launch -- a cold instruction
-        # cache, a clock dip -- otherwise moves a whole kernel family's average), counted `reps` times so that the
-        # sums below keep their meaning
-        runs = [net.profile(x, a) for _ in range(reps)]
-        for i, row in enumerate(runs[0]):
-            ms = sorted(r[i]["ms"] for r in runs)[reps // 2]
-            c = per.setdefault(row["kernel"], {"ms": 0.0, "flops": 0.0, "bytes": 0.0, "n": 0})
-            c["ms"] += ms * reps; c["flops"] += row["flops"] * reps; c["bytes"] += row["bytes"] * reps; c["n"] += reps
-        if args.kernel_table:
-            tot = sum(c["ms"] for c in per.values())
-            for k, c in sorted(per.items(), key=lambda kv: -kv[1]["ms"]):
-                print(f"{k:40s} {c['n'] // reps:4d} launches {c['ms'] / reps:9.3f} ms {100 * c['ms'] / tot:5.1f}%  "
-                      f"{c['flops'] / c['ms'] / 1e9:8.1f} TFLOP/s {c['bytes'] / c['ms'] / 1e6:8.1f} GB/s", file=sys.stderr)
-            for r in runs[-1]:
-                print(f"  {r['name']:48s} {r['kernel']:38s} {r['ms']:8.3f} ms {r['flops'] / max(r['ms'], 1e-6) / 1e9:8.1f} TF "
-                      f"{r['bytes'] / max(r['ms'], 1e-6) / 1e6:8.1f} GB/s", file=sys.stderr)
-        dom_name, dom = max(per.items(), key=lambda kv: kv[1]["ms"])
-        dom_raw = sum(sorted(r[i]["ms_raw"] for r in runs)[reps // 2] * reps for i, row in enumerate(runs[0]) if row["kernel"] == dom_name)
-        executed_flops = sum(c["flops"] for c in per.values()) / reps      # of one B-frame forward, as launched
-        tf = dom["flops"] / dom["ms"] / 1e9
-        gbs = dom["bytes"] / dom["ms"] / 1e6
-        mfma_peak = MFMA_F32_PEAK_TF if args.dtype == "f32" else MFMA_BF16_PEAK_TF
-        mfma_bound = dom_name.startswith(("pw_gemm", "ir_fused")) and tf / mfma_peak >= gbs / HBM_PEAK_GBS
-        tag = f"{PROFILE_TAG}_{'f32_b64' if args.dtype == 'f32' else 'bf16_b512'}"
-        roofline = {
-            "kernel": dom_name,
-            "bound": "mfma" if mfma_bound else "hbm",
-            "achieved": round(tf if mfma_bound else gbs, 2),
-            "peak": mfma_peak if mfma_bound else HBM_PEAK_GBS,
-            "unit": "TFLOP/s" if mfma_bound else "GB/s",
-            "frac": round((tf / mfma_peak) if mfma_bound else (gbs / HBM_PEAK_GBS), 4),
-            "traffic": None,
-            "algorithmic_bytes_per_launch": round(dom["bytes"] / dom["n"]),
-            "algorithmic_gflop_per_launch": round(dom["flops"] / dom["n"] / 1e9, 3),
-            "launches_per_step": dom["n"] // reps,
-            "avg_launch_ms": round(dom["ms"] / dom["n"], 4),
-            # share of the SERIALISED replay's kernel time (the timed two-lane step overlaps kernels, so it is shorter
-            # than the replay and a kernel runs slower inside it)
-            "share_of_replay": round(dom["ms"] / sum(c["ms"] for c in per.values()), 3),
-            "avg_launch_ms_raw": round(dom_raw / dom["n"], 4),     # the event pairs as measured (both are printed)
-            "measured": "HIP events around every launch (minus the calibrated cost of an empty event pair); the timed "
-                        "run's own launches (same lanes, tiles, grids) serialised on one stream; "
-                        f"profiles/{tag}_kernel_stats_replay.csv is rocprofv3 --kernel-trace --stats of `bench.py --replay-only`",
-        }
-        # HBM-side bytes and MFMA-busy of that kernel from the committed PMC passes (tools/collect_profiles.sh
-        # with --replay-only, i.e. these same launches; the counters are per launch, so they do not depend on
-        # the step count).  Only for the two configurations the passes were collected on.
-        # They are quoted only when they were collected from THIS version of the kernels (source_hash), else null + why.
-        from calipsync_amd import build as _build
-        src_hash = _build.source_hash()
-        roofline["source_hash"] = src_hash
-        default_cfg = (args.dtype == "f32" and B == 64) or (args.dtype == "bf16" and B == 512)
-        moved_per_frame = moved_missing = None
-        if default_cfg:
-            pmc, why = load_profile_json("pmc_traffic" if args.dtype == "f32" else "pmc_traffic_bf16_b512", src_hash)
-            if pmc and dom_name in pmc["kernels"]:
-                roofline["traffic"] = pmc["kernels"][dom_name]["hbm_bytes_per_launch"]
-                roofline["traffic_source"] = pmc["source"]
-            else:
-                roofline["traffic_source"] = why or f"{dom_name} not in the PMC summary"
-            if pmc:
-                moved_per_frame, moved_missing = hbm_moved_per_frame(pmc, {k: c["n"] // reps for k, c in per.items()}, B)
-            busy, why = load_profile_json("mfma_busy" if args.dtype == "f32" else "mfma_busy_bf16_b512", src_hash)
-            if busy and dom_name in busy["kernels"]:
-                # the matrix pipes' busy cycles over the kernel's duration in the TRACE pass at the clock the peak is quoted at
-                # (>= achieved / peak by construction); the PMC pass itself runs the kernel slower: both are printed
-                bk = busy["kernels"][dom_name]
-                roofline["mfma_busy"] = bk.get("mfma_busy_of_trace_time", bk["mfma_busy_of_kernel_time"])
-                roofline["mfma_busy_pmc_pass"] = bk["mfma_busy_of_kernel_time"]
-                roofline["pmc_pass_slowdown"] = bk.get("pmc_pass_slowdown")
-                roofline["mfma_busy_source"] = busy["source"]
-            else:
-                roofline["mfma_busy"] = None
-                roofline["mfma_busy_source"] = why or f"{dom_name} not in the PMC summary"
-            avg_us, why = rocprof_avg_us(tag, dom_name, src_hash)
-            roofline["avg_kernel_us_rocprof"] = avg_us
-            if avg_us is None:
-                roofline["avg_kernel_us_rocprof_source"] = why
-            else:
-                roofline["frac_rocprof"] = round(dom["flops"] / dom["n"] / (avg_us * 1e-6) / 1e12 / mfma_peak, 4) if mfma_bound \
-                    else round(dom["bytes"] / dom["n"] / (avg_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
-        work = arch.work_per_frame()
-        canon_bytes = work["canonical_bytes_f32"] // (1 if args.dtype == "f32" else 2)
         fps = world * B * args.steps / dt
         per_gpu = fps / world
-        stage = arch.stagewise_bound(mfma_peak * 1e12, HBM_PEAK_GBS * 1e9, 4 if args.dtype == "f32" else 2)
         two_lane = B >= 16 * lanes and lanes > 1
         result = {
             "metric": "160x160 lip-sync frames/sec (whole node)",
@@ -617,34 +683,18 @@ def main():
                        **({"rehearsal": f"{world} ranks share {n_dev} GPU(s), gloo"} if shared else {}),
                        **({"strong_scaling": strong} if strong else {})},
             **({"replay_only": "serialised replays only: value is NOT the two-lane rate"} if args.replay_only else {}),
-            "roofline": roofline,
-            "whole_net": {"mfma_frac": round(per_gpu * work["flops"] / (mfma_peak * 1e12), 4),
-                          "hbm_frac_canonical": round(per_gpu * canon_bytes / (HBM_PEAK_GBS * 1e9), 4),
-                          "gflop_per_frame": round(work["flops"] / 1e9, 3),
-                          # mfma_frac is quoted on the REFERENCE's flops.  The engine executes fewer: with
-                          # ups_commute the upsampled half of every Up block's expand conv runs at a quarter of the pixels
-                          # (up(W1a.lo) = W1a.up(lo)).  What the matrix pipes actually did:
-                          "executed_gflop_per_frame": round(executed_flops / B / 1e9, 3),
-                          "mfma_frac_executed": round(per_gpu * executed_flops / B / (mfma_peak * 1e12), 4),
-                          # the granularity the kernels implement: HBM bytes the fused engine really moves per
-                          # frame (PMC, hash-gated like roofline.traffic) and the share of the HBM roof that is; the
-                          # canonical figures around it are quoted on UN-FUSED conv-granularity bytes (context only)
-                          "hbm_bytes_moved_per_frame": None if moved_per_frame is None else round(moved_per_frame),
-                          "hbm_frac_moved": None if moved_per_frame is None else
-                          round(per_gpu * moved_per_frame / (HBM_PEAK_GBS * 1e9), 4),
-                          **({"hbm_moved_missing_kernels": moved_missing} if moved_missing else {}),
-                          "canonical_mb_per_frame": round(canon_bytes / 1e6, 2),
-                          # per stage max(canonical bytes / 8 TB/s, flops / matrix peak), summed
-                          "stagewise_bound_fps_per_gpu": round(stage["frames_per_s"], 1),
-                          "frac_of_stagewise_bound": round(per_gpu / stage["frames_per_s"], 4)},
         }
-        if world == 1 and args.dtype == "f32" and not args.no_secondary and not args.replay_only and not args.global_batch:
+        # ---- per-kernel timing with HIP events on the launch stream (--full; --kernel-table and --replay-only need it too)
+        if args.full or args.kernel_table or args.replay_only:
+            result["roofline"], result["whole_net"] = per_kernel_pass(net, x, a, args, B, per_gpu)
+        if args.full and world == 1 and args.dtype == "f32" and not args.no_secondary and not args.replay_only \
+                and not args.global_batch:
             from calipsync_amd import build as _build
             result["secondary"] = secondary_block(net, packed, x, a, dev, _build.source_hash())
         if args.e2e and world == 1:    # measured once per run: the secondary block's figure when it exists
             from calipsync_amd import frame_bench
             result["config"]["e2e"] = result["secondary"]["e2e"] if "secondary" in result else frame_bench.run(net, dev, batch=B)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(sd_np, args.cpu_seconds)
     if world > 1:
         dist.barrier()

@@ -84,7 +84,9 @@ def mlp_fusion(sd, x5: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
     """MLPFusion.forward (module/unet.py:233-249): per-pixel 2-layer MLP on
     cat(x5, a); BN1d over the channel axis; no activation after the 2nd BN."""
     b, c, h, w = x5.shape
-    t = torch.cat([x5.reshape(b, c, h * w), a.reshape(b, c, h * w)], 1).transpose(1, 2)  # [B,HW,2C]
+    # [B,HW,2C] built as the reference builds it (each input transposed, then joined on the last axis): a contiguous
+    # fc1 operand, so F.linear takes the same GEMM path as the reference and rounds as it does on every host
+    t = torch.cat([x5.reshape(b, c, h * w).transpose(1, 2), a.reshape(b, c, h * w).transpose(1, 2)], 2)
     t = F.linear(t, sd["mlp_fusion.fc1.weight"], sd["mlp_fusion.fc1.bias"])
     t = _act(_bn(sd, "mlp_fusion.bn1", t.transpose(1, 2)).transpose(1, 2))
     t = F.linear(t, sd["mlp_fusion.fc2.weight"], sd["mlp_fusion.fc2.bias"])

@@ -58,7 +58,7 @@ def test_bench_launches_its_own_ranks():
     one JSON line from rank 0, exit code 0."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--batch", "16", "--strong-frames", "64", "--no-cpu-baseline"],
+                          "--batch", "16", "--strong-frames", "64", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, env=env, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -79,7 +79,7 @@ def test_bench_rehearses_a_many_rank_launch():
     the 4096-over-8 split and `tests/test_bench_launcher.py` the N = 8 watchdog on the CPU)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "5", "--steps", "2", "--warmup", "1",
-                          "--batch", "8", "--strong-frames", "320", "--no-cpu-baseline"],
+                          "--batch", "8", "--strong-frames", "320", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, env=env, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

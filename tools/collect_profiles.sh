@@ -22,12 +22,12 @@ cd /tmp && export TMPDIR=/tmp
 hash=$(cd $R && python3 -c "from calipsync_amd.build import source_hash; print(source_hash())")
 rocprofv3 --kernel-trace --stats -d $out/replay --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-secondary --replay-only --steps 10 --warmup 3 $extra > $out/replay.log 2>&1
 echo "stats replay done"
-rocprofv3 --kernel-trace --stats -d $out/timed --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-secondary --steps 10 --warmup 3 $extra > $out/timed.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/timed --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-secondary --steps 10 --warmup 3 $extra > $out/timed.log 2>&1
 echo "stats timed done"
 for m in replay timed; do
   f=$(find $out/$m -name "*kernel_stats.csv" | head -1)
   cp $f $dst/${tag}_${cfg}_kernel_stats_$m.csv
-  echo "{\"source_hash\": \"$hash\", \"command\": \"rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-secondary $([ $m = replay ] && echo --replay-only) --steps 10 --warmup 3 $extra\"}" > $dst/${tag}_${cfg}_kernel_stats_$m.meta.json
+  echo "{\"source_hash\": \"$hash\", \"command\": \"rocprofv3 --kernel-trace --stats -- python3 bench.py $([ $m = timed ] && echo --full) --no-cpu-baseline --no-secondary $([ $m = replay ] && echo --replay-only) --steps 10 --warmup 3 $extra\"}" > $dst/${tag}_${cfg}_kernel_stats_$m.meta.json
 done
 rocprofv3 --pmc FETCH_SIZE -d $out/pmc_fetch --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-secondary --replay-only --steps 2 --warmup 1 $extra > $out/pmc_fetch.log 2>&1
 echo "pmc fetch done"
@@ -42,8 +42,8 @@ find $out $R/gpurun_out/pmc_busy_${tag}_$dt -name "*.csv" -size +5M -delete
 mkdir -p $R/profiles && cp $dst/${tag}_* $R/profiles/
 cd $R
 if [ "$dt" = f32 ]; then
-  python3 bench.py --e2e --kernel-table > $dst/${tag}_bench.json 2> $dst/${tag}_launch_table.txt
+  python3 bench.py --full --e2e --kernel-table > $dst/${tag}_bench.json 2> $dst/${tag}_launch_table.txt
 else
-  python3 bench.py --dtype bf16 --kernel-table > $dst/${tag}_bench_bf16_b512.json 2> $dst/${tag}_launch_table_bf16_b512.txt
+  python3 bench.py --full --dtype bf16 --kernel-table > $dst/${tag}_bench_bf16_b512.json 2> $dst/${tag}_launch_table_bf16_b512.txt
 fi
 ls -la $dst

@@ -14,8 +14,8 @@ tail -3 $O/pytest_gpu.log
 CASYNC_LIB=$BASE timeout -k 10 200 python tools/microbench.py ir --batch 32 > $O/ir_base.log 2>&1
 timeout -k 10 200 python tools/microbench.py ir --batch 32 > $O/ir_new.log 2>&1
 paste -d'\n' $O/ir_base.log $O/ir_new.log
-CASYNC_LIB=$BASE timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_base.json 2> $O/bench_base.err
-timeout -k 10 300 python bench.py --no-cpu-baseline --kernel-table > $O/bench_new.json 2> $O/bench_new.err
+CASYNC_LIB=$BASE timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_base.json 2> $O/bench_base.err
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --kernel-table > $O/bench_new.json 2> $O/bench_new.err
 python - <<PY
 import json
 for t in ("base", "new"):

@@ -7,7 +7,7 @@ timeout -k 10 500 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; rc=
 tail -4 $O/pytest_gpu.log
 [ $rc -ne 0 ] && grep -E "^(FAILED|ERROR)" $O/pytest_gpu.log | head -20
 for m in 0 1; do
-CASYNC_FUSE_DW=$m timeout -k 10 300 python bench.py --no-cpu-baseline --no-secondary --kernel-table > $O/bench_dw$m.json 2> $O/bench_dw$m.err
+CASYNC_FUSE_DW=$m timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-secondary --kernel-table > $O/bench_dw$m.json 2> $O/bench_dw$m.err
 done
 python - <<PY
 import json
