@@ -29,6 +29,11 @@ _PROTOS = {
     "casync_packed_offset": (c_i64, [C.c_int]),
     "casync_packed_size": (c_i64, [C.c_int]),
     "casync_packed_total": (c_i64, []),
+    "casync_packed_count_m": (C.c_int, [C.c_int]),
+    "casync_packed_name_m": (C.c_char_p, [C.c_int, C.c_int]),
+    "casync_packed_offset_m": (c_i64, [C.c_int, C.c_int]),
+    "casync_packed_size_m": (c_i64, [C.c_int, C.c_int]),
+    "casync_packed_total_m": (c_i64, [C.c_int]),
     "casync_workspace_bytes": (c_i64, [C.c_int]),
     "casync_workspace_bytes_dt": (c_i64, [C.c_int, C.c_int]),
     "casync_workspace_bytes_h": (c_i64, [C.c_void_p, C.c_int]),
@@ -36,6 +41,7 @@ _PROTOS = {
     "casync_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
     "casync_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "casync_create_ex": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "casync_create_mode": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "casync_destroy": (None, [C.c_void_p]),
     "casync_load_weights_host": (C.c_int, [C.c_void_p, C.c_void_p, c_i64]),
     "casync_load_weights_device": (C.c_int, [C.c_void_p, c_f32p, c_i64]),
@@ -76,6 +82,8 @@ _PROTOS = {
                                             C.c_void_p]),
     "casync_op_conv3x3": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_conv3x3_ex": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_audio_windows": (C.c_int, [c_f32p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_crop_to_input": (C.c_int, [C.c_void_p, c_f32p, C.c_int, C.c_void_p]),
     "casync_op_pred_to_u8": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -89,7 +97,7 @@ _PROTOS = {
 }
 
 EXPORTS = tuple(_PROTOS)
-ABI_VERSION = 6          # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
+ABI_VERSION = 7          # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
 
 
 def lib_path() -> str:
@@ -151,10 +159,20 @@ def check(status: int, what: str) -> int:
     return status
 
 
-def packed_layout():
-    """[(name, offset, size)] in floats, and the total -- the engine owns the layout."""
+# audio encoders (include/casync_hip.h CASYNC_AUDIO_*): the reference Model's `mode`
+AUDIO_MODES = {"hubert": 0, "wenet": 1}
+
+
+def packed_layout(mode: str = "hubert"):
+    """[(name, offset, size)] in floats, and the total, of one audio mode -- the engine owns the layout."""
     lib = load()
-    n = lib.casync_packed_count()
-    items = [(lib.casync_packed_name(i).decode(), lib.casync_packed_offset(i),
-              lib.casync_packed_size(i)) for i in range(n)]
-    return items, lib.casync_packed_total()
+    m = AUDIO_MODES[mode]
+    if m == 0:
+        n = lib.casync_packed_count()
+        items = [(lib.casync_packed_name(i).decode(), lib.casync_packed_offset(i),
+                  lib.casync_packed_size(i)) for i in range(n)]
+        return items, lib.casync_packed_total()
+    n = lib.casync_packed_count_m(m)
+    items = [(lib.casync_packed_name_m(m, i).decode(), lib.casync_packed_offset_m(m, i),
+              lib.casync_packed_size_m(m, i)) for i in range(n)]
+    return items, lib.casync_packed_total_m(m)

@@ -21,6 +21,10 @@ from typing import Iterator, List, Tuple
 CH = (32, 64, 128, 256, 512)
 FACE_HW = 160          # face crop is 160x160 (reference infer_api.py:238)
 AUDIO_HW = 32          # HuBERT window reshaped to [32,32,32] (infer_api.py:134)
+# per-frame audio tensor of each audio encoder (reference Model(6, mode), module/unet.py:281-284): HuBERT windows, and the
+# WeNet windows the reference dataset reshapes to (256, 16, 32) (dataset/dataset.py:173-174)
+AUDIO_SHAPE = {"hubert": (32, 32, 32), "wenet": (256, 16, 32)}
+MODES = tuple(AUDIO_SHAPE)
 EXPAND = 2             # expand_ratio used by every block in this model
 BN_EPS = 1e-5          # nn.BatchNorm default, eval mode
 LRELU_SLOPE = 0.01     # nn.LeakyReLU default slope
@@ -38,11 +42,16 @@ class IRBlock:
     cout: int
     stride: int
     res: bool
-    hw_in: int       # input spatial size (square)
+    hw_in: int       # input height (and width, for a square frame)
+    w_in: int = 0    # input width when it differs from the height (AudioConvWenet's 16x32 blocks); 0 = square
 
     @property
     def cexp(self) -> int:
         return self.cin * EXPAND
+
+    @property
+    def wd_in(self) -> int:
+        return self.w_in or self.hw_in
 
     @property
     def hw_out(self) -> int:
@@ -67,11 +76,23 @@ def face_encoder() -> List[List[IRBlock]]:
     return stages
 
 
-def audio_encoder_blocks() -> dict:
-    """``AudioConvHubert`` (module/unet.py:147-194)."""
+def _check_mode(mode: str) -> None:
+    if mode not in MODES:
+        raise ValueError(f"audio mode {mode!r}: one of {MODES}")
+
+
+def audio_encoder_blocks(mode: str = "hubert") -> dict:
+    """``AudioConvHubert`` (module/unet.py:147-194) or ``AudioConvWenet`` (module/unet.py:109-144: conv1 / conv2 are
+    256 -> 512 -> 256 residual blocks on 16x32 frames; conv3 is (1, 2)-strided, conv4 / conv6 / conv7 as in HuBERT)."""
+    _check_mode(mode)
+    if mode == "wenet":
+        first = {"conv1": IRBlock("audio_model.conv1", CH[3], CH[3], 1, True, 16, 32),
+                 "conv2": IRBlock("audio_model.conv2", CH[3], CH[3], 1, True, 16, 32)}
+    else:
+        first = {"conv1": IRBlock("audio_model.conv1", 32, CH[1], 1, False, 32),
+                 "conv2": IRBlock("audio_model.conv2", CH[1], CH[2], 1, False, 32)}
     return {
-        "conv1": IRBlock("audio_model.conv1", 32, CH[1], 1, False, 32),
-        "conv2": IRBlock("audio_model.conv2", CH[1], CH[2], 1, False, 32),
+        **first,
         # conv3: dense 3x3 s2 p1 128->256, 32->16 ; bn3 ; LeakyReLU
         "conv4": IRBlock("audio_model.conv4", CH[3], CH[3], 1, True, 16),
         # conv5: dense 3x3 s2 p3 256->512, 16->10 ; bn5 ; LeakyReLU
@@ -93,9 +114,9 @@ def decoder() -> List[List[IRBlock]]:
     return [_double(f"{n}.conv", cin, cout, 1, hw) for n, cin, cout, hw in spec]
 
 
-def all_ir_blocks() -> List[IRBlock]:
+def all_ir_blocks(mode: str = "hubert") -> List[IRBlock]:
     """Every IR block in ``state_dict`` registration order of the reference."""
-    a = audio_encoder_blocks()
+    a = audio_encoder_blocks(mode)
     out = [a["conv1"], a["conv2"], a["conv4"], a["conv6"], a["conv7"]]
     out += fuse_blocks()
     for st in face_encoder():
@@ -135,22 +156,24 @@ def _ir(b: IRBlock) -> Iterator[Entry]:
     yield from _bn(f"{p}.7", b.cout)
 
 
-def manifest() -> List[Entry]:
-    """The 582 ``state_dict`` entries, in the reference's registration order
+def manifest(mode: str = "hubert") -> List[Entry]:
+    """The 582 ``state_dict`` entries (wenet: 577, no ``audio_model.bn7``), in the reference's registration order
     (module/unet.py:281-312: audio_model, fuse_conv, inc, down1-4, up1-4, outc,
     outc_bn, mlp_fusion, attention_blocks, bn_kx, bn_tx)."""
     out: List[Entry] = []
-    a = audio_encoder_blocks()
+    a = audio_encoder_blocks(mode)
+    wenet = mode == "wenet"
     out += _ir(a["conv1"])
     out += _ir(a["conv2"])
-    out += _conv("audio_model.conv3", CH[3], CH[2], 3, True)
+    out += _conv("audio_model.conv3", CH[3], CH[3] if wenet else CH[2], 3, True)
     out += _bn("audio_model.bn3", CH[3])
     out += _ir(a["conv4"])
     out += _conv("audio_model.conv5", CH[4], CH[3], 3, True)
     out += _bn("audio_model.bn5", CH[4])
     out += _ir(a["conv6"])
     out += _ir(a["conv7"])
-    out += _bn("audio_model.bn7", CH[4])
+    if not wenet:
+        out += _bn("audio_model.bn7", CH[4])
     for b in fuse_blocks():
         out += _ir(b)
     for st in face_encoder():

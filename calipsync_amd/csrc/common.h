@@ -211,7 +211,7 @@ struct GemmEpilogue {
   const void* pre_res = nullptr;     // (T) [M, ld_pre]  added before the activation ...
   const float* pre_scale = nullptr;  // [N]          ... scaled per column (null = 1)
   int ld_pre = 0;
-  int act = 0;                       // LeakyReLU(0.01)
+  int act = 0;                       // 1 = LeakyReLU(0.01), 2 = ReLU (AudioConvWenet's conv3 / conv5)
   const void* post_res = nullptr;    // (T) [M, ld_post] added after the activation
   int ld_post = 0;
   const float* aff_s = nullptr;      // [N] v = lrelu(v*aff_s + aff_t) on the OUTPUT (aff_on_acc=0)
@@ -235,9 +235,9 @@ struct GemmEpilogue {
   // favours many small workgroups that interleave on a CU over few large ones (see pick_cfg)
   int concurrent = 0;
   // implicit-GEMM 3x3 convolution (conv_on): A is the NHWC input [B,H,W,C]; row m of the GEMM is output
-  // pixel (b, oy, ox), column k = (ky*3 + kx)*C + c reads in[b, oy*stride+ky-pad, ox*stride+kx-pad, c]
+  // pixel (b, oy, ox), column k = (ky*3 + kx)*C + c reads in[b, oy*conv_sh+ky-pad, ox*conv_sw+kx-pad, c]
   // (zero outside the image); W is [N][(ky,kx,c)].  K = 9*C, C a multiple of the 128-B k-tile.
-  int conv_on = 0, conv_h = 0, conv_w = 0, conv_c = 0, conv_ho = 0, conv_wo = 0, conv_stride = 0, conv_pad = 0;
+  int conv_on = 0, conv_h = 0, conv_w = 0, conv_c = 0, conv_ho = 0, conv_wo = 0, conv_sh = 0, conv_sw = 0, conv_pad = 0;
 };
 constexpr int kStreamKWgs = 256;                                  // stream-K workgroups (one per CU)
 constexpr long long kStreamKFloats = 2ll * kStreamKWgs * 128 * 64;  // two partial tiles per workgroup, up to 128x64
@@ -250,13 +250,13 @@ const char* pw_gemm_kernel_name(int m, int n, int k, bool stream_k, int dtype = 
 int launch_pw_gemm(const void* a, int lda, const void* w, void* c, int ldc, int m, int n, int k,
                    const GemmEpilogue& epi, hipStream_t stream, int dtype = DT_F32);
 
-// dense 3x3 convolution + bias (+ LeakyReLU if epi.act) as an implicit GEMM on the ring kernel: no im2col
-// buffer, the taps are gathered by the LDS-DMA loads themselves.  in: [B,H,W,cin] contiguous NHWC,
-// w: [cout][(ky,kx,cin)], out: [B*Ho*Wo, ldc].
+// dense 3x3 convolution + bias (+ the activation epi.act: LeakyReLU or ReLU) as an implicit GEMM on the ring kernel: no
+// im2col buffer, the taps are gathered by the LDS-DMA loads themselves.  in: [B,H,W,cin] contiguous NHWC,
+// w: [cout][(ky,kx,cin)], out: [B*Ho*Wo, ldc]; stride_h / stride_w apart (AudioConvWenet's conv3 is (1, 2)).
 int launch_conv3x3_gemm(const void* in, const void* w, void* out, int ldc, int batch, int h, int wdt, int cin,
-                        int cout, int stride, int pad, const GemmEpilogue& epi, hipStream_t stream,
+                        int cout, int stride_h, int stride_w, int pad, const GemmEpilogue& epi, hipStream_t stream,
                         int dtype = DT_F32);
-const char* conv3x3_gemm_kernel_name(int batch, int h, int wdt, int cin, int cout, int stride, int pad,
+const char* conv3x3_gemm_kernel_name(int batch, int h, int wdt, int cin, int cout, int stride_h, int stride_w, int pad,
                                      int dtype = DT_F32, bool concurrent = false, bool stream_k = false);
 
 // ---- other operators -------------------------------------------------------
@@ -293,11 +293,21 @@ bool pw_dw_deep(int hw, int frames, int stride, bool ups, int cin);   // the lau
 // activation (an Up block's upsampled half, see GemmEpilogue::ups_src)
 int launch_pw_dw(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,
                  int frames, int hw, int stride, int cin, int cexp, hipStream_t stream, const void* ups = nullptr, int ld_ups = 0);
+// rectangular frames (AudioConvWenet's 16x32 blocks, stride 1, no upsampled addend): one whole frame per tile
+bool pw_dw_rect_supported(int h, int w, int cin, int cexp, int stride);
+const char* pw_dw_rect_kernel_name(int h, int w);
+int launch_pw_dw_rect(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,
+                      int frames, int h, int w, int cin, int cexp, hipStream_t stream);
 // the bf16 engine's expand + depthwise kernel (pw_dw_bf16.hip): a, w1, d bf16; b1, wd, bd fp32; cin % 32 == 0, cexp % 64 == 0
 bool pw_dw_bf16_supported(int hw, int cin, int cexp, int stride);
 const char* pw_dw_bf16_kernel_name(int hw, int cexp, int frames, int stride = 1);
 // ups (optional, 20x20 / 40x40 stride 1): bf16 low-resolution addend [frames*(hw/2)^2, ld_ups], see launch_pw_dw
 bool pw_dw_bf16_takes_ups(int hw, int stride);
+// ... and its rectangular-frame counterpart (16x32, stride 1, no upsampled addend)
+bool pw_dw_bf16_rect_supported(int h, int w, int cin, int cexp, int stride);
+const char* pw_dw_bf16_rect_kernel_name(int h, int w);
+int launch_pw_dw_bf16_rect(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,
+                           int frames, int h, int w, int cin, int cexp, hipStream_t stream);
 int launch_pw_dw_bf16(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,
                       int frames, int hw, int stride, int cin, int cexp, hipStream_t stream, const void* ups = nullptr, int ld_ups = 0);
 int launch_upsample2x(const void* in, void* out, int ldc, int batch, int h, int wdt, int c,

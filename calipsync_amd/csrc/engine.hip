@@ -33,8 +33,12 @@ namespace {
 struct IR {  // inverted residual: PW expand -> DW3x3 -> PW project (module/unet.py:8-40)
   const char* prefix;
   int cin, cout, stride, res, hw_in;
+  int w_in = 0;   // frame width when it differs from the height (AudioConvWenet's 16x32 blocks, stride 1 only); 0 = square
   int cexp() const { return cin * 2; }
+  int wd() const { return w_in ? w_in : hw_in; }
+  bool square() const { return wd() == hw_in; }
   int hw_out() const { return stride == 1 ? hw_in : (hw_in + 2 - 3) / 2 + 1; }
+  int wd_out() const { return stride == 1 ? wd() : (wd() + 2 - 3) / 2 + 1; }
 };
 
 const IR kInc = {"inc.inconv.0", 6, 32, 1, 0, 160};
@@ -48,6 +52,12 @@ const IR kAudio[5] = {{"audio_model.conv1", 32, 64, 1, 0, 32},
                       {"audio_model.conv4", 256, 256, 1, 1, 16},
                       {"audio_model.conv6", 512, 512, 1, 1, 10},
                       {"audio_model.conv7", 512, 512, 1, 1, 10}};
+// AudioConvWenet (module/unet.py:109-144): conv1 / conv2 are 256 -> 512 -> 256 residual blocks on 16x32 frames; conv4, conv6
+// and conv7 are the HuBERT encoder's blocks of the same names (kAudio[2..4])
+const IR kAudioW[2] = {{"audio_model.conv1", 256, 256, 1, 1, 16, 32}, {"audio_model.conv2", 256, 256, 1, 1, 16, 32}};
+// per-frame floats of the NCHW audio window at the boundary
+inline int64_t audio_frame_floats(int mode) { return mode == CASYNC_AUDIO_WENET ? 256ll * 16 * 32 : 32ll * 32 * 32; }
+inline bool audio_mode_ok(int mode) { return mode == CASYNC_AUDIO_HUBERT || mode == CASYNC_AUDIO_WENET; }
 const IR kFuse[4] = {{"fuse_conv.0.double_conv.0", 1024, 512, 1, 0, 10},
                      {"fuse_conv.0.double_conv.1", 512, 512, 1, 1, 10},
                      {"fuse_conv.1.double_conv.0", 512, 256, 1, 0, 10},
@@ -89,23 +99,25 @@ struct Layout {
   }
 };
 
-const Layout& layout() {
-  static const Layout L = [] {
+Layout make_layout(int mode) {
+    const bool wenet = mode == CASYNC_AUDIO_WENET;
     Layout l;
     l.add("inc.inconv.0.fused", 620);  // [w1T 6x12][b1 12][wd 9x12][bd 12][w2T 12x32][b2 32]
     for (auto& st : kDown)
       for (auto& b : st) l.add_ir(b);
-    l.add_ir(kAudio[0]);
-    l.add_ir(kAudio[1]);
-    l.add("audio_model.conv3.w", 256ll * 9 * 128);  // [N][(ky,kx,cin)]
+    l.add_ir(wenet ? kAudioW[0] : kAudio[0]);
+    l.add_ir(wenet ? kAudioW[1] : kAudio[1]);
+    l.add("audio_model.conv3.w", 256ll * 9 * (wenet ? 256 : 128));  // [N][(ky,kx,cin)]
     l.add("audio_model.conv3.b", 256);
     l.add_ir(kAudio[2]);
     l.add("audio_model.conv5.w", 512ll * 9 * 256);
     l.add("audio_model.conv5.b", 512);
     l.add_ir(kAudio[3]);
     l.add_ir(kAudio[4]);
-    l.add("audio_model.bn7.s", 512);
-    l.add("audio_model.bn7.t", 512);
+    if (!wenet) {   // AudioConvWenet ends at conv7: no bn7 / relu7 (module/unet.py:135-144)
+      l.add("audio_model.bn7.s", 512);
+      l.add("audio_model.bn7.t", 512);
+    }
     l.add("mlp_fusion.fc1.w", 1024ll * 1024);
     l.add("mlp_fusion.fc1.b", 1024);
     l.add("mlp_fusion.fc2.w", 1024ll * 1024);  // bn2 and bn_tx folded in
@@ -142,8 +154,12 @@ const Layout& layout() {
     l.add("outc.w", 96);  // [3][32], outc_bn folded in
     l.add("outc.b", 3);
     return l;
-  }();
-  return L;
+}
+
+// the packed layout of an audio mode (anything but CASYNC_AUDIO_WENET: the HuBERT one)
+const Layout& layout(int mode = CASYNC_AUDIO_HUBERT) {
+  static const Layout L[2] = {make_layout(CASYNC_AUDIO_HUBERT), make_layout(CASYNC_AUDIO_WENET)};
+  return L[mode == CASYNC_AUDIO_WENET ? 1 : 0];
 }
 
 // ------------------------------------------------------------------ workspace arena
@@ -161,7 +177,7 @@ struct Ptr {
 // slots are sized for it.  With the fused kernels on (default) that is up2.0's 40x40x512, not the
 // 160x160x128 of up4.0 the fused kernel keeps in LDS (19.6 MB per frame less workspace).
 bool ir_is_fused(const CasyncOptions& o, const IR& b) {
-  return o.fuse_ir && b.hw_in >= o.fuse_min_hw && ir_fused_supported(b.cin, b.cout, b.stride);
+  return o.fuse_ir && b.square() && b.hw_in >= o.fuse_min_hw && ir_fused_supported(b.cin, b.cout, b.stride);
 }
 bool up_is_fused(const CasyncOptions& o, const IR& b0) {
   return o.fuse_ir && o.fuse_up && b0.hw_in >= o.fuse_min_hw && ir_fused_up_supported(b0.cin, b0.cout);
@@ -237,12 +253,17 @@ struct Arena {
       // skip_early: W1b . skip + b of up1.0 (20x20 x 1024) and up2.0 (40x40 x 512), small batches only
       {"EP1", 400 * 1024, 0},       {"EP2", 1600 * 512, 0}};
   // (the two skip_early buffers exist only for the batches that use them: 4.9 MB per frame)
-  Arena(const CasyncOptions& o, int batch) {
+  // wenet: the audio window is 256 x 16 x 32, conv1 / conv2 write 16x32 x 256 and expand to 16x32 x 512
+  Arena(const CasyncOptions& o, int batch, int mode = CASYNC_AUDIO_HUBERT) {
     b[E1].per_frame = b[E2].per_frame = max_unfused_expand(o);
     if (!skip_early_batch(o, batch)) b[EP1].per_frame = b[EP2].per_frame = 0;
+    if (mode == CASYNC_AUDIO_WENET) {
+      b[A0].per_frame = b[AC1].per_frame = 512 * 256;
+      b[AE1].per_frame = b[AE2].per_frame = 512 * 512;
+    }
   }
-  static int64_t bytes(const CasyncOptions& o, int batch, int esz = 4) {
-    Arena a(o, batch);
+  static int64_t bytes(const CasyncOptions& o, int batch, int esz = 4, int mode = CASYNC_AUDIO_HUBERT) {
+    Arena a(o, batch, mode);
     int64_t tot = 0;
     for (auto& x : a.b) tot += (x.per_frame * batch + 63) / 64 * 64;
     return tot * (int64_t)esz;
@@ -287,6 +308,7 @@ struct DeviceGuard {
 struct casync_engine {
   int device = 0;
   int dtype = DT_F32;        // activation storage type (DT_BF16: bf16 activations + bf16 GEMM weights)
+  int mode = CASYNC_AUDIO_HUBERT;   // audio encoder (fixed at creation): selects the packed layout, the arena and encode()'s branch
   const float* w = nullptr;  // packed weights on the device (fp32: biases, scales, DW / fused-IR weights)
   float* owned = nullptr;
   bf16_t* w16 = nullptr;     // bf16 image of the whole packed buffer (same element offsets), DT_BF16 only
@@ -309,10 +331,10 @@ struct casync_engine {
   bool streams_ready = false;
   CasyncOptions opt;         // this handle's switches: process defaults at create, casync_set_option afterwards
   CasyncOptions eff;         // what the forward in progress runs under (run_forward: `opt` + the bf16 large-batch plan)
-  const float* W(const std::string& name) const { return w + layout().off(name); }
+  const float* W(const std::string& name) const { return w + layout(mode).off(name); }
   // GEMM weight matrix in the engine's storage type
   const void* WG(const std::string& name) const {
-    return dtype == DT_BF16 ? (const void*)(w16 + layout().off(name)) : (const void*)(w + layout().off(name));
+    return dtype == DT_BF16 ? (const void*)(w16 + layout(mode).off(name)) : (const void*)(w + layout(mode).off(name));
   }
 };
 
@@ -437,14 +459,15 @@ struct Plan {
           [&] { return launch_pw_gemm(a, lda, w, c, ldc, (int)m, n, k, epi, r.s, dt()); });
   }
 
-  // Dense 3x3 conv + bias + LReLU (audio conv3 / conv5, module/unet.py:161-168) as an implicit GEMM:
-  // the ring kernel gathers the taps itself (no im2col buffer).
-  void conv3x3(const std::string& tag, Ptr in, const std::string& wname, Ptr out, int hw, int cin, int cout,
-               int stride, int pad) {
-    const int ho = (hw + 2 * pad - 3) / stride + 1;
-    const long long m = (long long)B * ho * ho;
+  // Dense 3x3 conv + bias + activation (audio conv3 / conv5: LReLU in AudioConvHubert, module/unet.py:161-168; ReLU and
+  // conv3's stride (1, 2) in AudioConvWenet, :119-133) as an implicit GEMM: the ring kernel gathers the taps itself (no
+  // im2col buffer).
+  void conv3x3(const std::string& tag, Ptr in, const std::string& wname, Ptr out, int h, int w, int cin, int cout,
+               int stride_h, int stride_w, int pad, int act) {
+    const int ho = (h + 2 * pad - 3) / stride_h + 1, wo = (w + 2 * pad - 3) / stride_w + 1;
+    const long long m = (long long)B * ho * wo;
     GemmEpilogue ep;
-    ep.act = 1;
+    ep.act = act;
     ep.bias = e.W(wname.substr(0, wname.size() - 1) + "b");
     ep.concurrent = concurrent ? 1 : 0;
     if (char* ctx = stream_k ? e.sk_ctx(lane, aux && r.s == aux ? 1 : 0) : nullptr) {
@@ -452,9 +475,9 @@ struct Plan {
       ep.sk_cnt = reinterpret_cast<unsigned*>(ctx + kStreamKFloats * 4);
     }
     const double es = dtype_size(dt());
-    r.run(tag.c_str(), conv3x3_gemm_kernel_name(B, hw, hw, cin, cout, stride, pad, dt(), concurrent, ep.sk_ws != nullptr),
-          2.0 * m * cout * 9 * cin, es * ((double)B * hw * hw * cin + (double)m * cout + 9.0 * cin * cout), [&] {
-      return launch_conv3x3_gemm(in, e.WG(wname), out, cout, B, hw, hw, cin, cout, stride, pad, ep, r.s, dt());
+    r.run(tag.c_str(), conv3x3_gemm_kernel_name(B, h, w, cin, cout, stride_h, stride_w, pad, dt(), concurrent, ep.sk_ws != nullptr),
+          2.0 * m * cout * 9 * cin, es * ((double)B * h * w * cin + (double)m * cout + 9.0 * cin * cout), [&] {
+      return launch_conv3x3_gemm(in, e.WG(wname), out, cout, B, h, w, cin, cout, stride_h, stride_w, pad, ep, r.s, dt());
     });
   }
 
@@ -465,7 +488,7 @@ struct Plan {
   void ir(const IR& b, Ptr in, int ld_in, Ptr out, int ld_out, Ptr e1, Ptr e2,
           const GemmEpilogue* extra = nullptr, Ptr ups = Ptr{}) {
     const std::string p = b.prefix;
-    const long long m_in = (long long)B * b.hw_in * b.hw_in, m_out = (long long)B * b.hw_out() * b.hw_out();
+    const long long m_in = (long long)B * b.hw_in * b.wd(), m_out = (long long)B * b.hw_out() * b.wd_out();
     const int k_in = ups.p ? b.cin / 2 : b.cin;
     const std::string w1name = p + (ups.p ? ".pw1b.w" : ".pw1.w");
     if (!extra && !ups.p && ir_is_fused(o, b)) {
@@ -481,16 +504,33 @@ struct Plan {
     }
     // the un-fused chain parks the expanded tensor in e1 / e2: they must have been sized for this block (the arena's
     // predicate and the plan's are the same functions; this catches the day they are not)
-    if (ar.per_frame_of(e2) < (int64_t)b.hw_in * b.hw_in * b.cexp()) {
+    if (ar.per_frame_of(e2) < (int64_t)b.hw_in * b.wd() * b.cexp()) {
       casync_set_error("plan: %s un-fused needs %lld expanded elements per frame, the workspace slot holds %lld", b.prefix,
-                       (long long)b.hw_in * b.hw_in * b.cexp(), (long long)ar.per_frame_of(e2));
+                       (long long)b.hw_in * b.wd() * b.cexp(), (long long)ar.per_frame_of(e2));
       r.status = CASYNC_ERR_STATE;
       return;
     }
     // (from fuse_dw_min = 12 frames per launch: below that its whole-frame tiles are too few to fill the chip -- B=1 0.92 vs 0.82 ms)
     // (below fuse_dw_deep frames per launch -- round 5 -- the stride-1 blocks take its one-frame tiles with a four-stage ring)
-    const bool deep = pw_dw_deep(b.hw_in, B, b.stride, ups.p != nullptr, k_in);
-    if (dt() == DT_F32 && o.fuse_dw && (b.hw_in < 40 || o.fuse_dw >= 2) && (deep || B >= (b.hw_in == 40 ? o.fuse_dw_min40 : o.fuse_dw_min)) &&
+    // (rectangular frames -- AudioConvWenet's 16x32 blocks -- have kernels of their own: whole-frame tiles from fuse_dw_min frames)
+    const bool sq = b.square();
+    const bool deep = sq && pw_dw_deep(b.hw_in, B, b.stride, ups.p != nullptr, k_in);
+    if (dt() == DT_F32 && o.fuse_dw && !sq && !ups.p && B >= o.fuse_dw_min && pw_dw_rect_supported(b.hw_in, b.wd(), k_in, b.cexp(), b.stride)) {
+      r.run((p + ".pw1dw").c_str(), pw_dw_rect_kernel_name(b.hw_in, b.wd()),
+            2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
+            4.0 * (m_in * (double)k_in + (double)b.cexp() * k_in + (double)m_out * b.cexp()), [&] {
+        return launch_pw_dw_rect(in, ld_in, e.W(w1name), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, b.cexp(), B,
+                                 b.hw_in, b.wd(), k_in, b.cexp(), r.s);
+      });
+    } else if (dt() == DT_BF16 && o.fuse_dw_bf16 && !sq && !ups.p && B >= o.fuse_dw_bf16_min &&
+               pw_dw_bf16_rect_supported(b.hw_in, b.wd(), k_in, b.cexp(), b.stride)) {
+      r.run((p + ".pw1dw").c_str(), pw_dw_bf16_rect_kernel_name(b.hw_in, b.wd()),
+            2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
+            2.0 * (m_in * (double)k_in + (double)b.cexp() * k_in + (double)m_out * b.cexp()), [&] {
+        return launch_pw_dw_bf16_rect(in, ld_in, e.WG(w1name), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, b.cexp(), B,
+                                      b.hw_in, b.wd(), k_in, b.cexp(), r.s);
+      });
+    } else if (dt() == DT_F32 && o.fuse_dw && sq && (b.hw_in < 40 || o.fuse_dw >= 2) && (deep || B >= (b.hw_in == 40 ? o.fuse_dw_min40 : o.fuse_dw_min)) &&
         pw_dw_supported(b.hw_in, k_in, b.cexp(), b.stride)) {
       // expand GEMM whose output tile is whole frames: the depthwise conv runs on the tile in LDS, E never exists
       // (flops: what this launch executes -- with `ups` the upsampled half was a GEMM at the low resolution)
@@ -500,7 +540,7 @@ struct Plan {
         return launch_pw_dw(in, ld_in, e.W(w1name), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2,
                             b.cexp(), B, b.hw_in, b.stride, k_in, b.cexp(), r.s, ups.p, b.cexp());
       });
-    } else if (dt() == DT_BF16 && o.fuse_dw_bf16 && (b.hw_in < 40 || o.fuse_dw_bf16 >= 2) && B >= o.fuse_dw_bf16_min &&
+    } else if (dt() == DT_BF16 && o.fuse_dw_bf16 && sq && (b.hw_in < 40 || o.fuse_dw_bf16 >= 2) && B >= o.fuse_dw_bf16_min &&
                pw_dw_bf16_supported(b.hw_in, k_in, b.cexp(), b.stride) && (!ups.p || pw_dw_bf16_takes_ups(b.hw_in, b.stride))) {
       // the bf16 engine's counterpart (round 5): 64-channel tiles, bf16 E image in LDS; E never reaches HBM
       r.run((p + ".pw1dw").c_str(), pw_dw_bf16_kernel_name(b.hw_in, b.cexp(), B, b.stride),
@@ -522,9 +562,9 @@ struct Plan {
         ep1.ups_h = ep1.ups_w = b.hw_in;
       }
       gemm(p + ".pw1", in, ld_in, w1name, e1, b.cexp(), m_in, b.cexp(), k_in, ep1, p + ".pw1.b");
-      r.run((p + ".dw").c_str(), dw3x3_kernel_name(b.hw_in, b.hw_in, b.cexp(), b.stride, dt()),
+      r.run((p + ".dw").c_str(), dw3x3_kernel_name(b.hw_in, b.wd(), b.cexp(), b.stride, dt()),
             2.0 * 9 * m_out * b.cexp(), dtype_size(dt()) * (double)(m_in + m_out) * b.cexp(), [&] {
-        return launch_dw3x3(e1, e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, B, b.hw_in, b.hw_in, b.cexp(),
+        return launch_dw3x3(e1, e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, B, b.hw_in, b.wd(), b.cexp(),
                             b.stride, r.s, dt());
       });
     }
@@ -564,8 +604,21 @@ struct Plan {
       }
       r.s = aux;
     }
-    // ---------------- audio encoder (module/unet.py:177-194)
+    // ---------------- audio encoder (module/unet.py:177-194; AudioConvWenet :135-144)
     Ptr AE1 = ar[A::AE1], AE2 = ar[A::AE2];
+    if (e.mode == CASYNC_AUDIO_WENET) {
+      // [B,256,16,32] -> NHWC 16x32 x 256; two residual blocks at 16x32; conv3 (1,2)-strided to 16x16 + ReLU; conv4; conv5
+      // + ReLU to 10x10; conv6; conv7 straight into the audio half of cat([x5, a]) (no bn7 / relu7)
+      r.run("audio.nchw_to_nhwc", kname("nchw_to_nhwc_kernel").c_str(), 0, (4.0 + dtype_size(dt())) * B * 131072,
+            [&] { return launch_nchw_to_nhwc(audio, ar[A::A0], B, 256, 512, r.s, dt()); });
+      ir(kAudioW[0], ar[A::A0], 256, ar[A::AC1], 256, AE1, AE2);
+      ir(kAudioW[1], ar[A::AC1], 256, ar[A::AC2], 256, AE1, AE2);
+      conv3x3("audio.conv3", ar[A::AC2], "audio_model.conv3.w", ar[A::AC3], 16, 32, 256, 256, 1, 2, 1, 2);
+      ir(kAudio[2], ar[A::AC3], 256, ar[A::AC4], 256, AE1, AE2);
+      conv3x3("audio.conv5", ar[A::AC4], "audio_model.conv5.w", ar[A::AC5], 16, 16, 256, 512, 2, 2, 3, 2);
+      ir(kAudio[3], ar[A::AC5], 512, ar[A::AC6], 512, AE1, AE2);
+      ir(kAudio[4], ar[A::AC6], 512, ar[A::CATA] + 512, 1024, AE1, AE2);
+    } else {
     if (win_feat)
       r.run("audio.window_gather", kname("audio_window_gather_kernel").c_str(), 0, (4.0 + dtype_size(dt())) * B * 32768,
             [&] { return launch_audio_window_gather(win_feat, win_steps, win_idx, ar[A::A0], B, r.s, dt()); });
@@ -574,15 +627,16 @@ struct Plan {
             [&] { return launch_nchw_to_nhwc(audio, ar[A::A0], B, 32, 1024, r.s, dt()); });
     ir(kAudio[0], ar[A::A0], 32, ar[A::AC1], 64, AE1, AE2);
     ir(kAudio[1], ar[A::AC1], 64, ar[A::AC2], 128, AE1, AE2);
-    conv3x3("audio.conv3", ar[A::AC2], "audio_model.conv3.w", ar[A::AC3], 32, 128, 256, 2, 1);
+    conv3x3("audio.conv3", ar[A::AC2], "audio_model.conv3.w", ar[A::AC3], 32, 32, 128, 256, 2, 2, 1, 1);
     ir(kAudio[2], ar[A::AC3], 256, ar[A::AC4], 256, AE1, AE2);
-    conv3x3("audio.conv5", ar[A::AC4], "audio_model.conv5.w", ar[A::AC5], 16, 256, 512, 2, 3);
+    conv3x3("audio.conv5", ar[A::AC4], "audio_model.conv5.w", ar[A::AC5], 16, 16, 256, 512, 2, 2, 3, 1);
     ir(kAudio[3], ar[A::AC5], 512, ar[A::AC6], 512, AE1, AE2);
     {
       GemmEpilogue bn7;  // relu7(bn7(x + conv(x))) fused behind conv7's residual add
       bn7.aff_s = e.W("audio_model.bn7.s");
       bn7.aff_t = e.W("audio_model.bn7.t");
       ir(kAudio[4], ar[A::AC6], 512, ar[A::CATA] + 512, 1024, AE1, AE2, &bn7);
+    }
     }
     // K and V projections of the audio features for all four attention blocks in one GEMM (module/unet.py:202-203,
     // 210, 214).  They depend on the audio branch alone, so they run HERE, on the audio stream beside the face encoder,
@@ -805,9 +859,9 @@ int check_forward_args(casync_handle h, const float* x, const float* a, float* o
     casync_set_error("forward: weights not loaded");
     return CASYNC_ERR_STATE;
   }
-  if (ws_bytes < Arena::bytes(h->opt, batch, dtype_size(h->dtype))) {
+  if (ws_bytes < Arena::bytes(h->opt, batch, dtype_size(h->dtype), h->mode)) {
     casync_set_error("forward: workspace %lld B < required %lld B", (long long)ws_bytes,
-                     (long long)Arena::bytes(h->opt, batch, dtype_size(h->dtype)));
+                     (long long)Arena::bytes(h->opt, batch, dtype_size(h->dtype), h->mode));
     return CASYNC_ERR_STATE;
   }
   CASYNC_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
@@ -860,6 +914,13 @@ const char* casync_packed_name(int i) {
 int64_t casync_packed_offset(int i) { return (i >= 0 && i < casync_packed_count()) ? layout().items[i].offset : -1; }
 int64_t casync_packed_size(int i) { return (i >= 0 && i < casync_packed_count()) ? layout().items[i].size : -1; }
 int64_t casync_packed_total(void) { return layout().total; }
+int casync_packed_count_m(int mode) { return audio_mode_ok(mode) ? (int)layout(mode).items.size() : 0; }
+const char* casync_packed_name_m(int mode, int i) {
+  return (i >= 0 && i < casync_packed_count_m(mode)) ? layout(mode).items[i].name.c_str() : nullptr;
+}
+int64_t casync_packed_offset_m(int mode, int i) { return (i >= 0 && i < casync_packed_count_m(mode)) ? layout(mode).items[i].offset : -1; }
+int64_t casync_packed_size_m(int mode, int i) { return (i >= 0 && i < casync_packed_count_m(mode)) ? layout(mode).items[i].size : -1; }
+int64_t casync_packed_total_m(int mode) { return audio_mode_ok(mode) ? layout(mode).total : -1; }
 int64_t casync_workspace_bytes(int batch) {
   return batch > 0 ? Arena::bytes(casync_default_options(), batch, 4) : -1;
 }
@@ -868,7 +929,7 @@ int64_t casync_workspace_bytes_dt(int batch, int dtype) {
              ? Arena::bytes(casync_default_options(), batch, dtype_size(dtype)) : -1;
 }
 int64_t casync_workspace_bytes_h(casync_handle h, int batch) {
-  return h && batch > 0 ? Arena::bytes(h->opt, batch, dtype_size(h->dtype)) : -1;
+  return h && batch > 0 ? Arena::bytes(h->opt, batch, dtype_size(h->dtype), h->mode) : -1;
 }
 
 int casync_set_option(casync_handle h, const char* name, int value) {
@@ -893,8 +954,13 @@ int casync_get_option(casync_handle h, const char* name, int* value) {
 int casync_create(int device_id, casync_handle* out) { return casync_create_ex(device_id, DT_F32, out); }
 
 int casync_create_ex(int device_id, int dtype, casync_handle* out) {
+  return casync_create_mode(device_id, dtype, CASYNC_AUDIO_HUBERT, out);
+}
+
+int casync_create_mode(int device_id, int dtype, int audio_mode, casync_handle* out) {
   CASYNC_REQUIRE(out, "create: null out");
   CASYNC_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "create: dtype %d (0 = fp32, 1 = bf16)", dtype);
+  CASYNC_REQUIRE(audio_mode_ok(audio_mode), "create: audio mode %d (0 = hubert, 1 = wenet)", audio_mode);
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
     casync_set_error("create: no HIP device visible");
@@ -910,6 +976,7 @@ int casync_create_ex(int device_id, int dtype, casync_handle* out) {
   casync_engine* e = new casync_engine();
   e->device = device_id;
   e->dtype = dtype;
+  e->mode = audio_mode;
   e->opt = casync_default_options();   // the environment was read once; this handle keeps its own copy
   {
     DeviceGuard guard(device_id);
@@ -971,8 +1038,8 @@ static int refresh_bf16_weights(casync_handle h, int64_t n) {
 
 int casync_load_weights_host(casync_handle h, const float* packed, int64_t n_floats) {
   CASYNC_REQUIRE(h && packed, "load_weights: null");
-  CASYNC_REQUIRE(n_floats == layout().total, "load_weights: %lld floats, layout needs %lld",
-                 (long long)n_floats, (long long)layout().total);
+  CASYNC_REQUIRE(n_floats == layout(h->mode).total, "load_weights: %lld floats, layout needs %lld",
+                 (long long)n_floats, (long long)layout(h->mode).total);
   {
     DeviceGuard guard(h->device);
     CASYNC_CHECK_HIP(guard.err);
@@ -985,8 +1052,8 @@ int casync_load_weights_host(casync_handle h, const float* packed, int64_t n_flo
 
 int casync_load_weights_device(casync_handle h, const float* packed_dev, int64_t n_floats) {
   CASYNC_REQUIRE(h && packed_dev, "load_weights_device: null");
-  CASYNC_REQUIRE(n_floats == layout().total, "load_weights_device: %lld floats, layout needs %lld",
-                 (long long)n_floats, (long long)layout().total);
+  CASYNC_REQUIRE(n_floats == layout(h->mode).total, "load_weights_device: %lld floats, layout needs %lld",
+                 (long long)n_floats, (long long)layout(h->mode).total);
   CASYNC_REQUIRE(((uintptr_t)packed_dev % 256) == 0, "load_weights_device: buffer must be 256-B aligned");
   hipPointerAttribute_t attr;
   if (hipPointerGetAttributes(&attr, packed_dev) == hipSuccess && attr.type == hipMemoryTypeDevice)
@@ -1128,7 +1195,7 @@ static int run_forward(casync_handle h, const FwdArgs& A, hipStream_t caller, st
     Runner r;
     r.s = lane_stream(l);
     r.profile = serial;
-    Plan p{*h, Arena(o, A.batch), r, bl};
+    Plan p{*h, Arena(o, A.batch, h->mode), r, bl};
     p.lane = l;
     p.kv_in_encode = o.kv_early >= 2 || (o.kv_early == 1 && lanes == 1);
     p.skip_early = lanes == 1 && h->dtype == DT_F32 && skip_early_batch(o, A.batch) &&
@@ -1150,7 +1217,7 @@ static int run_forward(casync_handle h, const FwdArgs& A, hipStream_t caller, st
       p.win_steps = A.n_steps;
       p.win_idx = A.idx + b0;
     }
-    if (phase == 0) p.encode(A.x + (size_t)b0 * 6 * 160 * 160, A.feat ? nullptr : A.a + (size_t)b0 * 32 * 32 * 32);
+    if (phase == 0) p.encode(A.x + (size_t)b0 * 6 * 160 * 160, A.feat ? nullptr : A.a + (size_t)b0 * audio_frame_floats(h->mode));
     else if (phase == 1) p.trunk();
     else p.decode(A.out + (size_t)b0 * 3 * 160 * 160);
     r.finish();
@@ -1203,6 +1270,9 @@ int casync_forward(casync_handle h, const float* x, const float* a, float* out, 
 int casync_forward_windows(casync_handle h, const float* x, const float* features, int n_steps,
                            const int32_t* frame_idx, float* out, int batch, void* ws, int64_t ws_bytes,
                            casync_stream stream) {
+  CASYNC_REQUIRE(!h || h->mode == CASYNC_AUDIO_HUBERT,
+                 "forward_windows: the device window gather builds HuBERT windows; a wenet handle takes its [B,256,16,32] audio "
+                 "through casync_forward");
   CASYNC_REQUIRE(features && frame_idx && n_steps > 0, "forward_windows: null features / indices");
   CASYNC_REQUIRE(((uintptr_t)features % 16) == 0, "forward_windows: features must be 16-B aligned");
   int st = check_forward_args(h, x, features, out, batch, ws, ws_bytes);
@@ -1227,10 +1297,11 @@ int casync_profile_forward(casync_handle h, const float* x, const float* a, floa
 int64_t casync_tap(casync_handle h, const char* name, int batch, void* ws, void* dst, int64_t dst_floats,
                    casync_stream stream) {
   CASYNC_REQUIRE(h && name && ws && dst && batch > 0, "tap: bad args");
-  Arena ar(h->opt, batch);
+  Arena ar(h->opt, batch, h->mode);
   ar.bind(ws, batch, dtype_size(h->dtype));
   using A = Arena;
   struct T { const char* n; Ptr p; int ld, c, rows; };
+  const bool wenet = h->mode == CASYNC_AUDIO_WENET;
   const T taps[] = {
       {"x1", ar[A::CAT4] + 32, 64, 32, 25600},  {"x2", ar[A::CAT3] + 64, 128, 64, 6400},
       {"x3", ar[A::CAT2] + 128, 256, 128, 1600}, {"x4", ar[A::CAT1] + 256, 512, 256, 400},
@@ -1240,7 +1311,9 @@ int64_t casync_tap(casync_handle h, const char* name, int batch, void* ws, void*
       {"att2", ar[A::OX2], 1024, 1024, 100},    {"att3", ar[A::OX3], 1024, 1024, 100},
       {"fuse", ar[A::F], 256, 256, 100},        {"u1", ar[A::U1], 128, 128, 400},
       {"u2", ar[A::U2], 64, 64, 1600},          {"u3", ar[A::U3], 32, 32, 6400},
-      {"u4", ar[A::U4], 32, 32, 25600},         {"audio_conv2", ar[A::AC2], 128, 128, 1024},
+      {"u4", ar[A::U4], 32, 32, 25600},
+      {"audio_conv1", ar[A::AC1], wenet ? 256 : 64, wenet ? 256 : 64, wenet ? 512 : 1024},
+      {"audio_conv2", ar[A::AC2], wenet ? 256 : 128, wenet ? 256 : 128, wenet ? 512 : 1024},
       {"audio_conv3", ar[A::AC3], 256, 256, 256}, {"audio_conv4", ar[A::AC4], 256, 256, 256},
       {"audio_conv5", ar[A::AC5], 512, 512, 100}};
   for (const T& t : taps) {
@@ -1305,10 +1378,15 @@ int casync_op_pw_gemm(const void* a, int lda, const void* w, const float* bias, 
 }
 int casync_op_conv3x3(const void* in, const void* w, const float* bias, void* out, int batch, int h, int wdt,
                       int cin, int cout, int stride, int pad, int act, casync_stream stream) {
+  return casync_op_conv3x3_ex(in, w, bias, out, batch, h, wdt, cin, cout, stride, stride, pad, act, stream);
+}
+int casync_op_conv3x3_ex(const void* in, const void* w, const float* bias, void* out, int batch, int h, int wdt,
+                         int cin, int cout, int stride_h, int stride_w, int pad, int act, casync_stream stream) {
   GemmEpilogue e;
   e.bias = bias;
   e.act = act;
-  return launch_conv3x3_gemm(in, w, out, cout, batch, h, wdt, cin, cout, stride, pad, e, (hipStream_t)stream, g_op_dtype);
+  return launch_conv3x3_gemm(in, w, out, cout, batch, h, wdt, cin, cout, stride_h, stride_w, pad, e, (hipStream_t)stream,
+                             g_op_dtype);
 }
 int casync_op_dw3x3(const void* in, const float* w, const float* bias, void* out, int batch, int h,
                     int wdt, int c, int stride, casync_stream stream) {

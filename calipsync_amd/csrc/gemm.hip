@@ -94,7 +94,9 @@ __device__ __forceinline__ float col_const(const float* regs, const float* mem, 
 // EUPS: the epilogue can add a bilinearly upsampled low-resolution tensor (GemmEpilogue::ups_src).  Compiled only into
 // pw_gemm_ups_kernel: its four extra row gathers per output row would set the register count -- and with it the
 // occupancy -- of every other GEMM instance (measured: bf16 128x128 2 -> 1 waves/SIMD, -13 % at B=512).
-template <typename T, int NT, int BM, int BN, int PAD = 4, bool SWZ = false, bool LITE = false, bool EUPS = false>
+// RELU: epi.act = 2 (ReLU) is honoured -- compiled into the implicit-GEMM conv instances only (AudioConvWenet's conv3 / conv5):
+// a runtime slope in the shared activation cost every GEMM instance 2-4 registers, the bf16 64x64 / upsampling ones a wave per SIMD.
+template <typename T, int NT, int BM, int BN, int PAD = 4, bool SWZ = false, bool LITE = false, bool EUPS = false, bool RELU = false>
 __device__ __forceinline__ void epilogue_rows_cols(const float* Cs, int m0, int n0, int M, T* __restrict__ C, int ldc,
                                                    const GemmEpilogue& epi, int tid, const EpiCols<T>& k) {
   constexpr int CPT = V16<T>::N, TPR = BN / CPT, RPP = NT / TPR, LDC_S = BN + PAD;
@@ -136,6 +138,12 @@ __device__ __forceinline__ void epilogue_rows_cols(const float* Cs, int m0, int 
     if (epi.act) {
 #pragma unroll
       for (int e = 0; e < CPT; ++e) v.v[e] = lrelu(v.v[e]);
+      if constexpr (RELU) {   // act 2: ReLU = max(LeakyReLU(v), 0), exactly (a negative v maps to +0)
+        if (epi.act == 2) {
+#pragma unroll
+          for (int e = 0; e < CPT; ++e) v.v[e] = fmaxf(v.v[e], 0.f);
+        }
+      }
     }
     if (epi.post_res) {
       const V16<T> r = ld16(static_cast<const T*>(epi.post_res) + (size_t)m * epi.ld_post + n);
@@ -162,12 +170,12 @@ __device__ __forceinline__ void epilogue_rows_cols(const float* Cs, int m0, int 
   }
 }
 
-template <typename T, int NT, int BM, int BN, int PAD = 4, bool SWZ = false, bool EUPS = false>
+template <typename T, int NT, int BM, int BN, int PAD = 4, bool SWZ = false, bool EUPS = false, bool RELU = false>
 __device__ __forceinline__ void epilogue_rows(const float* Cs, int m0, int n0, int M, T* __restrict__ C,
                                               int ldc, const GemmEpilogue& epi, int tid) {
   EpiCols<T> k;
   k.load(epi, n0 + (tid % (BN / V16<T>::N)) * V16<T>::N);
-  epilogue_rows_cols<T, NT, BM, BN, PAD, SWZ, false, EUPS>(Cs, m0, n0, M, C, ldc, epi, tid, k);
+  epilogue_rows_cols<T, NT, BM, BN, PAD, SWZ, false, EUPS, RELU>(Cs, m0, n0, M, C, ldc, epi, tid, k);
 }
 
 template <typename T, int BM, int BN, int WM, int WN>
@@ -439,7 +447,7 @@ __device__ __forceinline__ void glds_body(const T* __restrict__ A, int lda, cons
           const int hw = epi.conv_ho * epi.conv_wo;
           const int b = row / hw, rem = row - b * hw;
           const int oy = rem / epi.conv_wo, ox = rem - oy * epi.conv_wo;
-          const int iy0 = oy * epi.conv_stride - epi.conv_pad, ix0 = ox * epi.conv_stride - epi.conv_pad;
+          const int iy0 = oy * epi.conv_sh - epi.conv_pad, ix0 = ox * epi.conv_sw - epi.conv_pad;
           src[j] = A + (((long long)b * epi.conv_h + iy0) * epi.conv_w + ix0) * (long long)epi.conv_c + cs * E16;
           int mk = 0;
 #pragma unroll
@@ -735,9 +743,9 @@ __device__ __forceinline__ void glds_body(const T* __restrict__ A, int lda, cons
         }
         __syncthreads();
       }
-      if constexpr (WK == 2) epilogue_rows_cols<T, 256, BM / WM, BN, 4, false, false, EUPS>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid, kcols);
-      else if (PREF64) epilogue_rows_cols<T, 256, BM / WM, BN, 4, false, false, EUPS>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid, kcols);
-      else epilogue_rows<T, 256, BM / WM, BN, 4, false, EUPS>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid);
+      if constexpr (WK == 2) epilogue_rows_cols<T, 256, BM / WM, BN, 4, false, false, EUPS, CONV>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid, kcols);
+      else if (PREF64) epilogue_rows_cols<T, 256, BM / WM, BN, 4, false, false, EUPS, CONV>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid, kcols);
+      else epilogue_rows<T, 256, BM / WM, BN, 4, false, EUPS, CONV>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid);
       __syncthreads();   // staging consumed before the next block / the next loads overwrite the ring
     }
   };
@@ -1119,10 +1127,10 @@ int launch_conv_t(const T* in, const T* w, T* out, int ldc, int m, int n, int k,
 }
 }  // namespace
 
-const char* conv3x3_gemm_kernel_name(int batch, int h, int wdt, int cin, int cout, int stride, int pad, int dtype,
+const char* conv3x3_gemm_kernel_name(int batch, int h, int wdt, int cin, int cout, int stride_h, int stride_w, int pad, int dtype,
                                      bool concurrent, bool stream_k) {
   static thread_local char buf[64];
-  const int ho = (h + 2 * pad - 3) / stride + 1, wo = (wdt + 2 * pad - 3) / stride + 1;
+  const int ho = (h + 2 * pad - 3) / stride_h + 1, wo = (wdt + 2 * pad - 3) / stride_w + 1;
   const int m = batch * ho * wo;
   const int cfg = pick_cfg(m, cout, 9 * cin, stream_k, dtype, nullptr, concurrent, false);   // the launch's own choice
   const bool small = cfg == C64x64 || cfg == C64x32 || cout % 64 || m <= 4096;
@@ -1132,21 +1140,22 @@ const char* conv3x3_gemm_kernel_name(int batch, int h, int wdt, int cin, int cou
 }
 
 int launch_conv3x3_gemm(const void* in, const void* w, void* out, int ldc, int batch, int h, int wdt, int cin,
-                        int cout, int stride, int pad, const GemmEpilogue& epi_in, hipStream_t stream, int dtype) {
+                        int cout, int stride_h, int stride_w, int pad, const GemmEpilogue& epi_in, hipStream_t stream, int dtype) {
   const int bk = ROWB / dtype_size(dtype), e16 = 16 / dtype_size(dtype);
   CASYNC_REQUIRE(in && w && out && batch > 0, "conv3x3: bad args");
   CASYNC_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "conv3x3: dtype %d", dtype);
   CASYNC_REQUIRE(cin % bk == 0, "conv3x3: cin=%d must be a multiple of %d", cin, bk);
   CASYNC_REQUIRE(cout % 64 == 0, "conv3x3: cout=%d must be a multiple of 64", cout);
-  CASYNC_REQUIRE(stride >= 1 && pad >= 0 && h + 2 * pad >= 3 && wdt + 2 * pad >= 3, "conv3x3: geometry");
+  CASYNC_REQUIRE(stride_h >= 1 && stride_w >= 1 && pad >= 0 && h + 2 * pad >= 3 && wdt + 2 * pad >= 3, "conv3x3: geometry");
+  CASYNC_REQUIRE(epi_in.act >= 0 && epi_in.act <= 2, "conv3x3: act %d (0 none, 1 LeakyReLU, 2 ReLU)", epi_in.act);
   CASYNC_REQUIRE(ldc >= cout && ldc % e16 == 0, "conv3x3: ldc=%d", ldc);
   CASYNC_REQUIRE(((uintptr_t)in % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)out % 16) == 0,
                  "conv3x3: in/w/out must be 16-B aligned");
   GemmEpilogue epi = epi_in;
   epi.conv_on = 1;
-  epi.conv_h = h; epi.conv_w = wdt; epi.conv_c = cin; epi.conv_stride = stride; epi.conv_pad = pad;
-  epi.conv_ho = (h + 2 * pad - 3) / stride + 1;
-  epi.conv_wo = (wdt + 2 * pad - 3) / stride + 1;
+  epi.conv_h = h; epi.conv_w = wdt; epi.conv_c = cin; epi.conv_sh = stride_h; epi.conv_sw = stride_w; epi.conv_pad = pad;
+  epi.conv_ho = (h + 2 * pad - 3) / stride_h + 1;
+  epi.conv_wo = (wdt + 2 * pad - 3) / stride_w + 1;
   const long long m = (long long)batch * epi.conv_ho * epi.conv_wo;
   CASYNC_REQUIRE(m < (1ll << 31), "conv3x3: too many output pixels");
   if (dtype == DT_BF16)

@@ -50,18 +50,19 @@ struct ETile {
 // KF = floats per k-tile row: 32 (128-B rows, gemm.hip's ring) or 16 (64-B rows: half the ring, so that the whole
 // working set of a workgroup stays near the 32 KB of the 64x64 GEMM tiles it shares the CUs with -- a workgroup that
 // fills a CU's LDS shuts the other lane's kernels out, measured -2 % end to end with 74 KB rings)
-template <int HW, int F, int BN, int KF, int S = 1, int NST_ = 2>
+// WD: frame width when it differs from the height HW (AudioConvWenet's 16x32 frames: pw_dw_rect_kernel)
+template <int HW, int F, int BN, int KF, int S = 1, int NST_ = 2, int WD = HW>
 struct FTGeom {
   static constexpr int NST = NST_;                             // ring stages
   static constexpr int ROWB = KF * 4, RPI = 1024 / ROWB;       // row bytes; rows one LDS-DMA instruction fills (8 / 16)
-  static constexpr int P = HW * HW, M = F * P, MT = (M + 15) / 16, M_PAD = 16 * MT;
+  static constexpr int P = HW * WD, M = F * P, MT = (M + 15) / 16, M_PAD = 16 * MT;
   static constexpr int NT = BN / 16, WPN = 4 / NT;             // n-tiles; waves that share an n-tile
   static constexpr int MTW = (MT + WPN - 1) / WPN;             // m-tiles per wave
   static constexpr int ROWS = M_PAD + BN, LPT = (ROWS + 4 * RPI - 1) / (4 * RPI), STAGE = LPT * 4 * RPI * ROWB;
   static constexpr int NQ = BN / 4;                            // channel quads
-  static constexpr int HO = (HW + 2 - 3) / S + 1;              // output rows = columns
-  using E = ETile<HW, BN, F * HW>;                             // frame f occupies image rows f HW .. + HW - 1
-  static constexpr int RS = pick_runs(NQ * HO, HO, F), RPS = (HO + RS - 1) / RS;   // runs per frame, rows per run
+  static constexpr int HO = (HW + 2 - 3) / S + 1, WO = (WD + 2 - 3) / S + 1;   // output rows, columns
+  using E = ETile<WD, BN, F * HW>;                             // frame f occupies image rows f HW .. + HW - 1
+  static constexpr int RS = pick_runs(NQ * WO, HO, F), RPS = (HO + RS - 1) / RS;   // runs per frame, rows per run
   static constexpr size_t etile = E::bytes;
   static constexpr size_t lds = NST * (size_t)STAGE > etile ? NST * (size_t)STAGE : etile;
   static constexpr int occ = (int)(160 * 1024 / lds) >= 4 ? 4 : (int)(160 * 1024 / lds);
@@ -230,6 +231,92 @@ __device__ __forceinline__ void dw_run(const float* sE, int R0, int ox, int cq, 
   }
 }
 
+// pw_dw_kernel's body for frames of HW rows x WD columns, without the upsampled addend (pw_dw_rect_kernel; the square kernel
+// below keeps its own text, so its code does not move -- routed through this body, the compiler gave the deep 16x16 instance a
+// different register allocation)
+template <int HW, int F, int BN, int KF, int S, int NST, int WD>
+__device__ __forceinline__ void pw_dw_body(
+    const float* __restrict__ A, int lda, const float* __restrict__ W1, const float* __restrict__ b1,
+    const float* __restrict__ wd, const float* __restrict__ bd, float* __restrict__ D, int ldd, int frames, int K, int N,
+    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes) {
+  using G = FTGeom<HW, F, BN, KF, S, NST, WD>;
+  using E = typename G::E;
+  constexpr int ROWB = G::ROWB, RPI = G::RPI, CPR = ROWB / 16;   // 16-B columns per row
+  extern __shared__ __attribute__((aligned(16))) char ring[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, q = lane >> 4, lrow = lane / CPR, lcol = lane % CPR;
+
+  // XCD-aware tile order (speed only): workgroups b, b + 8, ... share an XCD; give each XCD a contiguous run of tiles so
+  // the channel tiles of one frame group (same A rows) meet in one L2
+  int ft, nt;
+  {
+    const int t = blockIdx.x, qn = nwg >> 3, r = nwg & 7, xcd = t & 7, idx = t >> 3;
+    const int bid = (xcd < r ? xcd * (qn + 1) : r * (qn + 1) + (xcd - r) * qn) + idx;
+    ft = bid / n_ntiles;
+    nt = bid - ft * n_ntiles;
+  }
+  const int f0 = ft * F, nf = frames - f0 < F ? frames - f0 : F;   // frames of this tile
+  const int m0 = f0 * G::P, m_valid = nf * G::P, n0 = nt * BN;
+  const int nk = K / KF;
+
+  // ---- LDS-DMA: this lane's source offset of each of the wave's LPT instructions (8 rows x 128 B each) ----
+  int voff[G::LPT];
+#pragma unroll
+  for (int j = 0; j < G::LPT; ++j) {
+    const int r = (j * 4 + wave) * RPI + lrow;             // row inside the stage: [0, M_PAD) = A, then BN rows of W1
+    const int cs = lcol ^ ft_key<KF>(r);                   // swizzled source column
+    if ((j * 4 + wave) * RPI < G::M_PAD) {
+      const int row = m0 + (r < m_valid ? r : m_valid - 1);   // pad rows re-read the last pixel; never used
+      voff[j] = (int)__umul24((unsigned)row, (unsigned)(lda * 4)) + cs * 16;   // rows < 2^24, row bytes < 2^24, operand < 2 GiB (launcher)
+    } else {
+      const int wr = r - G::M_PAD < BN ? r - G::M_PAD : 0;    // rows behind the tile (LPT rounds up) re-read W row 0
+      voff[j] = (n0 + wr) * K * 4 + cs * 16;
+    }
+  }
+  const int wn = wave % G::NT, wm = wave / G::NT;
+  f32x4 acc[G::MTW];
+  pw_dw_gemm<G, BN, KF>(ring, A, W1, a_bytes, w_bytes, voff, nk, wave, l15, q, acc);
+
+  // ---- epilogue 1: + b1, LeakyReLU -> the zero-bordered E image ----
+  float* sE = reinterpret_cast<float*>(ring);
+  e_zero_columns<E, F * HW, G::NQ, WD>(sE, tid);
+  {
+    const f32x4 bias = *reinterpret_cast<const f32x4*>(b1 + n0 + 16 * wn + 4 * q);
+#pragma unroll
+    for (int i = 0; i < G::MTW; ++i) {
+      const int t = wm + G::WPN * i;
+      const int px = 16 * t + l15;
+      if (t < G::MT && px < m_valid) {
+        const int f = px / G::P, rem = px - f * G::P, y = rem / WD, x = rem - y * WD;
+        *reinterpret_cast<f32x4*>(sE + E::at(f * HW + y, x, 4 * wn + q)) = lrelu4(acc[i] + bias);
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- epilogue 2: depthwise 3x3 (zero columns = the horizontal padding; the vertical one by skipping tap rows), + bd, LeakyReLU -> D ----
+  {
+    constexpr int HO = G::HO, WO = G::WO, NITEM = G::NQ * WO * G::RS * F;
+    f32x4 wt[9];
+    int cq_of = -1;
+    for (int id = tid; id < NITEM; id += 256) {
+      const int cq = id % G::NQ, rest = id / G::NQ, ox = rest % WO, run = rest / WO, f = run / G::RS, r0 = (run - f * G::RS) * G::RPS;
+      if (f >= nf) continue;
+      if (cq != cq_of) {   // (256 % NQ == 0: a thread keeps its channel quad; loaded once)
+        const float* wq = wd + n0 + 4 * cq;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) wt[t] = *reinterpret_cast<const f32x4*>(wq + (size_t)t * N);
+        cq_of = cq;
+      }
+      const f32x4 bv = *reinterpret_cast<const f32x4*>(bd + n0 + 4 * cq);
+      const int nrows = HO - r0 < G::RPS ? HO - r0 : G::RPS;
+      dw_run<E, S, HW, true>(sE, f * HW + r0 * S - 1, ox, cq, r0, wt, bv,
+                             D + ((size_t)(f0 + f) * HO * WO + (size_t)r0 * WO + ox) * ldd + n0 + 4 * cq, (size_t)WO * ldd, nrows);
+    }
+  }
+}
+
 template <int HW, int F, int BN, int KF, int S, int NST = 2>
 __global__ __launch_bounds__(256, (FTGeom<HW, F, BN, KF, S, NST>::occ)) void pw_dw_kernel(
     const float* __restrict__ A, int lda, const float* __restrict__ W1, const float* __restrict__ b1,
@@ -321,6 +408,16 @@ __global__ __launch_bounds__(256, (FTGeom<HW, F, BN, KF, S, NST>::occ)) void pw_
                              D + ((size_t)(f0 + f) * HO * HO + (size_t)r0 * HO + ox) * ldd + n0 + 4 * cq, (size_t)HO * ldd, nrows);
     }
   }
+}
+
+// Rectangular frames (AudioConvWenet's 16x32 blocks, module/unet.py:114-117): one whole H x W frame per tile, stride 1.  16x32 x
+// 32 channels: a 68-KB E image over a 72-KB two-stage ring -- two workgroups per CU.
+template <int H, int W, int BN, int KF>
+__global__ __launch_bounds__(256, (FTGeom<H, 1, BN, KF, 1, 2, W>::occ)) void pw_dw_rect_kernel(
+    const float* __restrict__ A, int lda, const float* __restrict__ W1, const float* __restrict__ b1,
+    const float* __restrict__ wd, const float* __restrict__ bd, float* __restrict__ D, int ldd, int frames, int K, int N,
+    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes, const float* __restrict__ ups, int ld_ups) {
+  pw_dw_body<H, 1, BN, KF, 1, 2, W>(A, lda, W1, b1, wd, bd, D, ldd, frames, K, N, n_ntiles, nwg, a_bytes, w_bytes);
 }
 
 // ---- 40 x 40 frames: a whole frame does not fit a tile (1600 pixels x 32 channels = 200 KB), so the tile is a STRIP of
@@ -461,13 +558,17 @@ int launch_fs(const float* a, int lda, const float* w1, const float* b1, const f
   return CASYNC_OK;
 }
 
-template <int HW, int F, int BN, int KF, int S, int NST = 2>
+template <int HW, int F, int BN, int KF, int S, int NST = 2, int WD = HW>
 int launch_ft(const float* a, int lda, const float* w1, const float* b1, const float* wd, const float* bd, float* d, int ldd,
               int frames, int k, int n, const float* ups, int ld_ups, hipStream_t stream) {
-  using G = FTGeom<HW, F, BN, KF, S, NST>;
-  auto kern = pw_dw_kernel<HW, F, BN, KF, S, NST>;
+  using G = FTGeom<HW, F, BN, KF, S, NST, WD>;
+  static_assert(WD == HW || (F == 1 && S == 1 && NST == 2), "rectangular frames: one frame per tile, stride 1, two stages");
+  auto kern = [] {
+    if constexpr (WD == HW) return pw_dw_kernel<HW, F, BN, KF, S, NST>;
+    else return pw_dw_rect_kernel<HW, WD, BN, KF>;
+  }();
   static unsigned long long attr_once = 0;
-  constexpr bool UPS_OK = F == 1 && BN == 32 && (HW / 2) * (HW / 2) * 128 <= kUpsTileBytes && G::lds % 16 == 0;   // (20x20: 12.8 KB)
+  constexpr bool UPS_OK = WD == HW && F == 1 && BN == 32 && (HW / 2) * (HW / 2) * 128 <= kUpsTileBytes && G::lds % 16 == 0;   // (20x20: 12.8 KB)
   CASYNC_REQUIRE(!ups || UPS_OK, "pw_dw: no upsampled addend for %dx%d tiles of %d frames", HW, HW, F);
   if (int st = casync_ensure_dyn_lds(&attr_once, reinterpret_cast<const void*>(kern), (int)G::lds + (UPS_OK ? kUpsTileBytes : 0))) return st;
   const int n_ft = (frames + F - 1) / F, n_nt = n / BN;
@@ -483,6 +584,28 @@ int launch_ft(const float* a, int lda, const float* w1, const float* b1, const f
 }
 
 }  // namespace
+
+bool pw_dw_rect_supported(int h, int w, int cin, int cexp, int stride) {
+  return h == 16 && w == 32 && stride == 1 && cin % 16 == 0 && cexp % 32 == 0;
+}
+
+const char* pw_dw_rect_kernel_name(int h, int w) {
+  static thread_local char buf[64];
+  snprintf(buf, sizeof(buf), "pw_dw_rect_kernel<%d, %d, 32, 16>", h, w);
+  return buf;
+}
+
+int launch_pw_dw_rect(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,
+                      int frames, int h, int w, int cin, int cexp, hipStream_t stream) {
+  CASYNC_REQUIRE(a && w1 && b1 && wd && bd && d && frames > 0, "pw_dw_rect: bad args");
+  CASYNC_REQUIRE(pw_dw_rect_supported(h, w, cin, cexp, 1), "pw_dw_rect: no instance for %dx%d cin=%d cexp=%d", h, w, cin, cexp);
+  CASYNC_REQUIRE(lda >= cin && lda % 4 == 0 && ldd >= cexp && ldd % 4 == 0, "pw_dw_rect: bad leading dimensions");
+  CASYNC_REQUIRE(((uintptr_t)a % 16) == 0 && ((uintptr_t)w1 % 16) == 0 && ((uintptr_t)d % 16) == 0 && ((uintptr_t)b1 % 16) == 0 &&
+                     ((uintptr_t)wd % 16) == 0 && ((uintptr_t)bd % 16) == 0,
+                 "pw_dw_rect: pointers must be 16-B aligned");
+  return launch_ft<16, 1, 32, 16, 1, 2, 32>(static_cast<const float*>(a), lda, static_cast<const float*>(w1), b1, wd, bd,
+                                            static_cast<float*>(d), ldd, frames, cin, cexp, nullptr, 0, stream);
+}
 
 bool pw_dw_supported(int hw, int cin, int cexp, int stride) {
   if (cin % 16 || cexp % 32) return false;

@@ -288,26 +288,27 @@ __device__ __forceinline__ int xcd_tile(int t, int nwg) {
   return (xcd < r ? xcd * (qn + 1) : r * (qn + 1) + (xcd - r) * qn) + idx;
 }
 
-// ---- whole frames: F frames of HW x HW pixels x BN channels per workgroup ----
-template <int HW, int F, int BN, int S>
-struct FTGeomB : GemmGeomB<F * HW * HW, BN> {
-  using Base = GemmGeomB<F * HW * HW, BN>;
-  static constexpr int P = HW * HW, M = F * P;
+// ---- whole frames: F frames of HW x WD pixels (WD = HW but for pw_dw_bf16_rect_kernel) x BN channels per workgroup ----
+template <int HW, int F, int BN, int S, int WD = HW>
+struct FTGeomB : GemmGeomB<F * HW * WD, BN> {
+  using Base = GemmGeomB<F * HW * WD, BN>;
+  static constexpr int P = HW * WD, M = F * P;
   static constexpr int NQ = BN / 8;                            // 16-B channel columns
-  static constexpr int HO = (HW + 2 - 3) / S + 1;              // output rows = columns
-  using E = ETileB<HW, BN, F * HW>;                            // frame f occupies image rows f HW .. + HW - 1
-  static constexpr int RPS = pick_rps(NQ * HO, HO, F, S), RS = (HO + RPS - 1) / RPS;   // rows per run, runs per frame
+  static constexpr int HO = (HW + 2 - 3) / S + 1, WO = (WD + 2 - 3) / S + 1;   // output rows, columns
+  using E = ETileB<WD, BN, F * HW>;                            // frame f occupies image rows f HW .. + HW - 1
+  static constexpr int RPS = pick_rps(NQ * WO, HO, F, S), RS = (HO + RPS - 1) / RPS;   // rows per run, runs per frame
   static constexpr size_t lds = (2 * (size_t)Base::STAGE > E::bytes ? 2 * (size_t)Base::STAGE : E::bytes + 15) / 16 * 16;
   static constexpr int occ = 160 * 1024 / lds >= 2 ? 2 : 1;
   static_assert(lds <= 160 * 1024, "LDS budget");
 };
 
-template <int HW, int F, int BN, int S>
-__global__ __launch_bounds__(256, (FTGeomB<HW, F, BN, S>::occ)) void pw_dw_bf16_kernel(
+template <int HW, int F, int BN, int S, int WD>
+__device__ __forceinline__ void pw_dw_bf16_body(
     const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W1, const float* __restrict__ b1,
     const float* __restrict__ wd, const float* __restrict__ bd, bf16_t* __restrict__ D, int ldd, int frames, int K, int N,
     int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes, const bf16_t* __restrict__ ups, int ld_ups) {
-  using G = FTGeomB<HW, F, BN, S>;
+  using G = FTGeomB<HW, F, BN, S, WD>;
+  constexpr bool SQ = WD == HW;
   using E = typename G::E;
   extern __shared__ __attribute__((aligned(16))) char ring[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -323,7 +324,8 @@ __global__ __launch_bounds__(256, (FTGeomB<HW, F, BN, S>::occ)) void pw_dw_bf16_
   dma_offsets<G>(voff, wave, lane, lda, K, n0, BN, [&](int r) { return m0 + (r < m_valid ? r : m_valid - 1); });   // pad rows re-read the last pixel
   // the low-resolution tile of the upsampled addend travels under the GEMM (F = 1 frame, BN = 64: the whole HW/2 x HW/2 frame)
   char* sG = ring + G::lds;
-  if (ups) ups_tile_load_b<HW / 2>(sG, ups + (size_t)f0 * (HW / 2) * (HW / 2) * ld_ups + n0, ld_ups, 0, HW / 2, wave, lane);
+  if constexpr (SQ)
+    if (ups) ups_tile_load_b<HW / 2>(sG, ups + (size_t)f0 * (HW / 2) * (HW / 2) * ld_ups + n0, ld_ups, 0, HW / 2, wave, lane);
   // (the expand biases are requested before the K loop and the depthwise taps before epilogue 1 -- both are the head of a
   // latency chain otherwise: a global load in front of the first instruction that needs it)
   const int ng = wave % G::NG, mg = wave / G::NG;
@@ -336,19 +338,21 @@ __global__ __launch_bounds__(256, (FTGeomB<HW, F, BN, S>::occ)) void pw_dw_bf16_
 
   // ---- epilogue 1: + b1 (+ the upsampled addend), LeakyReLU -> the zero-bordered bf16 E image ----
   char* sE = ring;
-  e_zero_border<E, F * HW, HW>(sE, tid);
+  e_zero_border<E, F * HW, WD>(sE, tid);
   {
 #pragma unroll
     for (int i = 0; i < G::MTW; ++i) {
       const int t = mg + G::MG * i;
       const int px = 16 * t + l15;
       if (t < G::MT && px < m_valid) {
-        const int f = px / G::P, rem = px - f * G::P, y = rem / HW, x = rem - y * HW;
+        const int f = px / G::P, rem = px - f * G::P, y = rem / WD, x = rem - y * WD;
         f32x4 v0 = acc[i][0] + bias0, v1 = acc[i][1] + bias1;
-        if (ups) {
-          const UpsCorners uc = ups_corners<HW>(0, y, x);
-          v0 += ups_at_lds_b(sG, uc, 4 * ng + (q >> 1), q & 1);
-          v1 += ups_at_lds_b(sG, uc, 4 * ng + 2 + (q >> 1), q & 1);
+        if constexpr (SQ) {
+          if (ups) {
+            const UpsCorners uc = ups_corners<HW>(0, y, x);
+            v0 += ups_at_lds_b(sG, uc, 4 * ng + (q >> 1), q & 1);
+            v1 += ups_at_lds_b(sG, uc, 4 * ng + 2 + (q >> 1), q & 1);
+          }
         }
         e_store<E>(sE, f * HW + y, x, ng, q, lrelu4(v0), lrelu4(v1));
       }
@@ -358,16 +362,34 @@ __global__ __launch_bounds__(256, (FTGeomB<HW, F, BN, S>::occ)) void pw_dw_bf16_
 
   // ---- epilogue 2: depthwise 3x3 (zero columns / the zero row = the padding), + bd, LeakyReLU -> D ----
   {
-    constexpr int HO = G::HO, NITEM = G::NQ * HO * G::RS * F;
+    constexpr int HO = G::HO, WO = G::WO, NITEM = G::NQ * WO * G::RS * F;
     static_assert(256 % G::NQ == 0, "a thread keeps its channel column");
     for (int id = tid; id < NITEM; id += 256) {
-      const int c = id % G::NQ, rest = id / G::NQ, ox = rest % HO, run = rest / HO, f = run / G::RS, r0 = (run - f * G::RS) * G::RPS;
+      const int c = id % G::NQ, rest = id / G::NQ, ox = rest % WO, run = rest / WO, f = run / G::RS, r0 = (run - f * G::RS) * G::RPS;
       if (f >= nf) continue;
       const int nrows = HO - r0 < G::RPS ? HO - r0 : G::RPS;
       dw_run_b<E, S, HW, true, G::RPS>(sE, f * HW + r0 * S - 1, r0 * S - 1, ox, c, taps,
-                                       D + ((size_t)(f0 + f) * HO * HO + (size_t)r0 * HO + ox) * ldd + n0 + 8 * c, (size_t)HO * ldd, nrows);
+                                       D + ((size_t)(f0 + f) * HO * WO + (size_t)r0 * WO + ox) * ldd + n0 + 8 * c, (size_t)WO * ldd, nrows);
     }
   }
+}
+
+template <int HW, int F, int BN, int S>
+__global__ __launch_bounds__(256, (FTGeomB<HW, F, BN, S>::occ)) void pw_dw_bf16_kernel(
+    const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W1, const float* __restrict__ b1,
+    const float* __restrict__ wd, const float* __restrict__ bd, bf16_t* __restrict__ D, int ldd, int frames, int K, int N,
+    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes, const bf16_t* __restrict__ ups, int ld_ups) {
+  pw_dw_bf16_body<HW, F, BN, S, HW>(A, lda, W1, b1, wd, bd, D, ldd, frames, K, N, n_ntiles, nwg, a_bytes, w_bytes, ups, ld_ups);
+}
+
+// Rectangular frames (AudioConvWenet's 16x32 blocks): one whole H x W frame per tile, stride 1, no upsampled addend.  16x32 x 64
+// channels: a 72-KB bf16 E image over a 72-KB two-stage ring -- two workgroups per CU, as the 20x20 instance.
+template <int H, int W, int BN>
+__global__ __launch_bounds__(256, (FTGeomB<H, 1, BN, 1, W>::occ)) void pw_dw_bf16_rect_kernel(
+    const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W1, const float* __restrict__ b1,
+    const float* __restrict__ wd, const float* __restrict__ bd, bf16_t* __restrict__ D, int ldd, int frames, int K, int N,
+    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes, const bf16_t* __restrict__ ups, int ld_ups) {
+  pw_dw_bf16_body<H, 1, BN, 1, W>(A, lda, W1, b1, wd, bd, D, ldd, frames, K, N, n_ntiles, nwg, a_bytes, w_bytes, nullptr, 0);
 }
 
 // ---- 40 x 40 frames: the tile is a STRIP of SR output rows of one frame -- its (SR - 1) * STRIDE + 3 input rows x 40
@@ -524,6 +546,32 @@ const char* pw_dw_bf16_kernel_name(int hw, int cexp, int frames, int stride) {
 }
 
 bool pw_dw_bf16_takes_ups(int hw, int stride) { return stride == 1 && (hw == 20 || hw == 40); }
+
+bool pw_dw_bf16_rect_supported(int h, int w, int cin, int cexp, int stride) {
+  return h == 16 && w == 32 && stride == 1 && cin % 32 == 0 && cexp % 64 == 0;
+}
+
+const char* pw_dw_bf16_rect_kernel_name(int h, int w) {
+  static thread_local char buf[64];
+  snprintf(buf, sizeof(buf), "pw_dw_bf16_rect_kernel<%d, %d, 64>", h, w);
+  return buf;
+}
+
+int launch_pw_dw_bf16_rect(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,
+                           int frames, int h, int w, int cin, int cexp, hipStream_t stream) {
+  CASYNC_REQUIRE(a && w1 && b1 && wd && bd && d && frames > 0, "pw_dw_rect (bf16): bad args");
+  CASYNC_REQUIRE(pw_dw_bf16_rect_supported(h, w, cin, cexp, 1), "pw_dw_rect (bf16): no instance for %dx%d cin=%d cexp=%d", h, w, cin, cexp);
+  CASYNC_REQUIRE(lda >= cin && lda % 8 == 0 && ldd >= cexp && ldd % 8 == 0, "pw_dw_rect (bf16): bad leading dimensions");
+  CASYNC_REQUIRE(((uintptr_t)a % 16) == 0 && ((uintptr_t)w1 % 16) == 0 && ((uintptr_t)d % 16) == 0 && ((uintptr_t)b1 % 16) == 0 &&
+                     ((uintptr_t)wd % 16) == 0 && ((uintptr_t)bd % 16) == 0,
+                 "pw_dw_rect (bf16): pointers must be 16-B aligned");
+  using G = FTGeomB<16, 1, 64, 1, 32>;
+  static unsigned long long attr_once = 0;
+  const int n_nt = cexp / 64;
+  return launch_common<G>(pw_dw_bf16_rect_kernel<16, 32, 64>, &attr_once, false, (long long)frames * n_nt, static_cast<const bf16_t*>(a),
+                          lda, static_cast<const bf16_t*>(w1), b1, wd, bd, static_cast<bf16_t*>(d), ldd, frames, cin, cexp, n_nt, nullptr,
+                          0, stream);
+}
 
 int launch_pw_dw_bf16(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,
                       int frames, int hw, int stride, int cin, int cexp, hipStream_t stream, const void* ups, int ld_ups) {

@@ -57,10 +57,11 @@ def _fold_dense3x3(sd: Mapping, conv: str, bn: str, out: Dict[str, np.ndarray]) 
     out[f"{conv}.b"] = _np64(sd[f"{conv}.bias"]) * s + t
 
 
-def fold(sd: Mapping) -> Dict[str, np.ndarray]:
-    """All packed tensors by engine name (float64; rounded when written)."""
+def fold(sd: Mapping, mode: str = "hubert") -> Dict[str, np.ndarray]:
+    """All packed tensors by engine name (float64; rounded when written).  ``mode``: the audio encoder
+    (``arch.MODES``); wenet has no bn7 (AudioConvWenet ends at conv7, module/unet.py:135-144)."""
     out: Dict[str, np.ndarray] = {}
-    blocks = arch.all_ir_blocks()
+    blocks = arch.all_ir_blocks(mode)
     for b in blocks:
         if b.prefix == "inc.inconv.0":
             tmp: Dict[str, np.ndarray] = {}
@@ -84,8 +85,9 @@ def fold(sd: Mapping) -> Dict[str, np.ndarray]:
         out[f"{b.prefix}.pw1b.w"] = np.ascontiguousarray(w1[:, c_lo:])
     _fold_dense3x3(sd, "audio_model.conv3", "audio_model.bn3", out)
     _fold_dense3x3(sd, "audio_model.conv5", "audio_model.bn5", out)
-    s7, t7 = _bn_affine(sd, "audio_model.bn7")
-    out["audio_model.bn7.s"], out["audio_model.bn7.t"] = s7, t7
+    if mode == "hubert":
+        s7, t7 = _bn_affine(sd, "audio_model.bn7")
+        out["audio_model.bn7.s"], out["audio_model.bn7.t"] = s7, t7
 
     # MLP fusion + bn_tx (module/unet.py:240-246, 323-326):
     #   tx = bn_tx(cat + bn2(fc2(lrelu(bn1(fc1(cat))))))
@@ -131,13 +133,13 @@ def fold(sd: Mapping) -> Dict[str, np.ndarray]:
     return out
 
 
-def pack(sd: Mapping, layout=None) -> np.ndarray:
-    """state_dict -> flat fp32 buffer in the engine's packed layout."""
+def pack(sd: Mapping, layout=None, mode: str = "hubert") -> np.ndarray:
+    """state_dict -> flat fp32 buffer in the engine's packed layout of audio mode ``mode``."""
     if layout is None:
         from . import _lib
-        layout = _lib.packed_layout()
+        layout = _lib.packed_layout(mode)
     items, total = layout
-    folded = fold(sd)
+    folded = fold(sd, mode)
     buf = np.zeros(total, dtype=np.float32)
     seen = set()
     for name, off, size in items:

@@ -61,10 +61,11 @@ def _stream(key: str) -> int:
     return zlib.crc32(key.encode("utf-8"))
 
 
-def make_state_dict(seed: int = WEIGHT_SEED) -> Dict[str, np.ndarray]:
-    """All 582 entries of the reference ``state_dict`` as NumPy arrays (G1.2)."""
+def make_state_dict(seed: int = WEIGHT_SEED, mode: str = "hubert") -> Dict[str, np.ndarray]:
+    """All 582 entries of the reference ``state_dict`` (wenet: 577) as NumPy arrays (G1.2).  A key present in both
+    modes with the same shape gets the same values in both."""
     sd: Dict[str, np.ndarray] = {}
-    for key, shape, dtype, role in arch.manifest():
+    for key, shape, dtype, role in arch.manifest(mode):
         n = int(np.prod(shape)) if shape else 1
         s = _stream(key)
         if role in ("conv_weight", "linear_weight"):
@@ -126,14 +127,14 @@ def make_inputs_b(batch: int = BATCH_B) -> Tuple[np.ndarray, np.ndarray]:
     return x, (a * np.float32(AUDIO_SCALE_B)).astype(np.float32)
 
 
-def make_inputs(batch: int, seed: int = INPUT_SEED) -> Tuple[np.ndarray, np.ndarray]:
-    """Synthetic frames: x ~ U(0,1) [B,6,160,160], audio ~ N(0,1) [B,32,32,32].
+def make_inputs(batch: int, seed: int = INPUT_SEED, mode: str = "hubert") -> Tuple[np.ndarray, np.ndarray]:
+    """Synthetic frames: x ~ U(0,1) [B,6,160,160], audio ~ N(0,1) [B,32,32,32] (wenet: [B,256,16,32]).
 
     Mirrors the reference self-benchmark's shapes
     (image_infer_v1/models/unet.py:342-347).  Frame ``b`` depends only on
     ``(seed, b)``, so any shard of a larger batch reproduces the same frames."""
     x = np.empty((batch, 6, arch.FACE_HW, arch.FACE_HW), dtype=np.float32)
-    a = np.empty((batch, 32, arch.AUDIO_HW, arch.AUDIO_HW), dtype=np.float32)
+    a = np.empty((batch,) + arch.AUDIO_SHAPE[mode], dtype=np.float32)
     for b in range(batch):
         x[b] = uniform01(seed, 0x1000000 + b, x[b].size).astype(np.float32).reshape(x[b].shape)
         a[b] = normal01(seed, 0x2000000 + b, a[b].size).astype(np.float32).reshape(a[b].shape)

@@ -56,19 +56,22 @@ def forward_chunked(net, x: torch.Tensor, audio: torch.Tensor, chunk: int = 512,
     return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
-def packed_total() -> int:
+def packed_total(mode: str = "hubert") -> int:
     from . import _lib
-    return int(_lib.load().casync_packed_total())
+    return int(_lib.load().casync_packed_total_m(_lib.AUDIO_MODES[mode]))
 
 
 def broadcast_packed_weights(model_on_src, device: torch.device, src: int = 0,
-                             group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
+                             group: Optional[dist.ProcessGroup] = None, mode: Optional[str] = None) -> torch.Tensor:
     """Rank `src` folds + packs its model's weights; everyone receives the flat buffer.
 
     ``model_on_src`` is the calipsync_amd.unet.Model holding the checkpoint on rank `src`
-    (ignored -- may be None -- elsewhere).  Returns a contiguous fp32 tensor on `device`
-    that ``Model.adopt_packed`` can take without another copy."""
-    n = packed_total()
+    (ignored -- may be None -- elsewhere).  ``mode``: the models' audio encoder (default: the
+    source model's, "hubert" on the other ranks -- a wenet run passes it on every rank).  Returns a
+    contiguous fp32 tensor on `device` that ``Model.adopt_packed`` can take without another copy."""
+    if mode is None:
+        mode = getattr(model_on_src, "mode", "hubert") if model_on_src is not None else "hubert"
+    n = packed_total(mode)
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     rank = dist.get_rank(group) if distributed else src
     if rank == src:

@@ -16,6 +16,11 @@ The module tree only *holds* parameters (so ``state_dict`` / ``load_state_dict``
 hand-written HIP kernels behind the C ABI of ``libcasync_hip.so``.  PyTorch is used for
 device memory and streams only.  There is no CPU or eager fallback: without a ROCm
 device or without the built library ``forward`` raises.
+
+Checkpoints of the reference's other audio encoder (``Model(6, "wenet")``, ``AudioConvWenet``,
+module/unet.py:109-144, 577 keys, audio ``[B,256,16,32]``) run through ``WenetModel(6)`` -- the same
+engine and the same methods.  ``Model`` itself keeps its contract: HuBERT only, any other mode raises
+``NotImplementedError`` (``tests/test_abi.py`` pins it).
 """
 from __future__ import annotations
 
@@ -70,26 +75,29 @@ def _default_init(key: str, shape, role: str) -> torch.Tensor:
 class Model(nn.Module):
     """CASync lip-sync U-Net on MI355X.  Same constructor and call contract as the
     reference ``Model(n_channels=6, mode='hubert', n_blocks=4)`` (module/unet.py:274)."""
+    _modes = ("hubert",)      # the audio encoders this class's constructor accepts
 
     def __init__(self, n_channels: int = 6, mode: str = "hubert", n_blocks: int = 4, *,
                  precision: str = "fp32"):
         """``precision`` (keyword-only extension of the reference signature): "fp32" is the
         parity path (|delta| < 1e-3 vs the reference, measured ~1e-6); "bf16" stores activations
-        and feeds the matrix cores in bf16 with fp32 accumulation (BASELINE configs[2]; ~1e-2)."""
+        and feeds the matrix cores in bf16 with fp32 accumulation (BASELINE configs[2]; ~1e-2).
+        ``mode``: "hubert" here; ``WenetModel`` takes "wenet"."""
         super().__init__()
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
         self._dtype = 1 if precision == "bf16" else 0
         if n_channels != 6:
             raise ValueError("the inference contract is 6 input channels (reference crop + masked crop)")
-        if mode != "hubert":
-            raise NotImplementedError(
-                "only mode='hubert' is on the inference path (infer_api.py:41); "
-                "AudioConvWenet is out of the hot-path contract")
+        if mode not in self._modes:
+            hint = "; WeNet checkpoints run through calipsync_amd.unet.WenetModel(6)" if mode == "wenet" else ""
+            raise NotImplementedError(f"{type(self).__name__}(mode={mode!r}): this class takes mode {self._modes[0]!r}"
+                                      f"{hint} (the reference's encoders: {arch.MODES}, module/unet.py:281-284)")
         if n_blocks != arch.N_ATT_BLOCKS:
             raise NotImplementedError("the engine is built for n_blocks=4 (reference default)")
         self.n_channels = n_channels
-        for key, shape, _dtype, role in arch.manifest():
+        self.mode = mode
+        for key, shape, _dtype, role in arch.manifest(mode):
             _install(self, key, _default_init(key, shape, role),
                      is_buffer=role in ("bn_mean", "bn_var", "bn_count"))
         self._engine: Optional[int] = None          # casync_handle
@@ -158,7 +166,8 @@ class Model(nn.Module):
             if self._engine is not None:
                 lib.casync_destroy(self._engine)
             h = C.c_void_p()
-            _lib.check(lib.casync_create_ex(dev.index or 0, self._dtype, C.byref(h)), "casync_create_ex")
+            _lib.check(lib.casync_create_mode(dev.index or 0, self._dtype, _lib.AUDIO_MODES[self.mode], C.byref(h)),
+                       "casync_create_mode")
             self._engine, self._engine_device = h, dev
             self._packed = None
             for name, value in self._options.items():
@@ -167,7 +176,7 @@ class Model(nn.Module):
     def packed_weights_host(self) -> np.ndarray:
         """BN-folded flat fp32 buffer (engine layout) from the current parameters."""
         sd = {k: v.detach().cpu() for k, v in self.state_dict().items()}
-        return pack.pack(sd)
+        return pack.pack(sd, mode=self.mode)
 
     def adopt_packed(self, packed_dev: torch.Tensor) -> None:
         """Use an already packed device buffer (e.g. filled by an RCCL broadcast)."""
@@ -206,8 +215,10 @@ class Model(nn.Module):
             raise RuntimeError("the MI355X engine implements the eval-mode forward only; call .eval()")
         if x.dim() != 4 or tuple(x.shape[1:]) != (6, arch.FACE_HW, arch.FACE_HW):
             raise RuntimeError(f"x must be [B,6,160,160], got {tuple(x.shape)}")
-        if audio_feat.dim() != 4 or tuple(audio_feat.shape[1:]) != (32, 32, 32):
-            raise RuntimeError(f"audio_feat must be [B,32,32,32], got {tuple(audio_feat.shape)}")
+        want = arch.AUDIO_SHAPE[self.mode]
+        if audio_feat.dim() != 4 or tuple(audio_feat.shape[1:]) != want:
+            raise RuntimeError(f"audio_feat must be [B,{','.join(map(str, want))}] (mode={self.mode!r}), "
+                               f"got {tuple(audio_feat.shape)}")
         if x.shape[0] != audio_feat.shape[0]:
             raise RuntimeError("x and audio_feat must have the same batch size")
         dev = self._device()
@@ -248,7 +259,11 @@ class Model(nn.Module):
         the window ``FrameSynthesizer._get_audio_features`` (reference infer_api.py:99-145)
         builds on the host, bit for bit, including its corner cases (a clip shorter than the pad, an
         index past the end or negative: the reference's truncated ``zeros_like`` pads then miss 16 rows
-        and it falls back to an all-zero window).  Equivalent to ``forward(x, windows)``."""
+        and it falls back to an all-zero window).  Equivalent to ``forward(x, windows)``.  HuBERT models only: the
+        reference builds no WeNet windows on its inference path."""
+        if self.mode != "hubert":
+            raise NotImplementedError("forward_windows gathers HuBERT windows; a mode='wenet' model takes its "
+                                      "[B,256,16,32] windows through forward()")
         dev = self._device()
         if dev.type != "cuda":
             raise RuntimeError("casync_amd.Model runs on a ROCm device only (no CPU fallback)")
@@ -294,13 +309,16 @@ class Model(nn.Module):
         shapes = {"x1": (160, 32), "x2": (80, 64), "x3": (40, 128), "x4": (20, 256), "x5": (10, 512),
                   "a": (10, 512), "tx": (10, 1024), "kx": (10, 1024), "fuse": (10, 256),
                   "u1": (20, 128), "u2": (40, 64), "u3": (80, 32), "u4": (160, 32),
-                  "audio_conv2": (32, 128), "audio_conv3": (16, 256), "audio_conv4": (16, 256),
+                  "audio_conv1": (32, 64), "audio_conv2": (32, 128), "audio_conv3": (16, 256), "audio_conv4": (16, 256),
                   "audio_conv5": (10, 512)}
+        shapes = {k: (hw, hw, c) for k, (hw, c) in shapes.items()}
+        if self.mode == "wenet":
+            shapes["audio_conv1"] = shapes["audio_conv2"] = (16, 32, 256)
         for i in range(4):
-            shapes[f"att{i}"] = (10, 1024)
-        hw, c = shapes[name]
-        assert per == hw * hw * c
-        return probe[:batch * per].view(batch, hw, hw, c).permute(0, 3, 1, 2).float().contiguous()
+            shapes[f"att{i}"] = (10, 10, 1024)
+        h, w, c = shapes[name]
+        assert per == h * w * c
+        return probe[:batch * per].view(batch, h, w, c).permute(0, 3, 1, 2).float().contiguous()
 
     @torch.no_grad()
     def profile(self, x: torch.Tensor, audio_feat: torch.Tensor) -> List[dict]:
@@ -326,3 +344,15 @@ class Model(nn.Module):
                 _lib.load().casync_destroy(self._engine)
         except Exception:
             pass
+
+
+class WenetModel(Model):
+    """The reference's ``Model(6, 'wenet')`` (``AudioConvWenet``, module/unet.py:109-144, 281-284) on the same engine:
+    strict ``load_state_dict`` of its 577-key checkpoints (no ``audio_model.bn7``), ``forward(x, audio_feat)`` with
+    ``audio_feat`` ``[B,256,16,32]`` fp32 (the reference dataset's reshape, dataset/dataset.py:173-174), ``tap``,
+    ``profile``, ``set_precision``, ``packed_weights_host`` / ``adopt_packed``.  ``forward_windows`` raises: the
+    reference has no inference-side WeNet window builder."""
+    _modes = ("wenet",)
+
+    def __init__(self, n_channels: int = 6, mode: str = "wenet", n_blocks: int = 4, *, precision: str = "fp32"):
+        super().__init__(n_channels, mode, n_blocks, precision=precision)

@@ -43,7 +43,7 @@ enum {
 /* ---- introspection (callable without a GPU) --------------------------- */
 /* Bumped on every change of a prototype, struct layout or the packed-weight layout; the ctypes
  * host (calipsync_amd/_lib.py) refuses a library whose version differs from the one it binds.   */
-#define CASYNC_ABI_VERSION 6
+#define CASYNC_ABI_VERSION 7
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -57,11 +57,25 @@ int64_t     casync_packed_offset(int i);
 int64_t     casync_packed_size(int i);
 int64_t     casync_packed_total(void);          /* floats in the whole buffer  */
 
+/* Audio encoder of a handle (reference Model(6, mode), module/unet.py:281-284), fixed at creation.
+ * The entries without a mode argument mean CASYNC_AUDIO_HUBERT.                                  */
+enum {
+  CASYNC_AUDIO_HUBERT = 0,    /* AudioConvHubert: audio [B,32,32,32], 582-key state_dict       */
+  CASYNC_AUDIO_WENET = 1      /* AudioConvWenet:  audio [B,256,16,32], 577 keys (no bn7)       */
+};
+/* The packed layout of one audio mode (wenet: no audio_model.bn7.s/.t, conv1 / conv2 take 256
+ * channels, conv3.w is 256 x 9 x 256).  An unknown mode answers 0 / NULL / -1.                   */
+int         casync_packed_count_m(int audio_mode);
+const char* casync_packed_name_m(int audio_mode, int i);
+int64_t     casync_packed_offset_m(int audio_mode, int i);
+int64_t     casync_packed_size_m(int audio_mode, int i);
+int64_t     casync_packed_total_m(int audio_mode);
+
 /* Workspace (activations, NHWC fp32) needed for a batch of B frames.        */
 int64_t     casync_workspace_bytes(int batch);               /* fp32 engine            */
 int64_t     casync_workspace_bytes_dt(int batch, int dtype); /* 0 = fp32, 1 = bf16     */
-/* ... for THIS handle (its dtype and options: the arena is smaller when the fused kernels are on,
- * which is the default).  Any arena at least this large is accepted by casync_forward.          */
+/* ... for THIS handle (its dtype, audio mode and options: the arena is smaller when the fused kernels
+ * are on, which is the default).  Any arena at least this large is accepted by casync_forward.  */
 int64_t     casync_workspace_bytes_h(casync_handle h, int batch);
 
 /* ---- tuning options ---------------------------------------------------- */
@@ -82,10 +96,13 @@ int  casync_create(int device_id, casync_handle* out);
  * (BASELINE configs[2]; ~1e-2 vs the reference, reported separately).  The boundary
  * tensors stay fp32 either way.                                                  */
 int  casync_create_ex(int device_id, int dtype, casync_handle* out);
+/* Model(6, "wenet") as well: audio_mode = CASYNC_AUDIO_HUBERT | CASYNC_AUDIO_WENET.  The handle's
+ * packed layout is casync_packed_*_m(audio_mode).                                                */
+int  casync_create_mode(int device_id, int dtype, int audio_mode, casync_handle* out);
 void casync_destroy(casync_handle h);
 
 /* Replaces net.load_state_dict(...) (infer_api.py:42): the packed, BN-folded
- * buffer of casync_packed_total() floats.  _host copies from host memory into
+ * buffer of casync_packed_total_m(mode) floats.  _host copies from host memory into
  * an engine-owned device buffer; _device adopts a caller-owned device buffer
  * (e.g. the tensor an RCCL broadcast just filled) without copying -- the
  * caller keeps it alive for the life of the handle.                          */
@@ -94,7 +111,9 @@ int  casync_load_weights_device(casync_handle h, const float* packed_dev, int64_
 
 /* Replaces Model.forward(x, audio_feat) (module/unet.py:314-345).
  *   x_dev     [B,6,160,160]  NCHW fp32   (reference crop ch0-2, masked crop ch3-5)
- *   audio_dev [B,32,32,32]   NCHW fp32   (HuBERT window)
+ *   audio_dev [B,32,32,32]   NCHW fp32   (HuBERT window; CASYNC_AUDIO_HUBERT handle)
+ *             [B,256,16,32]  NCHW fp32   (WeNet window, CASYNC_AUDIO_WENET handle: the reference
+ *                                         dataset's reshape, dataset/dataset.py:173-174)
  *   out_dev   [B,3,160,160]  NCHW fp32   in (0,1)
  * Enqueues on `stream`, no host synchronisation, no allocation.             */
 int  casync_forward(casync_handle h, const float* x_dev, const float* audio_dev,
@@ -105,14 +124,17 @@ int  casync_forward(casync_handle h, const float* x_dev, const float* audio_dev,
  * [n_steps, 2, 1024] fp32 feature array of the clip (uploaded once), frame_idx_dev[b] the video
  * frame index of batch entry b; entry b sees features[idx-8 : idx+8], zero-padded past both
  * ends, reshaped to (32,32,32) -- exactly FrameSynthesizer._get_audio_features
- * (infer_api.py:99-145), without the B x 128 KB host windows and their H2D copy.           */
+ * (infer_api.py:99-145), without the B x 128 KB host windows and their H2D copy.
+ * HuBERT handles only: a CASYNC_AUDIO_WENET handle returns CASYNC_ERR_ARG (the reference has no
+ * inference-side WeNet window builder).                                                     */
 int  casync_forward_windows(casync_handle h, const float* x_dev, const float* features_dev,
                             int n_steps, const int32_t* frame_idx_dev, float* out_dev, int batch,
                             void* workspace_dev, int64_t workspace_bytes, casync_stream stream);
 
 /* Debug taps: copy a named NHWC intermediate of the LAST forward (same batch,
  * same workspace) into dst_dev; returns its per-frame float count or <0.
- * Names: x1 x2 x3 x4 x5 a tx kx fuse u1 u2 u3 u4 att0..att3 audio_conv2..5   */
+ * Names: x1 x2 x3 x4 x5 a tx kx fuse u1 u2 u3 u4 att0..att3 audio_conv1..5
+ * (audio_conv1 / audio_conv2 of a wenet handle are 16x32 frames of 256 channels)  */
 int64_t casync_tap(casync_handle h, const char* name, int batch, void* workspace_dev,
                    void* dst_dev, int64_t dst_elems, casync_stream stream);  /* dst: engine dtype */
 
@@ -157,6 +179,11 @@ int casync_debug_ir_stamps(void* dev_words);
  * out [B,Ho,Wo,cout].  cin % (128 B / elem) == 0, cout % 64 == 0. */
 int casync_op_conv3x3(const void* in, const void* w, const float* bias, void* out, int batch, int h, int w_,
                       int cin, int cout, int stride, int pad, int act, casync_stream stream);
+/* The same with the strides of the two axes apart and a choice of activation: act 0 = none,
+ * 1 = LeakyReLU(0.01), 2 = ReLU (AudioConvWenet conv3: stride (1,2) pad 1, conv5: stride 2 pad 3,
+ * each + BN + ReLU; module/unet.py:119-133).  Ho = (h+2pad-3)/stride_h+1, Wo = (w+2pad-3)/stride_w+1. */
+int casync_op_conv3x3_ex(const void* in, const void* w, const float* bias, void* out, int batch, int h, int w_,
+                         int cin, int cout, int stride_h, int stride_w, int pad, int act, casync_stream stream);
 
 /* Depthwise 3x3, pad 1, stride 1|2, + bias + LeakyReLU on NHWC.
  * Replaces nn.Conv2d(groups=C,k=3)+BN+LeakyReLU (module/unet.py:21-30).
