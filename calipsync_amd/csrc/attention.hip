@@ -191,11 +191,6 @@ __global__ __launch_bounds__(256) void cross_attention_kernel(
 
 }  // namespace
 
-const char* cross_attention_kernel_name(int dtype) {
-  if (dtype == DT_BF16) return casync_opts().att_bf16 ? "cross_attention_bf16_kernel" : "cross_attention_kernel<__bf16>";
-  return "cross_attention_kernel<float>";
-}
-
 int launch_cross_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                            const void* res, int ld_res, const float* gamma_dev, void* out,
                            int ld_out, int batch, hipStream_t stream, int dtype) {
@@ -220,13 +215,10 @@ int launch_cross_attention(const void* q, int ldq, const void* k, int ldk, const
   if (forced_nz == 1 || forced_nz == 2 || forced_nz == 4) nz = forced_nz;
   const dim3 grid(batch, 4, nz);
   if (dtype == DT_BF16)
-    hipLaunchKernelGGL(cross_attention_kernel<bf16_t>, grid, dim3(256), ATT_LDS_BYTES, stream, (const bf16_t*)q,
-                       ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (const bf16_t*)res, ld_res, gamma_dev,
-                       (bf16_t*)out, ld_out);
-  else
-    hipLaunchKernelGGL(cross_attention_kernel<float>, grid, dim3(256), ATT_LDS_BYTES, stream, (const float*)q,
+    return casync_launch(cross_attention_kernel<bf16_t>, grid, dim3(256), ATT_LDS_BYTES, stream, (const bf16_t*)q,
+                         ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (const bf16_t*)res, ld_res, gamma_dev,
+                         (bf16_t*)out, ld_out);
+  return casync_launch(cross_attention_kernel<float>, grid, dim3(256), ATT_LDS_BYTES, stream, (const float*)q,
                        ldq, (const float*)k, ldk, (const float*)v, ldv, (const float*)res, ld_res, gamma_dev,
                        (float*)out, ld_out);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
 }

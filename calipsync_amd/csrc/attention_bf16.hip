@@ -224,8 +224,6 @@ int launch_cross_attention_bf16(const void* q, int ldq, const void* k, int ldk, 
                  "cross_attention (bf16): alignment");
   static unsigned long long once = 0;
   if (int st = casync_ensure_dyn_lds(&once, reinterpret_cast<const void*>(cross_attention_bf16_kernel), ATTB_LDS_BYTES)) return st;
-  hipLaunchKernelGGL(cross_attention_bf16_kernel, dim3(batch), dim3(256), ATTB_LDS_BYTES, stream, (const bf16_t*)q, ldq,
-                     (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (const bf16_t*)res, ld_res, gamma_dev, (bf16_t*)out, ld_out);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  return casync_launch(cross_attention_bf16_kernel, dim3(batch), dim3(256), ATTB_LDS_BYTES, stream, (const bf16_t*)q, ldq,
+                       (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (const bf16_t*)res, ld_res, gamma_dev, (bf16_t*)out, ld_out);
 }

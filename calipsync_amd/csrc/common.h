@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <utility>
+
 #include "../../include/casync_hip.h"
 
 #define CASYNC_LRELU_SLOPE 0.01f
@@ -168,6 +170,23 @@ int casync_ensure_dyn_lds(unsigned long long* once_mask, const void* fn, int byt
     }                                                                                 \
   } while (0)
 
+// Every device launch of the engine: launch, check, and note the kernel on this thread.  The profile names each row
+// from that note (engine.hip, Runner::run), so the instance a launcher picks is known in one place only.
+struct CasyncLaunchNote {
+  const void* kernel = nullptr;   // the last kernel launched on this thread
+  unsigned count = 0;             // launches since the note was cleared
+};
+inline thread_local CasyncLaunchNote casync_launch_note;
+
+template <typename... P, typename... A>
+int casync_launch(void (*k)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A&&... a) {
+  hipLaunchKernelGGL(k, grid, block, lds, s, std::forward<A>(a)...);
+  CASYNC_CHECK_HIP(hipGetLastError());
+  casync_launch_note.kernel = reinterpret_cast<const void*>(k);
+  ++casync_launch_note.count;
+  return CASYNC_OK;
+}
+
 #define CASYNC_REQUIRE(cond, ...)                \
   do {                                           \
     if (!(cond)) {                               \
@@ -244,8 +263,6 @@ constexpr long long kStreamKFloats = 2ll * kStreamKWgs * 128 * 64;  // two parti
 constexpr int kStreamKCounters = 256;
 constexpr long long kStreamKBytes = kStreamKFloats * 4 + kStreamKCounters * 4;
 
-const char* pw_gemm_kernel_name(int m, int n, int k, bool stream_k, int dtype = DT_F32, bool concurrent = false,
-                                bool ups = false);
 // a, w, c (and the (T) epilogue pointers) are `dtype` elements; lda/ldc in elements
 int launch_pw_gemm(const void* a, int lda, const void* w, void* c, int ldc, int m, int n, int k,
                    const GemmEpilogue& epi, hipStream_t stream, int dtype = DT_F32);
@@ -256,19 +273,13 @@ int launch_pw_gemm(const void* a, int lda, const void* w, void* c, int ldc, int 
 int launch_conv3x3_gemm(const void* in, const void* w, void* out, int ldc, int batch, int h, int wdt, int cin,
                         int cout, int stride_h, int stride_w, int pad, const GemmEpilogue& epi, hipStream_t stream,
                         int dtype = DT_F32);
-const char* conv3x3_gemm_kernel_name(int batch, int h, int wdt, int cin, int cout, int stride_h, int stride_w, int pad,
-                                     int dtype = DT_F32, bool concurrent = false, bool stream_k = false);
 
 // ---- other operators -------------------------------------------------------
 int launch_dw3x3(const void* in, const float* w, const float* bias, void* out, int batch, int h,
                  int wdt, int c, int stride, hipStream_t stream, int dtype = DT_F32);
-const char* dw3x3_kernel_name(int h, int wdt, int c, int stride, int dtype = DT_F32);
 int launch_dw3x3_ups(const float* pre, const float* g, int ldg, const float* w, const float* bias, float* out, int batch, int h,
                      int wdt, int c, hipStream_t stream);
-const char* dw3x3_ups_kernel_name(int h, int wdt, int c);
 bool ir_fused_supported(int cin, int cout, int stride);
-// as rocprofv3 prints it; h, w > 0: the instance launch_ir_fused / launch_ir_fused_up picks for that shape
-const char* ir_fused_kernel_name(int cin, int cout, int stride, int dtype = DT_F32, bool ups = false, int h = 0, int w = 0);
 bool ir_fused_up_supported(int cin, int cout);
 int launch_ir_fused_up(const void* lo, int ld_lo, int c_lo, const void* in, int ld_in, const void* w1,
                        const float* b1, const float* wd, const float* bd, const void* w2,
@@ -278,7 +289,6 @@ int launch_ir_fused_up(const void* lo, int ld_lo, int c_lo, const void* in, int 
 int launch_ir_fused_upg(const float* g, int ld_g, const float* in, int ld_in, const float* w1, const float* b1,
                         const float* wd, const float* bd, const float* w2, const float* b2, float* out, int ld_out,
                         int batch, int h, int w, int cin, int cout, hipStream_t stream);
-const char* ir_fused_upg_kernel_name(int cin, int cout);
 // w1 / w2 are in the call's storage type (fp32 or bf16); b1, wd, bd, b2 are always fp32
 int launch_ir_fused(const void* in, int ld_in, const void* w1, const float* b1, const float* wd,
                     const float* bd, const void* w2, const float* b2, void* out, int ld_out,
@@ -287,7 +297,6 @@ int launch_ir_fused(const void* in, int ld_in, const void* w1, const float* b1, 
 // expand 1x1 + depthwise 3x3 of a low-resolution inverted residual in one kernel (pw_dw.hip): fp32, 10x10 / 16x16 /
 // 20x20 frames; a [frames*hw*hw, lda], w1 [cexp][cin], wd [9][cexp], d [frames*ho*ho, ldd]
 bool pw_dw_supported(int hw, int cin, int cexp, int stride);
-const char* pw_dw_kernel_name(int hw, int cin, int frames, int stride = 1);
 bool pw_dw_deep(int hw, int frames, int stride, bool ups, int cin);   // the launch takes the deep-ring one-frame tiles
 // ups (optional): low-resolution addend [frames*(hw/2)^2, ld_ups] whose bilinear x2 upsample is added before the first
 // activation (an Up block's upsampled half, see GemmEpilogue::ups_src)
@@ -295,17 +304,14 @@ int launch_pw_dw(const void* a, int lda, const void* w1, const float* b1, const 
                  int frames, int hw, int stride, int cin, int cexp, hipStream_t stream, const void* ups = nullptr, int ld_ups = 0);
 // rectangular frames (AudioConvWenet's 16x32 blocks, stride 1, no upsampled addend): one whole frame per tile
 bool pw_dw_rect_supported(int h, int w, int cin, int cexp, int stride);
-const char* pw_dw_rect_kernel_name(int h, int w);
 int launch_pw_dw_rect(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,
                       int frames, int h, int w, int cin, int cexp, hipStream_t stream);
 // the bf16 engine's expand + depthwise kernel (pw_dw_bf16.hip): a, w1, d bf16; b1, wd, bd fp32; cin % 32 == 0, cexp % 64 == 0
 bool pw_dw_bf16_supported(int hw, int cin, int cexp, int stride);
-const char* pw_dw_bf16_kernel_name(int hw, int cexp, int frames, int stride = 1);
 // ups (optional, 20x20 / 40x40 stride 1): bf16 low-resolution addend [frames*(hw/2)^2, ld_ups], see launch_pw_dw
 bool pw_dw_bf16_takes_ups(int hw, int stride);
 // ... and its rectangular-frame counterpart (16x32, stride 1, no upsampled addend)
 bool pw_dw_bf16_rect_supported(int h, int w, int cin, int cexp, int stride);
-const char* pw_dw_bf16_rect_kernel_name(int h, int w);
 int launch_pw_dw_bf16_rect(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,
                            int frames, int h, int w, int cin, int cexp, hipStream_t stream);
 int launch_pw_dw_bf16(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,
@@ -315,7 +321,6 @@ int launch_upsample2x(const void* in, void* out, int ldc, int batch, int h, int 
 int launch_cross_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                            const void* res, int ld_res, const float* gamma_dev, void* out,
                            int ld_out, int batch, hipStream_t stream, int dtype = DT_F32);
-const char* cross_attention_kernel_name(int dtype);
 // the bf16 engine's attention core (attention_bf16.hip): q, k, v, res, out bf16; one workgroup per frame
 int launch_cross_attention_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* res, int ld_res,
                                 const float* gamma_dev, void* out, int ld_out, int batch, hipStream_t stream);

@@ -346,6 +346,39 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restric
   if (i < n) st4(out + i, ld4(in + i));
 }
 
+// Short name of a mangled kernel symbol, as tools/kernel_names.py short() writes it ("pw_gemm_kernel<__bf16, 128, 128, 2, 2>"),
+// and a port of its decoder: the template arguments of this engine's kernels are float / __bf16 / int / bool literals, any
+// other shape keeps the bare name.  (Not a general demangler: binutils' does not know DF16b, the mangling of __bf16.)
+std::string kernel_short_name(const char* m) {
+  const char* p = strncmp(m, "_ZN12_GLOBAL__N_1", 17) == 0 ? m + 17 : strncmp(m, "_Z", 2) == 0 ? m + 2 : nullptr;
+  char* end = nullptr;
+  const size_t n = p ? strtoul(p, &end, 10) : 0;
+  if (!p || end == p || strlen(end) < n) return m;
+  const std::string name(end, n);
+  const char* r = end + n;
+  if (*r != 'I') return name;
+  std::string args;
+  for (++r; *r && *r != 'E';) {
+    if (!args.empty()) args += ", ";
+    if (strncmp(r, "DF16b", 5) == 0) {
+      args += "__bf16";
+      r += 5;
+    } else if (*r == 'f') {
+      args += "float";
+      ++r;
+    } else if (r[0] == 'L' && (r[1] == 'i' || r[1] == 'b')) {
+      const char* e = strchr(r, 'E');
+      if (!e) return name;
+      const std::string v(r + 2, e);
+      args += r[1] == 'b' ? (v == "1" ? "true" : "false") : (v[0] == 'n' ? "-" + v.substr(1) : v);
+      r = e + 1;
+    } else {
+      return name;
+    }
+  }
+  return name + "<" + args + ">";
+}
+
 // ------------------------------------------------------------------ launch recorder
 struct Runner {
   hipStream_t s;
@@ -354,28 +387,37 @@ struct Runner {
   std::vector<hipEvent_t> ev;
   int status = CASYNC_OK;
 
+  // f() issues one kernel launch (casync_launch): a profiled row is named after the kernel it launched
   template <class F>
-  void run(const char* name, const char* kernel, double flops, double bytes, F&& f) {
+  void run(const char* name, double flops, double bytes, F&& f) {
     if (status != CASYNC_OK) return;
-    if (profile) {
-      hipEvent_t a, b;
-      (void)hipEventCreate(&a);
-      (void)hipEventCreate(&b);
-      (void)hipEventRecord(a, s);
+    if (!profile) {
       status = f();
-      (void)hipEventRecord(b, s);
-      ev.push_back(a);
-      ev.push_back(b);
-      casync_kernel_time t;
-      memset(&t, 0, sizeof(t));
-      strncpy(t.name, name, sizeof(t.name) - 1);
-      strncpy(t.kernel, kernel, sizeof(t.kernel) - 1);
-      t.flops = flops;
-      t.bytes = bytes;
-      rec.push_back(t);
-    } else {
-      status = f();
+      return;
     }
+    hipEvent_t a, b;
+    (void)hipEventCreate(&a);
+    (void)hipEventCreate(&b);
+    (void)hipEventRecord(a, s);
+    casync_launch_note = CasyncLaunchNote();
+    status = f();
+    (void)hipEventRecord(b, s);
+    ev.push_back(a);
+    ev.push_back(b);
+    if (status == CASYNC_OK && casync_launch_note.count != 1) {
+      casync_set_error("profile: %s issued %u kernel launches, not one", name, casync_launch_note.count);
+      status = CASYNC_ERR_STATE;
+    }
+    casync_kernel_time t;
+    memset(&t, 0, sizeof(t));
+    strncpy(t.name, name, sizeof(t.name) - 1);
+    if (status == CASYNC_OK) {
+      const char* mangled = hipKernelNameRefByPtr(casync_launch_note.kernel, s);
+      strncpy(t.kernel, mangled ? kernel_short_name(mangled).c_str() : "?", sizeof(t.kernel) - 1);
+    }
+    t.flops = flops;
+    t.bytes = bytes;
+    rec.push_back(t);
   }
   void finish() {
     if (!profile) return;
@@ -433,10 +475,6 @@ struct Plan {
 
   // GEMM wrapper with work accounting (algorithmic bytes: A + C once, W once)
   int dt() const { return e.dtype; }
-  const char* tn() const { return e.dtype == DT_BF16 ? "__bf16" : "float"; }
-  std::string kname(const char* base, const char* rest = "") const {
-    return std::string(base) + "<" + tn() + rest + ">";
-  }
 
   void gemm(const std::string& tag, const void* a, int lda, const std::string& wname, void* c,
             int ldc, long long m, int n, int k, GemmEpilogue epi, const std::string& bname = "",
@@ -454,8 +492,7 @@ struct Plan {
     }
     epi.concurrent = concurrent ? 1 : 0;
     epi.stamps = g_gemm_stamps;
-    r.run(tag.c_str(), pw_gemm_kernel_name((int)m, n, k, epi.sk_ws != nullptr, dt(), concurrent, epi.ups_src != nullptr),
-          alg_flops > 0 ? alg_flops : 2.0 * m * n * k, bytes,
+    r.run(tag.c_str(), alg_flops > 0 ? alg_flops : 2.0 * m * n * k, bytes,
           [&] { return launch_pw_gemm(a, lda, w, c, ldc, (int)m, n, k, epi, r.s, dt()); });
   }
 
@@ -475,8 +512,7 @@ struct Plan {
       ep.sk_cnt = reinterpret_cast<unsigned*>(ctx + kStreamKFloats * 4);
     }
     const double es = dtype_size(dt());
-    r.run(tag.c_str(), conv3x3_gemm_kernel_name(B, h, w, cin, cout, stride_h, stride_w, pad, dt(), concurrent, ep.sk_ws != nullptr),
-          2.0 * m * cout * 9 * cin, es * ((double)B * h * w * cin + (double)m * cout + 9.0 * cin * cout), [&] {
+    r.run(tag.c_str(), 2.0 * m * cout * 9 * cin, es * ((double)B * h * w * cin + (double)m * cout + 9.0 * cin * cout), [&] {
       return launch_conv3x3_gemm(in, e.WG(wname), out, cout, B, h, w, cin, cout, stride_h, stride_w, pad, ep, r.s, dt());
     });
   }
@@ -494,8 +530,7 @@ struct Plan {
     if (!extra && !ups.p && ir_is_fused(o, b)) {
       const double flops = 2.0 * (m_in * (double)b.cin * b.cexp() + 9.0 * m_out * b.cexp() +
                                   (double)m_out * b.cexp() * b.cout);
-      r.run((p + ".fused").c_str(), ir_fused_kernel_name(b.cin, b.cout, b.stride, dt(), false, b.hw_in, b.hw_in), flops,
-            dtype_size(dt()) * (m_in * (double)b.cin + (double)m_out * b.cout), [&] {
+      r.run((p + ".fused").c_str(), flops, dtype_size(dt()) * (m_in * (double)b.cin + (double)m_out * b.cout), [&] {
         return launch_ir_fused(in, ld_in, e.WG(p + ".pw1.w"), e.W(p + ".pw1.b"), e.W(p + ".dw.w"),
                                e.W(p + ".dw.b"), e.WG(p + ".pw2.w"), e.W(p + ".pw2.b"), out, ld_out, B,
                                b.hw_in, b.hw_in, b.cin, b.cout, b.stride, b.res, r.s, dt());
@@ -516,16 +551,14 @@ struct Plan {
     const bool sq = b.square();
     const bool deep = sq && pw_dw_deep(b.hw_in, B, b.stride, ups.p != nullptr, k_in);
     if (dt() == DT_F32 && o.fuse_dw && !sq && !ups.p && B >= o.fuse_dw_min && pw_dw_rect_supported(b.hw_in, b.wd(), k_in, b.cexp(), b.stride)) {
-      r.run((p + ".pw1dw").c_str(), pw_dw_rect_kernel_name(b.hw_in, b.wd()),
-            2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
+      r.run((p + ".pw1dw").c_str(), 2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
             4.0 * (m_in * (double)k_in + (double)b.cexp() * k_in + (double)m_out * b.cexp()), [&] {
         return launch_pw_dw_rect(in, ld_in, e.W(w1name), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, b.cexp(), B,
                                  b.hw_in, b.wd(), k_in, b.cexp(), r.s);
       });
     } else if (dt() == DT_BF16 && o.fuse_dw_bf16 && !sq && !ups.p && B >= o.fuse_dw_bf16_min &&
                pw_dw_bf16_rect_supported(b.hw_in, b.wd(), k_in, b.cexp(), b.stride)) {
-      r.run((p + ".pw1dw").c_str(), pw_dw_bf16_rect_kernel_name(b.hw_in, b.wd()),
-            2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
+      r.run((p + ".pw1dw").c_str(), 2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
             2.0 * (m_in * (double)k_in + (double)b.cexp() * k_in + (double)m_out * b.cexp()), [&] {
         return launch_pw_dw_bf16_rect(in, ld_in, e.WG(w1name), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, b.cexp(), B,
                                       b.hw_in, b.wd(), k_in, b.cexp(), r.s);
@@ -534,8 +567,7 @@ struct Plan {
         pw_dw_supported(b.hw_in, k_in, b.cexp(), b.stride)) {
       // expand GEMM whose output tile is whole frames: the depthwise conv runs on the tile in LDS, E never exists
       // (flops: what this launch executes -- with `ups` the upsampled half was a GEMM at the low resolution)
-      r.run((p + ".pw1dw").c_str(), pw_dw_kernel_name(b.hw_in, k_in, B, b.stride),
-            2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
+      r.run((p + ".pw1dw").c_str(), 2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
             4.0 * (m_in * (double)k_in + (double)b.cexp() * k_in + (double)m_out * b.cexp()), [&] {
         return launch_pw_dw(in, ld_in, e.W(w1name), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2,
                             b.cexp(), B, b.hw_in, b.stride, k_in, b.cexp(), r.s, ups.p, b.cexp());
@@ -543,8 +575,7 @@ struct Plan {
     } else if (dt() == DT_BF16 && o.fuse_dw_bf16 && sq && (b.hw_in < 40 || o.fuse_dw_bf16 >= 2) && B >= o.fuse_dw_bf16_min &&
                pw_dw_bf16_supported(b.hw_in, k_in, b.cexp(), b.stride) && (!ups.p || pw_dw_bf16_takes_ups(b.hw_in, b.stride))) {
       // the bf16 engine's counterpart (round 5): 64-channel tiles, bf16 E image in LDS; E never reaches HBM
-      r.run((p + ".pw1dw").c_str(), pw_dw_bf16_kernel_name(b.hw_in, b.cexp(), B, b.stride),
-            2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
+      r.run((p + ".pw1dw").c_str(), 2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
             2.0 * (m_in * (double)k_in + (double)b.cexp() * k_in + (double)m_out * b.cexp()), [&] {
         return launch_pw_dw_bf16(in, ld_in, e.WG(w1name), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, b.cexp(), B,
                                  b.hw_in, b.stride, k_in, b.cexp(), r.s, ups.p, b.cexp());
@@ -562,8 +593,7 @@ struct Plan {
         ep1.ups_h = ep1.ups_w = b.hw_in;
       }
       gemm(p + ".pw1", in, ld_in, w1name, e1, b.cexp(), m_in, b.cexp(), k_in, ep1, p + ".pw1.b");
-      r.run((p + ".dw").c_str(), dw3x3_kernel_name(b.hw_in, b.wd(), b.cexp(), b.stride, dt()),
-            2.0 * 9 * m_out * b.cexp(), dtype_size(dt()) * (double)(m_in + m_out) * b.cexp(), [&] {
+      r.run((p + ".dw").c_str(), 2.0 * 9 * m_out * b.cexp(), dtype_size(dt()) * (double)(m_in + m_out) * b.cexp(), [&] {
         return launch_dw3x3(e1, e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, B, b.hw_in, b.wd(), b.cexp(),
                             b.stride, r.s, dt());
       });
@@ -609,7 +639,7 @@ struct Plan {
     if (e.mode == CASYNC_AUDIO_WENET) {
       // [B,256,16,32] -> NHWC 16x32 x 256; two residual blocks at 16x32; conv3 (1,2)-strided to 16x16 + ReLU; conv4; conv5
       // + ReLU to 10x10; conv6; conv7 straight into the audio half of cat([x5, a]) (no bn7 / relu7)
-      r.run("audio.nchw_to_nhwc", kname("nchw_to_nhwc_kernel").c_str(), 0, (4.0 + dtype_size(dt())) * B * 131072,
+      r.run("audio.nchw_to_nhwc", 0, (4.0 + dtype_size(dt())) * B * 131072,
             [&] { return launch_nchw_to_nhwc(audio, ar[A::A0], B, 256, 512, r.s, dt()); });
       ir(kAudioW[0], ar[A::A0], 256, ar[A::AC1], 256, AE1, AE2);
       ir(kAudioW[1], ar[A::AC1], 256, ar[A::AC2], 256, AE1, AE2);
@@ -620,10 +650,10 @@ struct Plan {
       ir(kAudio[4], ar[A::AC6], 512, ar[A::CATA] + 512, 1024, AE1, AE2);
     } else {
     if (win_feat)
-      r.run("audio.window_gather", kname("audio_window_gather_kernel").c_str(), 0, (4.0 + dtype_size(dt())) * B * 32768,
+      r.run("audio.window_gather", 0, (4.0 + dtype_size(dt())) * B * 32768,
             [&] { return launch_audio_window_gather(win_feat, win_steps, win_idx, ar[A::A0], B, r.s, dt()); });
     else
-      r.run("audio.nchw_to_nhwc", kname("nchw_to_nhwc_kernel").c_str(), 0, (4.0 + dtype_size(dt())) * B * 32768,
+      r.run("audio.nchw_to_nhwc", 0, (4.0 + dtype_size(dt())) * B * 32768,
             [&] { return launch_nchw_to_nhwc(audio, ar[A::A0], B, 32, 1024, r.s, dt()); });
     ir(kAudio[0], ar[A::A0], 32, ar[A::AC1], 64, AE1, AE2);
     ir(kAudio[1], ar[A::AC1], 64, ar[A::AC2], 128, AE1, AE2);
@@ -648,7 +678,7 @@ struct Plan {
       r.s = main_s;
     }
     // ---------------- face encoder (module/unet.py:315-319)
-    r.run("inc", dt() == DT_BF16 && o.inc_mfma ? "inc_bf16_kernel" : kname("inc_kernel").c_str(), 2.0 * B * 25600 * (72 + 108 + 384),
+    r.run("inc", 2.0 * B * 25600 * (72 + 108 + 384),
           (double)B * 25600 * (6 * 4 + 32 * dtype_size(dt())), [&] {
       return launch_inc(x, e.W("inc.inconv.0.fused"), ar[A::CAT4] + 32, 64, B, r.s, dt());
     });
@@ -736,7 +766,7 @@ struct Plan {
         ldq = 64;
       }
       Ptr kv = ar[A::KV] + i * kKV;
-      r.run((p + ".attn").c_str(), cross_attention_kernel_name(dt()), 2.0 * M10 * 100 * (64 + 512),
+      r.run((p + ".attn").c_str(), 2.0 * M10 * 100 * (64 + 512),
             dtype_size(dt()) * (double)M10 * (64 + kKV + 1024), [&] {
         return launch_cross_attention(Qp, ldq, kv, kBlocks * kKV, kv + 64, kBlocks * kKV, P1, 576,
                                       e.W(p + ".gamma"), ar[A::AO], 512, B, r.s, dt());
@@ -793,7 +823,7 @@ struct Plan {
             return;
           }
           const float* pre = (const float*)ar[i == 0 ? A::EP1 : A::EP2].p;
-          r.run((p + ".dwups").c_str(), dw3x3_ups_kernel_name(2 * hw, 2 * hw, b0.cexp()), 2.0 * 9 * m * b0.cexp(),
+          r.run((p + ".dwups").c_str(), 2.0 * 9 * m * b0.cexp(),
                 4.0 * ((double)m * b0.cexp() * 2 + (double)m / 4 * b0.cexp()), [&] {
             return launch_dw3x3_ups(pre, (const float*)ar[A::UG].p, b0.cexp(), e.W(p + ".dw.w"), e.W(p + ".dw.b"), (float*)E2.p, B,
                                     2 * hw, 2 * hw, b0.cexp(), r.s);
@@ -811,8 +841,7 @@ struct Plan {
         const double m = (double)B * 4 * hw * hw;
         gemm(p + ".pw1a", lo, c, p + ".pw1a.w", ar[A::UG], b0.cexp(), (long long)B * hw * hw, b0.cexp(), c, GemmEpilogue(), "-",
              2.0 * B * hw * hw * (double)c * b0.cexp());
-        r.run((p + ".upfused").c_str(), ir_fused_upg_kernel_name(b0.cin, b0.cout),
-              2.0 * m * (c * b0.cexp() + 9.0 * b0.cexp() + b0.cexp() * b0.cout),
+        r.run((p + ".upfused").c_str(), 2.0 * m * (c * b0.cexp() + 9.0 * b0.cexp() + b0.cexp() * b0.cout),
               4.0 * (m / 4 * b0.cexp() + m * c + m * b0.cout), [&] {
                 return launch_ir_fused_upg((const float*)ar[A::UG].p, b0.cexp(), (const float*)(cat[i] + c).p, cc,
                                            e.W(p + ".pw1b.w"), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"),
@@ -823,8 +852,7 @@ struct Plan {
         // bilinear x2 folded into the fused block's input load: up(x) is never materialised
         const std::string p = b0.prefix;
         const double m = (double)B * 4 * hw * hw;
-        r.run((p + ".upfused").c_str(), ir_fused_kernel_name(b0.cin, b0.cout, 1, dt(), true, 2 * hw, 2 * hw),
-              2.0 * m * (b0.cin * b0.cexp() + 9.0 * b0.cexp() + b0.cexp() * b0.cout),
+        r.run((p + ".upfused").c_str(), 2.0 * m * (b0.cin * b0.cexp() + 9.0 * b0.cexp() + b0.cexp() * b0.cout),
               dtype_size(dt()) * (m / 4 * c + m * c + m * b0.cout), [&] {
                 return launch_ir_fused_up(lo, c, c, cat[i], cc, e.WG(p + ".pw1.w"), e.W(p + ".pw1.b"),
                                           e.W(p + ".dw.w"), e.W(p + ".dw.b"), e.WG(p + ".pw2.w"),
@@ -832,7 +860,7 @@ struct Plan {
                                           dt());
               });
       } else {
-        r.run(("up" + std::to_string(i + 1) + ".bilinear").c_str(), kname("upsample2x_kernel").c_str(), 0,
+        r.run(("up" + std::to_string(i + 1) + ".bilinear").c_str(), 0,
               dtype_size(dt()) * (double)B * hw * hw * c * 5, [&] {
           return launch_upsample2x(lo, cat[i], cc, B, hw, hw, c, r.s, dt());
         });
@@ -844,7 +872,7 @@ struct Plan {
       c = kUp[i][1].cout;
     }
     // ---------------- head (module/unet.py:342-344)
-    r.run("outc", kname("outc_kernel").c_str(), 2.0 * B * 25600 * 96, (double)B * 25600 * (32 * dtype_size(dt()) + 12), [&] {
+    r.run("outc", 2.0 * B * 25600 * 96, (double)B * 25600 * (32 * dtype_size(dt()) + 12), [&] {
       return launch_outc(ar[A::U4], 32, e.W("outc.w"), e.W("outc.b"), out, B, r.s, dt());
     });
   }
@@ -1030,8 +1058,7 @@ static int refresh_bf16_weights(casync_handle h, int64_t n) {
   CASYNC_CHECK_HIP(guard.err);
   if (!h->w16) CASYNC_CHECK_HIP(hipMalloc((void**)&h->w16, n * sizeof(bf16_t)));
   const long long blocks = (n / 4 + 255) / 256;   // packed total is a multiple of 64 floats
-  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, h->w, h->w16, (long long)n);
-  CASYNC_CHECK_HIP(hipGetLastError());
+  if (int st = casync_launch(f32_to_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, h->w, h->w16, (long long)n)) return st;
   CASYNC_CHECK_HIP(hipDeviceSynchronize());   // one-time, at weight load (not on the forward path)
   return CASYNC_OK;
 }

@@ -349,11 +349,10 @@ int casync_frame_prepare(const uint8_t* regions_dev, const int32_t* geom_dev, in
                          float* x_dev, casync_stream stream) {
   CASYNC_REQUIRE(regions_dev && geom_dev && crops168_dev && batch > 0 && batch <= 65535, "frame_prepare: bad args");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(frame_resize168_kernel, dim3(blocks_for(168 * 168), batch), dim3(256), 0, s, regions_dev, geom_dev,
-                     crops168_dev);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  if (x_dev) return launch_crop_to_input(crops168_dev, x_dev, batch, s);
-  return CASYNC_OK;
+  const int st = casync_launch(frame_resize168_kernel, dim3(blocks_for(168 * 168), batch), dim3(256), 0, s, regions_dev, geom_dev,
+                               crops168_dev);
+  if (st || !x_dev) return st;
+  return launch_crop_to_input(crops168_dev, x_dev, batch, s);
 }
 
 int casync_frame_paste_back(const uint8_t* regions_dev, const int32_t* geom_dev, const int32_t* pts_dev,
@@ -370,20 +369,20 @@ int casync_frame_paste_back(const uint8_t* regions_dev, const int32_t* geom_dev,
   const long long max_px = (long long)max_h * max_w;
   CASYNC_CHECK_HIP(hipMemsetAsync(mask_a_dev, 0, (size_t)mask_bytes, s));
   CASYNC_CHECK_HIP(hipMemsetAsync(area_dev, 0, (size_t)batch * sizeof(int32_t), s));
+  int st = CASYNC_OK;
   if (max_width > 0)
-    hipLaunchKernelGGL(frame_synth_kernel, dim3(blocks_for((long long)max_width * max_width), batch), dim3(256), 0, s,
+    st = casync_launch(frame_synth_kernel, dim3(blocks_for((long long)max_width * max_width), batch), dim3(256), 0, s,
                        crops168_dev, pred_dev, geom_dev, synth_dev);
-  hipLaunchKernelGGL(frame_polyfill_kernel, dim3(max_h, batch), dim3(64), 0, s, geom_dev, pts_dev, mask_a_dev);
-  hipLaunchKernelGGL(frame_polylines_kernel, dim3(batch), dim3(64), 0, s, geom_dev, pts_dev, mask_a_dev);
-  hipLaunchKernelGGL(frame_area_kernel, dim3(64, batch), dim3(256), 0, s, geom_dev, mask_a_dev, area_dev);
-  hipLaunchKernelGGL(frame_dilate_kernel<true>, dim3(blocks_for(max_px), batch), dim3(256), 0, s, geom_dev, area_dev,
-                     mask_a_dev, mask_b_dev);
-  hipLaunchKernelGGL(frame_dilate_kernel<false>, dim3(blocks_for(max_px), batch), dim3(256), 0, s, geom_dev, area_dev,
-                     mask_b_dev, mask_a_dev);
-  hipLaunchKernelGGL(frame_blend_kernel, dim3(blocks_for(max_px), batch), dim3(256), 0, s, regions_dev, geom_dev, synth_dev,
-                     mask_a_dev, out_regions_dev);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  if (!st) st = casync_launch(frame_polyfill_kernel, dim3(max_h, batch), dim3(64), 0, s, geom_dev, pts_dev, mask_a_dev);
+  if (!st) st = casync_launch(frame_polylines_kernel, dim3(batch), dim3(64), 0, s, geom_dev, pts_dev, mask_a_dev);
+  if (!st) st = casync_launch(frame_area_kernel, dim3(64, batch), dim3(256), 0, s, geom_dev, mask_a_dev, area_dev);
+  if (!st) st = casync_launch(frame_dilate_kernel<true>, dim3(blocks_for(max_px), batch), dim3(256), 0, s, geom_dev, area_dev,
+                              mask_a_dev, mask_b_dev);
+  if (!st) st = casync_launch(frame_dilate_kernel<false>, dim3(blocks_for(max_px), batch), dim3(256), 0, s, geom_dev, area_dev,
+                              mask_b_dev, mask_a_dev);
+  if (!st) st = casync_launch(frame_blend_kernel, dim3(blocks_for(max_px), batch), dim3(256), 0, s, regions_dev, geom_dev, synth_dev,
+                              mask_a_dev, out_regions_dev);
+  return st;
 }
 
 }  // extern "C"

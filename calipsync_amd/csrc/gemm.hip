@@ -889,10 +889,8 @@ int launch_glds_t(const T* a, int lda, const T* w, T* c, int ldc, int m, int n, 
     e2.buf_a_bytes = (unsigned)ab;
     e2.buf_w_bytes = (unsigned)wb;
   }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a, lda, w, c, ldc, m, n, k, n_ntiles,
-                     (int)nwg, (int)sk.dp_tiles, sk.wgs, sk.per, e2);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  return casync_launch(kern, dim3(grid), dim3(256), lds, stream, a, lda, w, c, ldc, m, n, k, n_ntiles,
+                       (int)nwg, (int)sk.dp_tiles, sk.wgs, sk.per, e2);
 }
 
 
@@ -911,49 +909,62 @@ int launch_cfg_t(const T* a, int lda, const T* w, T* c, int ldc, int m, int n, i
   constexpr int per_cu = (int)(160 * 1024 / lds) < 8 ? (int)(160 * 1024 / lds) : 8;
   const long long cap = 256ll * (per_cu < 1 ? 1 : per_cu);
   const unsigned grid = (unsigned)(persist && nwg > cap ? cap : nwg);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WM * WN), lds, stream, a, lda, w, c, ldc, m, n, k,
-                     n_ntiles, (int)nwg, epi);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  return casync_launch(kern, dim3(grid), dim3(64 * WM * WN), lds, stream, a, lda, w, c, ldc, m, n, k,
+                       n_ntiles, (int)nwg, epi);
 }
 
 // 0 = register-staged kernel only, 1 = LDS-DMA ring for bf16, 2 = for both types (default)
 inline int glds_mode() { return casync_opts().gemm_glds; }
 
-template <int BM, int BN, int WM, int WN>
+// tile configurations of the GEMM (pick_cfg chooses one per launch)
+enum Cfg { C128x128 = 0, C128x64, C64x64, C128x32, C64x32, CFG_COUNT };
+
+struct TileCfg { Cfg id; int bm, bn; };
+constexpr TileCfg kTiles[] = {{C128x128, 128, 128}, {C128x64, 128, 64}, {C64x64, 64, 64}, {C128x32, 128, 32}, {C64x32, 64, 32}};
+
+// A and W within the 32-bit byte offsets of the ring kernels' buffer-addressed loads
+bool fits32(int m, int n, int k, int lda, int dtype) {
+  const size_t esz = dtype_size(dtype);
+  return ((size_t)(m - 1) * lda + k) * esz < (1ull << 31) && (size_t)n * k * esz < (1ull << 31);
+}
+
+// Does this launch run on the LDS-DMA ring kernel?  launch_cfg() launches it and pick_cfg() prices stream-K for it (the
+// register-staged kernel cannot split K).  The 128x128 ring leaves room for one workgroup per CU only: it is used when the
+// launch has at most one tile per CU anyway (then its deeper pipeline wins), else the register-staged kernel with two
+// co-resident workgroups.  The smaller tiles always take the ring, as long as A and W fit its 32-bit offsets.
+bool takes_ring(const TileCfg& t, int m, int n, int k, int lda, int dtype) {
+  if (!fits32(m, n, k, lda, dtype)) return false;
+  if (t.id == C64x32) return dtype == DT_F32 && glds_mode() >= 2;   // fp32 only (see pick_cfg)
+  const long long tiles = (long long)((m + t.bm - 1) / t.bm) * (n / t.bn);
+  return (t.id == C128x128 || t.id == C128x64 || t.id == C64x64) && (t.bm + t.bn < 256 || tiles <= 256) &&
+         ((dtype == DT_BF16 && glds_mode() >= 1) || (dtype == DT_F32 && glds_mode() >= 2));
+}
+
+template <Cfg ID, int WM, int WN>
 int launch_cfg(const void* a, int lda, const void* w, void* c, int ldc, int m, int n, int k,
                const GemmEpilogue& epi, hipStream_t stream, int dtype, bool use_sk) {
-
+  constexpr int BM = kTiles[ID].bm, BN = kTiles[ID].bn;
   // ring depth: 128x128 -> 3 stages (96 KB, one workgroup per CU), 128x64 -> 2 stages (48 KB, three
   // per CU), 64x64 -> 2 stages (32 KB, five per CU).  Measured every time: one more co-resident
   // workgroup beats one more stage of prefetch (128x64: +1.5 % fp32, +3.6 % bf16 end to end;
   // 64x64 two stages vs three: +0.8 % at B=64, +1.6 % at B=32 in the two-lane schedule).
   constexpr int NST2 = (BM + BN) >= 256 ? 3 : 2;
-  // The 128x128 ring leaves room for one workgroup per CU only: use it when the launch has at most
-  // one tile per CU anyway (then its deeper pipeline wins), else the register-staged kernel with
-  // two co-resident workgroups.  The smaller tiles always take the ring.
-  const long long tiles = (long long)((m + BM - 1) / BM) * (n / BN);
-  const size_t esz = dtype == DT_BF16 ? 2 : 4;
-  const bool fits32 = ((size_t)(m - 1) * lda + k) * esz < (1ull << 31) && (size_t)n * k * esz < (1ull << 31);
-  const bool ring_ok = fits32 && ((BM + BN) < 256 || tiles <= 256);
-  if constexpr (BM == 128 && BN == 128) {
+  if constexpr (ID == C128x128) {
     // round-6 experiment (`gemm_ring128`): the 128x128 bf16 tile on a TWO-stage ring, two workgroups per CU
     // (64 KB each), for the multi-round launches the register-staged kernel serves -- the configuration missing from
     // profiles/r5_bf16_gemm_variants.txt (the ring has no ds_write, which that table priced at 15-35 % of the staged kernel)
-    if (fits32 && dtype == DT_BF16 && glds_mode() >= 1 && casync_opts().gemm_ring128 && tiles > 256)
+    const long long tiles = (long long)((m + BM - 1) / BM) * (n / BN);
+    if (fits32(m, n, k, lda, dtype) && dtype == DT_BF16 && glds_mode() >= 1 && casync_opts().gemm_ring128 && tiles > 256)
       return launch_glds_t<bf16_t, 128, 128, WM, WN, 2>(static_cast<const bf16_t*>(a), lda, static_cast<const bf16_t*>(w),
                                                         static_cast<bf16_t*>(c), ldc, m, n, k, epi, stream, use_sk);
   }
   if constexpr (WM * WN == 4 && BN >= 64) {
-    if (ring_ok && dtype == DT_BF16 && glds_mode() >= 1) {
-      return launch_glds_t<bf16_t, BM, BN, WM, WN, NST2>(static_cast<const bf16_t*>(a), lda, static_cast<const bf16_t*>(w),
-                                                         static_cast<bf16_t*>(c), ldc, m, n, k, epi, stream, use_sk);
-    }
-    if (ring_ok && dtype == DT_F32 && glds_mode() >= 2) {
-      const float* af = static_cast<const float*>(a);
-      const float* wf = static_cast<const float*>(w);
-      float* cf = static_cast<float*>(c);
-      return launch_glds_t<float, BM, BN, WM, WN, NST2>(af, lda, wf, cf, ldc, m, n, k, epi, stream, use_sk);
+    if (takes_ring(kTiles[ID], m, n, k, lda, dtype)) {
+      if (dtype == DT_BF16)
+        return launch_glds_t<bf16_t, BM, BN, WM, WN, NST2>(static_cast<const bf16_t*>(a), lda, static_cast<const bf16_t*>(w),
+                                                           static_cast<bf16_t*>(c), ldc, m, n, k, epi, stream, use_sk);
+      return launch_glds_t<float, BM, BN, WM, WN, NST2>(static_cast<const float*>(a), lda, static_cast<const float*>(w),
+                                                        static_cast<float*>(c), ldc, m, n, k, epi, stream, use_sk);
     }
   }
   if (dtype == DT_BF16)
@@ -966,27 +977,14 @@ int launch_cfg(const void* a, int lda, const void* w, void* c, int ldc, int m, i
 // Tile choice.  On a 256-CU chip a launch of G workgroups finishes after ceil(G/256) "rounds" of
 // one tile per CU (co-resident tiles share the CU's matrix pipes, so they add, not overlap);
 // pick the tile that minimises rounds x tile area, preferring the larger tile on ties.
-enum Cfg { C128x128 = 0, C128x64, C64x64, C128x32, C64x32, CFG_COUNT };
-
-struct TileCfg { Cfg id; int bm, bn; };
-constexpr TileCfg kTiles[] = {{C128x128, 128, 128}, {C128x64, 128, 64}, {C64x64, 64, 64}, {C128x32, 128, 32}, {C64x32, 64, 32}};
-
-// does launch_cfg() send this config to the LDS-DMA ring kernel?
-bool takes_ring(const TileCfg& t, long long tiles, int dtype) {
-  if (t.id == C64x32) return dtype == DT_F32 && glds_mode() >= 2;   // fp32 only (see pick_cfg)
-  return (t.id == C128x128 || t.id == C128x64 || t.id == C64x64) &&
-         (t.bm + t.bn < 256 || tiles <= 256) &&
-         ((dtype == DT_BF16 && glds_mode() >= 1) || (dtype == DT_F32 && glds_mode() >= 2));
-}
-
-int pick_cfg(int m, int n, int k, bool stream_k, int dtype, bool* use_sk = nullptr, bool concurrent = false, bool small_m_ok = true) {
+int pick_cfg(int m, int n, int k, int lda, bool stream_k, int dtype, bool* use_sk = nullptr, bool concurrent = false, bool small_m_ok = true) {
   const int forced = casync_opts().gemm_cfg;
   const int nk = k / (ROWB / dtype_size(dtype));
   if (use_sk) *use_sk = false;
   if (forced >= 0 && forced < CFG_COUNT && n % kTiles[forced].bn == 0 && (forced != C64x32 || dtype == DT_F32)) {
     const TileCfg& t = kTiles[forced];
     const long long g = (long long)((m + t.bm - 1) / t.bm) * (n / t.bn);
-    if (use_sk) *use_sk = takes_ring(t, g, dtype) && stream_k_split(g, nk, t.bm * t.bn, stream_k).wgs > 0;
+    if (use_sk) *use_sk = takes_ring(t, m, n, k, lda, dtype) && stream_k_split(g, nk, t.bm * t.bn, stream_k).wgs > 0;
     return forced;
   }
   // Cost model fitted to tools/experiments/streamk_sweep.sh: a launch costs a fixed ~17 us (not
@@ -1029,7 +1027,7 @@ int pick_cfg(int m, int n, int k, bool stream_k, int dtype, bool* use_sk = nullp
     const double per_round = nk * (t.bm * t.bn + (dtype == DT_BF16 ? 6000.0 : 600.0)) / 8192.0;
     double cost = (double)((g + 255) / 256) * per_round;
     bool sk_better = false;
-    if (takes_ring(t, g, dtype) && stream_k_split(g, nk, t.bm * t.bn, stream_k).wgs) {
+    if (takes_ring(t, m, n, k, lda, dtype) && stream_k_split(g, nk, t.bm * t.bn, stream_k).wgs) {
       const double sk_cost = (double)g / 256.0 * per_round + 2.5 + 9.5 * (t.bm * t.bn) / 8192.0;
       if (sk_cost < cost) cost = sk_cost, sk_better = true;
     }
@@ -1042,33 +1040,6 @@ int pick_cfg(int m, int n, int k, bool stream_k, int dtype, bool* use_sk = nullp
 }
 
 }  // namespace
-
-// Name of the kernel instance launch_pw_gemm() will pick (as rocprofv3 prints it).
-const char* pw_gemm_kernel_name(int m, int n, int k, bool stream_k, int dtype, bool concurrent, bool ups) {
-  static thread_local char buf[64];
-  if (ups) return "pw_gemm_ups_kernel<float, 64, 64, 2, 2, 2>";
-  const char* t = dtype == DT_BF16 ? "__bf16" : "float";
-  const int id = pick_cfg(m, n, k, stream_k, dtype, nullptr, concurrent);
-  const char* cfg;
-  switch (id) {
-    case C128x128: cfg = "128, 128, 2, 2"; break;
-    case C128x64: cfg = "128, 64, 2, 2"; break;
-    case C64x64: cfg = "64, 64, 2, 2"; break;
-    case C64x32: cfg = "64, 32, 2, 1"; break;   // four stages, see the snprintf below
-    default: cfg = "128, 32, 4, 1"; break;
-  }
-  const TileCfg& tc = kTiles[id];
-  const long long tiles = (long long)((m + tc.bm - 1) / tc.bm) * (n / tc.bn);
-  const size_t esz = dtype_size(dtype);
-  if (id == C128x128 && dtype == DT_BF16 && glds_mode() >= 1 && casync_opts().gemm_ring128 && tiles > 256 &&
-      (size_t)m * k * esz < (1ull << 31) && (size_t)n * k * esz < (1ull << 31))
-    snprintf(buf, sizeof(buf), "pw_gemm_glds_kernel<__bf16, 128, 128, 2, 2, 2, false>");
-  else if (takes_ring(tc, tiles, dtype))
-    snprintf(buf, sizeof(buf), "pw_gemm_glds_kernel<%s, %s, %d, false>", t, cfg, id == C64x32 ? 4 : (tc.bm + tc.bn >= 256 ? 3 : 2));
-  else
-    snprintf(buf, sizeof(buf), "pw_gemm_kernel<%s, %s>", t, cfg);
-  return buf;
-}
 
 int launch_pw_gemm(const void* a, int lda, const void* w, void* c, int ldc, int m, int n, int k,
                    const GemmEpilogue& epi, hipStream_t stream, int dtype) {
@@ -1098,18 +1069,17 @@ int launch_pw_gemm(const void* a, int lda, const void* w, void* c, int ldc, int 
     return launch_glds_t<float, 64, 64, 2, 2, 2, false, true>(static_cast<const float*>(a), lda, static_cast<const float*>(w),
                                                               static_cast<float*>(c), ldc, m, n, k, epi, stream, false);
   }
-  switch (pick_cfg(m, n, k, epi.sk_ws != nullptr, dtype, &sk, epi.concurrent != 0)) {
-    case C128x128: return launch_cfg<128, 128, 2, 2>(a, lda, w, c, ldc, m, n, k, epi, stream, dtype, sk);
-    case C128x64: return launch_cfg<128, 64, 2, 2>(a, lda, w, c, ldc, m, n, k, epi, stream, dtype, sk);
-    case C64x64: return launch_cfg<64, 64, 2, 2>(a, lda, w, c, ldc, m, n, k, epi, stream, dtype, sk);
-    case C64x32: {
-      const bool fits32 = ((size_t)(m - 1) * lda + k) * 4 < (1ull << 31) && (size_t)n * k * 4 < (1ull << 31);
+  switch (pick_cfg(m, n, k, lda, epi.sk_ws != nullptr, dtype, &sk, epi.concurrent != 0)) {
+    case C128x128: return launch_cfg<C128x128, 2, 2>(a, lda, w, c, ldc, m, n, k, epi, stream, dtype, sk);
+    case C128x64: return launch_cfg<C128x64, 2, 2>(a, lda, w, c, ldc, m, n, k, epi, stream, dtype, sk);
+    case C64x64: return launch_cfg<C64x64, 2, 2>(a, lda, w, c, ldc, m, n, k, epi, stream, dtype, sk);
+    case C64x32:
       CASYNC_REQUIRE(dtype == DT_F32, "pw_gemm: the 64x32 tile is fp32 only");
-      if (!fits32) return launch_cfg<128, 32, 4, 1>(a, lda, w, c, ldc, m, n, k, epi, stream, dtype, false);   // pointer-addressed kernel
+      if (!fits32(m, n, k, lda, dtype))   // pointer-addressed kernel
+        return launch_cfg<C128x32, 4, 1>(a, lda, w, c, ldc, m, n, k, epi, stream, dtype, false);
       return launch_glds_t<float, 64, 32, 2, 1, 4>(static_cast<const float*>(a), lda, static_cast<const float*>(w),
                                                    static_cast<float*>(c), ldc, m, n, k, epi, stream, false);
-    }
-    default: return launch_cfg<128, 32, 4, 1>(a, lda, w, c, ldc, m, n, k, epi, stream, dtype, sk);
+    default: return launch_cfg<C128x32, 4, 1>(a, lda, w, c, ldc, m, n, k, epi, stream, dtype, sk);
   }
 }
 
@@ -1119,25 +1089,13 @@ template <typename T>
 int launch_conv_t(const T* in, const T* w, T* out, int ldc, int m, int n, int k, const GemmEpilogue& epi,
                   hipStream_t stream, int dtype) {
   bool sk = false;
-  const int cfg = pick_cfg(m, n, k, epi.sk_ws != nullptr, dtype, &sk, epi.concurrent != 0, false);
   // the ring kernel's two 48-KB-class tiles; the A "leading dimension" is unused (rows are gathered)
+  const int cfg = pick_cfg(m, n, k, 0, epi.sk_ws != nullptr, dtype, &sk, epi.concurrent != 0, false);
   const bool small = cfg == C64x64 || cfg == C64x32 || n % 64 || m <= 4096;
   return small ? launch_glds_t<T, 64, 64, 2, 2, 2, true>(in, 0, w, out, ldc, m, n, k, epi, stream, sk && cfg == C64x64)
                : launch_glds_t<T, 128, 64, 2, 2, 2, true>(in, 0, w, out, ldc, m, n, k, epi, stream, sk && cfg == C128x64);
 }
 }  // namespace
-
-const char* conv3x3_gemm_kernel_name(int batch, int h, int wdt, int cin, int cout, int stride_h, int stride_w, int pad, int dtype,
-                                     bool concurrent, bool stream_k) {
-  static thread_local char buf[64];
-  const int ho = (h + 2 * pad - 3) / stride_h + 1, wo = (wdt + 2 * pad - 3) / stride_w + 1;
-  const int m = batch * ho * wo;
-  const int cfg = pick_cfg(m, cout, 9 * cin, stream_k, dtype, nullptr, concurrent, false);   // the launch's own choice
-  const bool small = cfg == C64x64 || cfg == C64x32 || cout % 64 || m <= 4096;
-  snprintf(buf, sizeof(buf), "pw_gemm_glds_kernel<%s, %s, 2, 2, %d, true>", dtype == DT_BF16 ? "__bf16" : "float",
-             small ? "64, 64" : "128, 64", 2);
-  return buf;
-}
 
 int launch_conv3x3_gemm(const void* in, const void* w, void* out, int ldc, int batch, int h, int wdt, int cin,
                         int cout, int stride_h, int stride_w, int pad, const GemmEpilogue& epi_in, hipStream_t stream, int dtype) {

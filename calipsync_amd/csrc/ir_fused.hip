@@ -1070,10 +1070,8 @@ int launch_inst_b(const bf16_t* lo, int ld_lo, int c_lo, const bf16_t* in, int l
   if (int st = casync_ensure_dyn_lds(&attr_once, reinterpret_cast<const void*>(kern), (int)lds)) return st;
   const int ho = (h + 2 - 3) / STRIDE + 1, wo = (w + 2 - 3) / STRIDE + 1;
   dim3 grid((unsigned)(((wo + TW - 1) / TW) * ((ho + G::TH - 1) / G::TH) * batch));   // one dimension: the kernel orders the tiles by XCD
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, lo, ld_lo, c_lo, in, ld_in, w1, b1, wd, bd, w2, b2,
-                     out, ld_out, h, w, ho, wo, res);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  return casync_launch(kern, grid, dim3(256), lds, stream, lo, ld_lo, c_lo, in, ld_in, w1, b1, wd, bd, w2, b2,
+                       out, ld_out, h, w, ho, wo, res);
 }
 
 template <typename T, int CIN, int CE, int COUT, int STRIDE, int CC, int UPS>
@@ -1087,10 +1085,8 @@ int launch_inst_t(const T* lo, int ld_lo, int c_lo, const T* in, int ld_in, cons
   if (int st = casync_ensure_dyn_lds(&attr_once, reinterpret_cast<const void*>(kern), (int)lds)) return st;
   const int ho = (h + 2 - 3) / STRIDE + 1, wo = (w + 2 - 3) / STRIDE + 1;
   dim3 grid((unsigned)(((wo + TW - 1) / TW) * ((ho + G::TH - 1) / G::TH) * batch));   // one dimension: the kernel orders the tiles by XCD
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, lo, ld_lo, c_lo, in, ld_in, w1, b1, wd, bd, w2,
-                     b2, out, ld_out, h, w, ho, wo, res, g_ir_stamps);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  return casync_launch(kern, grid, dim3(256), lds, stream, lo, ld_lo, c_lo, in, ld_in, w1, b1, wd, bd, w2,
+                       b2, out, ld_out, h, w, ho, wo, res, g_ir_stamps);
 }
 
 // `ir_dw_mfma`: 1 = the depthwise phase of the bf16 kernel on the matrix pipe where that measured faster -- every instance
@@ -1179,22 +1175,6 @@ int launch_ir_fused_upg(const float* g, int ld_g, const float* in, int ld_in, co
     return launch_inst_t<float, 64, 256, 32, 1, 16, 2>(g, ld_g, 0, in, ld_in, w1, b1, wd, bd, w2, b2, out, ld_out, batch, h, w, 0, stream);
   casync_set_error("ir_fused_upg: no instance for cin=%d cout=%d", cin, cout);
   return CASYNC_ERR_ARG;
-}
-
-const char* ir_fused_upg_kernel_name(int cin, int cout) {
-  static thread_local char buf[64];
-  snprintf(buf, sizeof(buf), "ir_fused_kernel<float, %d, %d, %d, 1, 16, 2>", cin / 2, 2 * cin, cout);
-  return buf;
-}
-
-const char* ir_fused_kernel_name(int cin, int cout, int stride, int dtype, bool ups, int h, int w) {
-  static thread_local char buf[64];
-  if (dtype == DT_BF16)
-    snprintf(buf, sizeof(buf), "ir_fused_bf16_kernel<%d, %d, %d, %d, %s, %s>", cin, 2 * cin, cout, stride, ups ? "true" : "false",
-             ir_dw_mfma_on(cin, cout) ? "true" : "false");
-  else
-    snprintf(buf, sizeof(buf), "ir_fused_kernel<float, %d, %d, %d, %d, 16, %d>", cin, 2 * cin, cout, stride, ups ? 1 : 0);
-  return buf;
 }
 
 int launch_ir_fused(const void* in, int ld_in, const void* w1, const float* b1, const float* wd,

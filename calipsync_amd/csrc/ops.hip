@@ -619,13 +619,6 @@ static bool dw_lds_plan(int h, int wdt, int c, int stride, int dtype, int* csv, 
 }
 
 // depthwise 3x3 over LReLU(pre + up(g)) (dw3x3_ups_lds_kernel): fp32, stride 1, frames the slab plan takes
-const char* dw3x3_ups_kernel_name(int h, int wdt, int c) {
-  static thread_local char buf[64];
-  int csv = 8, th, nt;
-  dw_lds_plan(h, wdt, c, 1, DT_F32, &csv, &th, &nt);
-  snprintf(buf, sizeof(buf), "dw3x3_ups_lds_kernel<%d>", csv);
-  return buf;
-}
 int launch_dw3x3_ups(const float* pre, const float* g, int ldg, const float* w, const float* bias, float* out, int batch, int h,
                      int wdt, int c, hipStream_t stream) {
   CASYNC_REQUIRE(pre && g && w && bias && out, "dw3x3_ups: null pointer");
@@ -635,21 +628,8 @@ int launch_dw3x3_ups(const float* pre, const float* g, int ldg, const float* w, 
   CASYNC_REQUIRE(dw_lds_plan(h, wdt, c, 1, DT_F32, &csv, &th, &nt), "dw3x3_ups: %dx%dx%d does not fit the slab kernel", h, wdt, c);
   const size_t lds = (size_t)(th + 2) * (wdt + 2) * csv * 16;
   const dim3 grid(c / 4 / csv, nt, batch);
-  if (csv == 16) hipLaunchKernelGGL(dw3x3_ups_lds_kernel<16>, grid, dim3(256), lds, stream, pre, g, ldg, w, bias, out, h, wdt, c, th);
-  else hipLaunchKernelGGL(dw3x3_ups_lds_kernel<8>, grid, dim3(256), lds, stream, pre, g, ldg, w, bias, out, h, wdt, c, th);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
-}
-
-const char* dw3x3_kernel_name(int h, int wdt, int c, int stride, int dtype) {
-  static thread_local char buf[64];
-  const char* t = dtype == DT_BF16 ? "__bf16" : "float";
-  int csv, th, nt;
-  if (dw_lds_plan(h, wdt, c, stride, dtype, &csv, &th, &nt))
-    snprintf(buf, sizeof(buf), "dw3x3_lds_kernel<%s, %d>", t, csv);
-  else
-    snprintf(buf, sizeof(buf), "dw3x3_kernel<%s, %s>", t, stride == 1 ? "1, 4" : "2, 2");
-  return buf;
+  return casync_launch(csv == 16 ? dw3x3_ups_lds_kernel<16> : dw3x3_ups_lds_kernel<8>, grid, dim3(256), lds, stream, pre, g, ldg, w,
+                       bias, out, h, wdt, c, th);
 }
 
 int launch_dw3x3(const void* in, const float* w, const float* bias, void* out, int batch, int h,
@@ -664,14 +644,11 @@ int launch_dw3x3(const void* in, const float* w, const float* bias, void* out, i
     if (dw_lds_plan(h, wdt, c, stride, dtype, &csv, &th, &nt)) {
       const size_t lds = (size_t)(th + 2) * (wdt + 2) * csv * 16;
       const dim3 grid(c / vec / csv, nt, batch);
-#define CASYNC_DW_LDS_LAUNCH(TT, CSVV)                                                                      \
-  hipLaunchKernelGGL((dw3x3_lds_kernel<TT, CSVV>), grid, dim3(256), lds, stream, (const TT*)in, w, bias, \
-                     (TT*)out, h, wdt, c, th)
-      if (csv == 16) DT_DISPATCH(dtype, CASYNC_DW_LDS_LAUNCH(float, 16), CASYNC_DW_LDS_LAUNCH(bf16_t, 16));
-      else DT_DISPATCH(dtype, CASYNC_DW_LDS_LAUNCH(float, 8), CASYNC_DW_LDS_LAUNCH(bf16_t, 8));
-#undef CASYNC_DW_LDS_LAUNCH
-      CASYNC_CHECK_HIP(hipGetLastError());
-      return CASYNC_OK;
+      DT_DISPATCH(dtype,
+                  return casync_launch(csv == 16 ? dw3x3_lds_kernel<float, 16> : dw3x3_lds_kernel<float, 8>, grid, dim3(256), lds,
+                                       stream, (const float*)in, w, bias, (float*)out, h, wdt, c, th),
+                  return casync_launch(csv == 16 ? dw3x3_lds_kernel<bf16_t, 16> : dw3x3_lds_kernel<bf16_t, 8>, grid, dim3(256), lds,
+                                       stream, (const bf16_t*)in, w, bias, (bf16_t*)out, h, wdt, c, th));
     }
   }
   if (stride == 1) {
@@ -679,22 +656,19 @@ int launch_dw3x3(const void* in, const float* w, const float* bias, void* out, i
     const int strips = (wo + PX - 1) / PX;
     const long long total = (long long)batch * ho * strips * (c / vec);
     DT_DISPATCH(dtype,
-                hipLaunchKernelGGL((dw3x3_kernel<float, 1, PX>), dim3(blocks_for(total)), dim3(256), 0, stream,
-                                   (const float*)in, w, bias, (float*)out, h, wdt, c, ho, wo, strips, total),
-                hipLaunchKernelGGL((dw3x3_kernel<bf16_t, 1, PX>), dim3(blocks_for(total)), dim3(256), 0, stream,
-                                   (const bf16_t*)in, w, bias, (bf16_t*)out, h, wdt, c, ho, wo, strips, total));
-  } else {
-    constexpr int PX = 2;
-    const int strips = (wo + PX - 1) / PX;
-    const long long total = (long long)batch * ho * strips * (c / vec);
-    DT_DISPATCH(dtype,
-                hipLaunchKernelGGL((dw3x3_kernel<float, 2, PX>), dim3(blocks_for(total)), dim3(256), 0, stream,
-                                   (const float*)in, w, bias, (float*)out, h, wdt, c, ho, wo, strips, total),
-                hipLaunchKernelGGL((dw3x3_kernel<bf16_t, 2, PX>), dim3(blocks_for(total)), dim3(256), 0, stream,
-                                   (const bf16_t*)in, w, bias, (bf16_t*)out, h, wdt, c, ho, wo, strips, total));
+                return casync_launch(dw3x3_kernel<float, 1, PX>, dim3(blocks_for(total)), dim3(256), 0, stream,
+                                     (const float*)in, w, bias, (float*)out, h, wdt, c, ho, wo, strips, total),
+                return casync_launch(dw3x3_kernel<bf16_t, 1, PX>, dim3(blocks_for(total)), dim3(256), 0, stream,
+                                     (const bf16_t*)in, w, bias, (bf16_t*)out, h, wdt, c, ho, wo, strips, total));
   }
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  constexpr int PX = 2;
+  const int strips = (wo + PX - 1) / PX;
+  const long long total = (long long)batch * ho * strips * (c / vec);
+  DT_DISPATCH(dtype,
+              return casync_launch(dw3x3_kernel<float, 2, PX>, dim3(blocks_for(total)), dim3(256), 0, stream,
+                                   (const float*)in, w, bias, (float*)out, h, wdt, c, ho, wo, strips, total),
+              return casync_launch(dw3x3_kernel<bf16_t, 2, PX>, dim3(blocks_for(total)), dim3(256), 0, stream,
+                                   (const bf16_t*)in, w, bias, (bf16_t*)out, h, wdt, c, ho, wo, strips, total));
 }
 
 int launch_upsample2x(const void* in, void* out, int ldc, int batch, int h, int wdt, int c,
@@ -703,40 +677,32 @@ int launch_upsample2x(const void* in, void* out, int ldc, int batch, int h, int 
                  "upsample2x: bad args");
   const long long total = (long long)batch * 4 * h * wdt * (c / 4);
   DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(upsample2x_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, stream,
-                                 (const float*)in, (float*)out, ldc, h, wdt, c, total),
-              hipLaunchKernelGGL(upsample2x_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, stream,
-                                 (const bf16_t*)in, (bf16_t*)out, ldc, h, wdt, c, total));
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+              return casync_launch(upsample2x_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, stream,
+                                   (const float*)in, (float*)out, ldc, h, wdt, c, total),
+              return casync_launch(upsample2x_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, stream,
+                                   (const bf16_t*)in, (bf16_t*)out, ldc, h, wdt, c, total));
 }
 
 int launch_nchw_to_nhwc(const float* in, void* out, int batch, int c, int hw, hipStream_t stream, int dtype) {
   CASYNC_REQUIRE(in && out && batch > 0 && c % 4 == 0 && hw > 0, "nchw_to_nhwc: bad args");
   const long long total = (long long)batch * (c / 4) * hw;
   DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, stream, in,
-                                 (float*)out, c, hw, total),
-              hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, stream, in,
-                                 (bf16_t*)out, c, hw, total));
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+              return casync_launch(nchw_to_nhwc_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, stream, in,
+                                   (float*)out, c, hw, total),
+              return casync_launch(nchw_to_nhwc_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, stream, in,
+                                   (bf16_t*)out, c, hw, total));
 }
 
 int launch_crop_to_input(const unsigned char* crops, float* x, int batch, hipStream_t stream) {
   CASYNC_REQUIRE(crops && x && batch > 0, "crop_to_input: bad args");
   const long long total = (long long)batch * 25600;
-  hipLaunchKernelGGL(crop_to_input_kernel, dim3(blocks_for(total)), dim3(256), 0, stream, crops, x, total);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  return casync_launch(crop_to_input_kernel, dim3(blocks_for(total)), dim3(256), 0, stream, crops, x, total);
 }
 
 int launch_pred_to_u8(const float* pred, unsigned char* out, int batch, hipStream_t stream) {
   CASYNC_REQUIRE(pred && out && batch > 0, "pred_to_u8: bad args");
   const long long total = (long long)batch * 25600;
-  hipLaunchKernelGGL(pred_to_u8_kernel, dim3(blocks_for(total)), dim3(256), 0, stream, pred, out, total);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  return casync_launch(pred_to_u8_kernel, dim3(blocks_for(total)), dim3(256), 0, stream, pred, out, total);
 }
 
 int launch_audio_window_gather(const float* features, int n_steps, const int* idx_dev, void* out, int batch,
@@ -744,22 +710,18 @@ int launch_audio_window_gather(const float* features, int n_steps, const int* id
   CASYNC_REQUIRE(features && idx_dev && out && batch > 0 && n_steps > 0, "audio_window_gather: bad args");
   const long long total = (long long)batch * 8 * 1024;
   DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(audio_window_gather_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, stream,
-                                 features, n_steps, idx_dev, (float*)out, total),
-              hipLaunchKernelGGL(audio_window_gather_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, stream,
-                                 features, n_steps, idx_dev, (bf16_t*)out, total));
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+              return casync_launch(audio_window_gather_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, stream,
+                                   features, n_steps, idx_dev, (float*)out, total),
+              return casync_launch(audio_window_gather_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, stream,
+                                   features, n_steps, idx_dev, (bf16_t*)out, total));
 }
 
 int launch_audio_windows_nchw(const float* features, int n_steps, const int* idx_dev, float* out, int batch,
                               hipStream_t stream) {
   CASYNC_REQUIRE(features && idx_dev && out && batch > 0 && n_steps > 0, "audio_windows: bad args");
   const long long total = (long long)batch * 8 * 1024;
-  hipLaunchKernelGGL((audio_window_gather_kernel<float, true>), dim3(blocks_for(total)), dim3(256), 0, stream, features,
-                     n_steps, idx_dev, out, total);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  return casync_launch(audio_window_gather_kernel<float, true>, dim3(blocks_for(total)), dim3(256), 0, stream, features,
+                       n_steps, idx_dev, out, total);
 }
 
 int launch_inc(const float* x_nchw, const float* packed_inc, void* out, int ldc, int batch,
@@ -772,15 +734,11 @@ int launch_inc(const float* x_nchw, const float* packed_inc, void* out, int ldc,
   if (dtype == DT_BF16 && casync_opts().inc_mfma) {
     CASYNC_REQUIRE(ldc % 8 == 0 && ((uintptr_t)out % 16) == 0 && (long long)INC_HW * INC_HW * ldc * 2 < (1ll << 31),
                    "inc (bf16): the output rows must be 16-B aligned and a frame smaller than 2 GiB");
-    hipLaunchKernelGGL(inc_bf16_kernel, dim3(nwg), dim3(256), 0, stream, x_nchw, packed_inc, (bf16_t*)out, ldc, nwg);
-    CASYNC_CHECK_HIP(hipGetLastError());
-    return CASYNC_OK;
+    return casync_launch(inc_bf16_kernel, dim3(nwg), dim3(256), 0, stream, x_nchw, packed_inc, (bf16_t*)out, ldc, nwg);
   }
   DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(inc_kernel<float>, dim3(nwg), dim3(256), 0, stream, x_nchw, packed_inc, (float*)out, ldc, nwg),
-              hipLaunchKernelGGL(inc_kernel<bf16_t>, dim3(nwg), dim3(256), 0, stream, x_nchw, packed_inc, (bf16_t*)out, ldc, nwg));
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+              return casync_launch(inc_kernel<float>, dim3(nwg), dim3(256), 0, stream, x_nchw, packed_inc, (float*)out, ldc, nwg),
+              return casync_launch(inc_kernel<bf16_t>, dim3(nwg), dim3(256), 0, stream, x_nchw, packed_inc, (bf16_t*)out, ldc, nwg));
 }
 
 int launch_outc(const void* in, int ld_in, const float* w, const float* b, float* out_nchw,
@@ -789,10 +747,8 @@ int launch_outc(const void* in, int ld_in, const float* w, const float* b, float
                  "outc: bad args");
   const long long blocks = (long long)batch * INC_HW * INC_HW / 256;
   DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(outc_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)in,
-                                 ld_in, w, b, out_nchw),
-              hipLaunchKernelGGL(outc_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, stream,
-                                 (const bf16_t*)in, ld_in, w, b, out_nchw));
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+              return casync_launch(outc_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)in,
+                                   ld_in, w, b, out_nchw),
+              return casync_launch(outc_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, stream,
+                                   (const bf16_t*)in, ld_in, w, b, out_nchw));
 }

@@ -552,10 +552,8 @@ int launch_fs(const float* a, int lda, const float* w1, const float* b1, const f
   CASYNC_REQUIRE(nwg < (1ll << 31) && ab < (1ull << 31) && wb < (1ull << 31), "pw_dw: operand larger than 2 GiB");
   CASYNC_REQUIRE((long long)frames * G::P < (1ll << 24) && (long long)lda * 4 < (1ll << 24),
                  "pw_dw: %lld rows of %d floats exceed the kernel's 24-bit row arithmetic", (long long)frames * G::P, lda);
-  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), G::lds + (ups ? kUpsTileBytes : 0), stream, a, lda, w1, b1, wd, bd, d, ldd, frames, k, n, n_nt,
-                     (int)nwg, (unsigned)ab, (unsigned)wb, ups, ld_ups);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  return casync_launch(kern, dim3((unsigned)nwg), dim3(256), G::lds + (ups ? kUpsTileBytes : 0), stream, a, lda, w1, b1, wd, bd, d, ldd, frames, k, n, n_nt,
+                       (int)nwg, (unsigned)ab, (unsigned)wb, ups, ld_ups);
 }
 
 template <int HW, int F, int BN, int KF, int S, int NST = 2, int WD = HW>
@@ -577,22 +575,14 @@ int launch_ft(const float* a, int lda, const float* w1, const float* b1, const f
   CASYNC_REQUIRE(nwg < (1ll << 31) && ab < (1ull << 31) && wb < (1ull << 31), "pw_dw: operand larger than 2 GiB");
   CASYNC_REQUIRE((long long)frames * G::P < (1ll << 24) && (long long)lda * 4 < (1ll << 24),
                  "pw_dw: %lld rows of %d floats exceed the kernel's 24-bit row arithmetic", (long long)frames * G::P, lda);
-  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), G::lds + (ups ? kUpsTileBytes : 0), stream, a, lda, w1, b1, wd, bd, d, ldd, frames, k, n, n_nt,
-                     (int)nwg, (unsigned)ab, (unsigned)wb, ups, ld_ups);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  return casync_launch(kern, dim3((unsigned)nwg), dim3(256), G::lds + (ups ? kUpsTileBytes : 0), stream, a, lda, w1, b1, wd, bd, d, ldd, frames, k, n, n_nt,
+                       (int)nwg, (unsigned)ab, (unsigned)wb, ups, ld_ups);
 }
 
 }  // namespace
 
 bool pw_dw_rect_supported(int h, int w, int cin, int cexp, int stride) {
   return h == 16 && w == 32 && stride == 1 && cin % 16 == 0 && cexp % 32 == 0;
-}
-
-const char* pw_dw_rect_kernel_name(int h, int w) {
-  static thread_local char buf[64];
-  snprintf(buf, sizeof(buf), "pw_dw_rect_kernel<%d, %d, 32, 16>", h, w);
-  return buf;
 }
 
 int launch_pw_dw_rect(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,
@@ -618,14 +608,6 @@ bool pw_dw_supported(int hw, int cin, int cexp, int stride) {
 // (their k-tiles are 32 input channels wide: cin % 32, or the last 16 channels would be dropped -- ADVICE r5)
 bool pw_dw_deep(int hw, int frames, int stride, bool ups, int cin) {
   return hw <= 16 && stride == 1 && !ups && cin % 32 == 0 && frames >= 2 && frames < casync_opts().fuse_dw_deep;
-}
-
-const char* pw_dw_kernel_name(int hw, int cin, int frames, int stride) {
-  static thread_local char buf[64];
-  if (hw == 40) snprintf(buf, sizeof(buf), "pw_dw_strip_kernel<40, %d, %d, 32, 16>", stride == 1 ? 8 : 4, stride);
-  else if (pw_dw_deep(hw, frames, stride, false, cin)) snprintf(buf, sizeof(buf), "pw_dw_kernel<%d, 1, 32, 32, 1, %d>", hw, hw == 10 ? 4 : 3);
-  else snprintf(buf, sizeof(buf), "pw_dw_kernel<%d, %d, 32, 16, %d, 2>", hw, hw == 10 ? 2 : 1, stride);
-  return buf;
 }
 
 int launch_pw_dw(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,

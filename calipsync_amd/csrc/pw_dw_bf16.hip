@@ -493,10 +493,8 @@ int launch_common(Kern kern, unsigned long long* attr_once, bool ups_ok, long lo
   CASYNC_REQUIRE(nwg < (1ll << 31) && ab < (1ull << 31) && wb < (1ull << 31), "pw_dw (bf16): operand larger than 2 GiB");
   CASYNC_REQUIRE((long long)frames * G::P < (1ll << 24) && (long long)lda * 2 < (1ll << 24),
                  "pw_dw (bf16): %lld rows of %d elements exceed the kernel's 24-bit row arithmetic", (long long)frames * G::P, lda);
-  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), G::lds + (ups ? kUpsTileBytes : 0), stream, a, lda, w1, b1, wd, bd, d, ldd, frames,
-                     k, n, n_nt, (int)nwg, (unsigned)ab, (unsigned)wb, ups, ld_ups);
-  CASYNC_CHECK_HIP(hipGetLastError());
-  return CASYNC_OK;
+  return casync_launch(kern, dim3((unsigned)nwg), dim3(256), G::lds + (ups ? kUpsTileBytes : 0), stream, a, lda, w1, b1, wd, bd, d, ldd, frames,
+                       k, n, n_nt, (int)nwg, (unsigned)ab, (unsigned)wb, ups, ld_ups);
 }
 
 template <int HW, int SR, int STRIDE, int BN>
@@ -536,25 +534,10 @@ bool pw_dw_bf16_supported(int hw, int cin, int cexp, int stride) {
   return (hw == 20 || hw == 40) && (stride == 1 || stride == 2);
 }
 
-const char* pw_dw_bf16_kernel_name(int hw, int cexp, int frames, int stride) {
-  static thread_local char buf[64];
-  (void)frames;
-  if (hw == 40) snprintf(buf, sizeof(buf), "pw_dw_bf16_strip_kernel<40, %d, %d, 64>", stride == 1 ? 8 : 4, stride);
-  else if (hw == 20) snprintf(buf, sizeof(buf), "pw_dw_bf16_kernel<20, 1, 64, %d>", stride);
-  else snprintf(buf, sizeof(buf), "pw_dw_bf16_kernel<%d, %d, %d, 1>", hw, hw == 10 ? 2 : 1, bn_small(cexp));
-  return buf;
-}
-
 bool pw_dw_bf16_takes_ups(int hw, int stride) { return stride == 1 && (hw == 20 || hw == 40); }
 
 bool pw_dw_bf16_rect_supported(int h, int w, int cin, int cexp, int stride) {
   return h == 16 && w == 32 && stride == 1 && cin % 32 == 0 && cexp % 64 == 0;
-}
-
-const char* pw_dw_bf16_rect_kernel_name(int h, int w) {
-  static thread_local char buf[64];
-  snprintf(buf, sizeof(buf), "pw_dw_bf16_rect_kernel<%d, %d, 64>", h, w);
-  return buf;
 }
 
 int launch_pw_dw_bf16_rect(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d, int ldd,

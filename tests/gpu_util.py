@@ -1,9 +1,19 @@
 """Helpers for the -m gpu parity tests: call the C ABI with torch device tensors."""
 import contextlib
+import os
+import sys
 
 import torch
 
 from calipsync_amd import _lib
+
+
+def kernel_table():
+    """tools/kernel_resources.py's table of the built library's kernels, keyed by the short name a profiled row carries
+    (tools/kernel_names.py); None where the LLVM binutils of the ROCm image are missing."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import kernel_resources
+    return kernel_resources.table() if kernel_resources.tools_available() else None
 
 
 def dev():

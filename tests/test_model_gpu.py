@@ -9,7 +9,7 @@ import torch
 from calipsync_amd import recipe
 from calipsync_amd.unet import Model
 from conftest import sample_indices
-from gpu_util import options
+from gpu_util import kernel_table, options
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3          # north-star bar
@@ -326,6 +326,29 @@ def test_bf16_frames_independent(net_bf16):
     assert (full[3:4] - part).abs().max() < 2e-2     # stream-K k-split differs with the row count: bf16 ulps
     with options(net_bf16, gemm_streamk=0):
         assert torch.equal(net_bf16(xt, at)[3:4], net_bf16(xt[3:4].contiguous(), at[3:4].contiguous()))
+
+
+@pytest.mark.parametrize("precision,batch", [("fp32", 1), ("fp32", 8), ("fp32", 64), ("bf16", 8), ("bf16", 256)])
+def test_profile_rows_name_the_kernels_that_ran(request, precision, batch):
+    """Every profiled row is named after the kernel its launch ran: a kernel of the built library, in the short form the
+    kernel table and the rocprofv3 records use.  bf16 B=256 is the large-batch plan (three lanes, the 128x128 ring)."""
+    table = kernel_table()
+    if table is None:
+        pytest.skip("llvm binutils of the ROCm image not found")
+    m = request.getfixturevalue("net" if precision == "fp32" else "net_bf16")
+    x, a = recipe.make_inputs(batch)
+    rows = m.profile(torch.from_numpy(x).cuda(), torch.from_numpy(a).cuda())
+    assert rows
+    assert not [(r["name"], r["kernel"]) for r in rows if r["kernel"] not in table]
+
+
+def test_profile_names_the_split_attention_kernel_in_bf16(net_bf16):
+    """A forced channel split (att_nz) runs the bf16 engine's attention on the fp32-MFMA kernel of attention.hip; the rows say so."""
+    x, a = recipe.make_inputs(8)
+    with options(net_bf16, att_nz=2):
+        rows = net_bf16.profile(torch.from_numpy(x).cuda(), torch.from_numpy(a).cuda())
+    attn = [r["kernel"] for r in rows if r["name"].endswith(".attn")]
+    assert len(attn) == 4 and set(attn) == {"cross_attention_kernel<__bf16>"}, attn
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])

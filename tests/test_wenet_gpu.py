@@ -11,7 +11,7 @@ import torch
 from calipsync_amd import _lib, recipe
 from calipsync_amd.unet import Model, WenetModel
 from conftest import GOLDEN, sample_indices
-from gpu_util import ok, options, ptr, stream
+from gpu_util import kernel_table, ok, options, ptr, stream
 
 import wenet_ref
 
@@ -192,6 +192,8 @@ def test_profile_has_the_wenet_audio_rows(net):
     names = [r["name"] for r in rows]
     assert "audio.conv3" in names and "audio.conv5" in names
     assert not any("bn7" in n for n in names)
+    table = kernel_table()
+    assert table is None or not [(r["name"], r["kernel"]) for r in rows if r["kernel"] not in table]
     for r in rows:
         if r["name"].startswith("audio"):
             print(f"  {r['name']:<40} {r['kernel']:<44} {r['ms'] * 1e3:8.1f} us")

@@ -2,7 +2,9 @@
 
 rocprofv3 demangles the fp32 instances ("void (anonymous namespace)::pw_gemm_glds_kernel<float, 64, ...>(...)")
 but leaves the __bf16 ones mangled (its demangler does not know DF16b), so those are decoded here: the
-template arguments of this engine's kernels are only float / __bf16 / int / bool literals."""
+template arguments of this engine's kernels are only float / __bf16 / int / bool literals.  This is the one short
+form of a kernel name: kernel_resources.py keys its table by it, and the engine's profile rows carry the same form
+(engine.hip, kernel_short_name)."""
 import re
 
 

@@ -18,6 +18,8 @@ import subprocess
 import sys
 import tempfile
 
+from kernel_names import short   # (tools/ is on the path: as the script's own directory or put there by its importers)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OBJ_DIR = os.path.join(ROOT, "calipsync_amd", "lib", "obj")
 LLVM_BIN = "/opt/rocm/lib/llvm/bin"
@@ -26,30 +28,6 @@ TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 
 def tools_available() -> bool:
     return all(os.path.exists(os.path.join(LLVM_BIN, t)) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf"))
-
-
-def demangle(names):
-    try:
-        # binutils' c++filt does not know DF16b (std::bfloat16_t / __bf16): hand it the vendor-type spelling instead
-        out = subprocess.run(["c++filt"], input="\n".join(n.replace("DF16b", "u6__bf16") for n in names), capture_output=True,
-                             text=True, check=True).stdout.split("\n")
-    except (OSError, subprocess.CalledProcessError):
-        return list(names)
-    short = []
-    for d in out[:len(names)]:
-        d = d.replace("(anonymous namespace)::", "")
-        d = re.sub(r"^void ", "", d)
-        depth, cut = 0, len(d)
-        for i, ch in enumerate(d):            # cut the argument list: the first '(' outside the template brackets
-            if ch == "<":
-                depth += 1
-            elif ch == ">":
-                depth -= 1
-            elif ch == "(" and depth == 0:
-                cut = i
-                break
-        short.append(d[:cut])
-    return short
 
 
 def object_kernels(obj_path: str) -> dict:
@@ -85,13 +63,12 @@ def table(obj_dir: str = OBJ_DIR) -> dict:
         if not fn.endswith(".o"):
             continue
         ks = object_kernels(os.path.join(obj_dir, fn))
-        for mangled, short in zip(ks, demangle(list(ks))):
-            k = ks[mangled]
+        for mangled, k in ks.items():
             total = k["vgpr_count"]
-            out[short] = {"object": fn, "vgprs": total, "agprs": k.get("agpr_count", 0),
-                          "scratch": k.get("private_segment_fixed_size", 0),
-                          "static_lds": k.get("group_segment_fixed_size", 0),
-                          "waves": min(8, 512 // max(8, (total + 7) // 8 * 8))}
+            out[short(mangled)] = {"object": fn, "vgprs": total, "agprs": k.get("agpr_count", 0),
+                                   "scratch": k.get("private_segment_fixed_size", 0),
+                                   "static_lds": k.get("group_segment_fixed_size", 0),
+                                   "waves": min(8, 512 // max(8, (total + 7) // 8 * 8))}
     return out
 
 
