@@ -94,10 +94,32 @@ _PROTOS = {
     "casync_op_nchw_to_nhwc": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_inc": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_outc": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_void_p]),
+    # HuBERT feature extractor (ABI 8)
+    "casync_hubert_packed_count": (C.c_int, [C.c_int]),
+    "casync_hubert_packed_name": (C.c_char_p, [C.c_int, C.c_int]),
+    "casync_hubert_packed_offset": (c_i64, [C.c_int, C.c_int]),
+    "casync_hubert_packed_size": (c_i64, [C.c_int, C.c_int]),
+    "casync_hubert_packed_total": (c_i64, [C.c_int]),
+    "casync_hubert_tokens": (c_i64, [c_i64]),
+    "casync_hubert_workspace_bytes": (c_i64, [C.c_int, c_i64]),
+    "casync_hubert_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "casync_hubert_destroy": (None, [C.c_void_p]),
+    "casync_hubert_load_weights_host": (C.c_int, [C.c_void_p, C.c_void_p, c_i64]),
+    "casync_hubert_load_weights_device": (C.c_int, [C.c_void_p, c_f32p, c_i64]),
+    "casync_hubert_forward": (C.c_int, [C.c_void_p, c_f32p, C.c_int, c_i64, c_f32p, C.c_void_p, c_i64, C.c_void_p]),
+    "casync_hubert_forward_tap": (C.c_int, [C.c_void_p, c_f32p, C.c_int, c_i64, C.c_int, C.c_int, c_f32p, C.c_void_p, c_i64,
+                                            C.c_void_p]),
+    "casync_op_hubert_conv0": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "casync_op_hubert_layernorm": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_float,
+                                             C.c_int, C.c_void_p]),
+    "casync_op_hubert_posconv": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_hubert_attention": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_rows_gemm": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      c_f32p, C.c_int, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)
-ABI_VERSION = 7          # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
+ABI_VERSION = 8          # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
 
 
 def lib_path() -> str:
@@ -176,3 +198,14 @@ def packed_layout(mode: str = "hubert"):
     items = [(lib.casync_packed_name_m(m, i).decode(), lib.casync_packed_offset_m(m, i),
               lib.casync_packed_size_m(m, i)) for i in range(n)]
     return items, lib.casync_packed_total_m(m)
+
+
+def hubert_layout(layers: int):
+    """[(name, offset, size)] in floats, and the total, of the HuBERT engine's packed buffer for `layers` layers."""
+    lib = load()
+    n = lib.casync_hubert_packed_count(layers)
+    if n <= 0:
+        raise ValueError(f"HuBERT engine: no packed layout for {layers} layers")
+    items = [(lib.casync_hubert_packed_name(layers, i).decode(), lib.casync_hubert_packed_offset(layers, i),
+              lib.casync_hubert_packed_size(layers, i)) for i in range(n)]
+    return items, lib.casync_hubert_packed_total(layers)

@@ -38,6 +38,8 @@ template <> __device__ __forceinline__ void st4<bf16_t>(bf16_t* p, f32x4 v) {
 }
 
 __device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : v * CASYNC_LRELU_SLOPE; }
+// exact GELU, x * Phi(x) with the error function (torch.nn.functional.gelu, approximate='none')
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
 
 // Bilinear x2 upsample with align_corners=True (module/unet.py:86-91), the arithmetic of ATen's upsample_bilinear2d
 // evaluated exactly as written: src = dst * (in-1)/(out-1), l1 = frac, l0 = 1 - l1, taps combined as
@@ -85,6 +87,13 @@ __device__ __forceinline__ f32x4 ups_lerp(const UpsTap& ty, const UpsTap& tx, f3
   }
   return r;
 }
+
+// The device's cross-handle forward gate (engine.hip): a forward of `owner` on `caller` first waits for the forward another
+// handle (U-Net or HuBERT) enqueued last on the same device; *ev is the owner's event slot, recorded behind its forward when
+// somebody else's follows.  Held (the returned lock) until the forward is enqueued.  casync_gate_forget: on destroy.
+#include <mutex>
+int casync_gate_enter(int device, const void* owner, hipEvent_t* ev, hipStream_t caller, std::unique_lock<std::mutex>* lock);
+void casync_gate_forget(int device, const void* owner, hipEvent_t* ev);
 
 // thread-local error text behind casync_last_error()
 void casync_set_error(const char* fmt, ...);
@@ -266,6 +275,11 @@ constexpr long long kStreamKBytes = kStreamKFloats * 4 + kStreamKCounters * 4;
 // a, w, c (and the (T) epilogue pointers) are `dtype` elements; lda/ldc in elements
 int launch_pw_gemm(const void* a, int lda, const void* w, void* c, int ldc, int m, int n, int k,
                    const GemmEpilogue& epi, hipStream_t stream, int dtype = DT_F32);
+
+// fp32 GEMM whose A rows may overlap (lda < K: a channels-last strided conv, HuBERT's feature encoder); epi.act is 0 or 3
+// (exact GELU), bias and post_res are the only other epilogue terms; K % 32 == 0, N % 64 == 0
+int launch_rows_gemm(const float* a, int lda, const float* w, float* c, int ldc, int m, int n, int k, const GemmEpilogue& epi,
+                     hipStream_t stream);
 
 // dense 3x3 convolution + bias (+ the activation epi.act: LeakyReLU or ReLU) as an implicit GEMM on the ring kernel: no
 // im2col buffer, the taps are gathered by the LDS-DMA loads themselves.  in: [B,H,W,cin] contiguous NHWC,

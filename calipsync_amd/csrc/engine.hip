@@ -914,7 +914,8 @@ namespace {
 // forward cost 4 us per forward at B = 8).
 struct FwdGate {
   std::mutex m;
-  casync_handle last = nullptr;     // the handle whose forward was enqueued last on this device ...
+  const void* last = nullptr;       // the handle (U-Net or HuBERT) whose forward was enqueued last on this device ...
+  hipEvent_t* last_ev = nullptr;    // ... its event slot ...
   hipStream_t last_stream = nullptr;   // ... and the caller's stream it ended on (its lanes join there before it returns)
 };
 FwdGate& fwd_gate(int device) {
@@ -931,6 +932,32 @@ StreamPool& stream_pool(int device) {
   return pools[device < 0 || device >= 64 ? 0 : device];
 }
 }  // namespace
+
+int casync_gate_enter(int device, const void* owner, hipEvent_t* ev, hipStream_t caller, std::unique_lock<std::mutex>* lock) {
+  FwdGate& gate = fwd_gate(device);
+  *lock = std::unique_lock<std::mutex>(gate.m);
+  static const bool gate_off = getenv("CASYNC_NO_FWD_GATE") != nullptr;   // diagnosis only (tools/experiments/two_models.py)
+  if (!gate_off && gate.last && gate.last != owner) {
+    if (!*gate.last_ev) CASYNC_CHECK_HIP(hipEventCreateWithFlags(gate.last_ev, hipEventDisableTiming));
+    if (hipEventRecord(*gate.last_ev, gate.last_stream) == hipSuccess) {
+      CASYNC_CHECK_HIP(hipStreamWaitEvent(caller, *gate.last_ev, 0));
+    } else {                          // (the other forward's stream is gone: its work is done or the device will tell)
+      (void)hipGetLastError();
+      CASYNC_CHECK_HIP(hipDeviceSynchronize());
+    }
+  }
+  gate.last = owner;
+  gate.last_ev = ev;
+  gate.last_stream = caller;
+  return CASYNC_OK;
+}
+
+void casync_gate_forget(int device, const void* owner, hipEvent_t* ev) {
+  FwdGate& gate = fwd_gate(device);
+  std::lock_guard<std::mutex> lock(gate.m);
+  if (gate.last == owner) gate.last = nullptr, gate.last_ev = nullptr;
+  if (*ev) { (void)hipEventSynchronize(*ev); (void)hipEventDestroy(*ev); *ev = nullptr; }
+}
 
 extern "C" {
 
@@ -1028,10 +1055,7 @@ void casync_destroy(casync_handle h) {
   if (!h) return;
   DeviceGuard guard(h->device);
   {
-    FwdGate& gate = fwd_gate(h->device);
-    std::lock_guard<std::mutex> lock(gate.m);
-    if (gate.last == h) gate.last = nullptr;
-    if (h->ev_fwd) { (void)hipEventSynchronize(h->ev_fwd); (void)hipEventDestroy(h->ev_fwd); h->ev_fwd = nullptr; }
+    casync_gate_forget(h->device, h, &h->ev_fwd);
   }
   if (h->streams_ready) {
     for (int l = 0; l < casync_engine::kMaxLanes; ++l) {
@@ -1166,20 +1190,8 @@ static int run_forward(casync_handle h, const FwdArgs& A, hipStream_t caller, st
   DeviceGuard guard(h->device);
   CASYNC_CHECK_HIP(guard.err);
   const bool serial = prof != nullptr;
-  FwdGate& gate = fwd_gate(h->device);
-  std::unique_lock<std::mutex> gate_lock(gate.m);          // held until this forward is enqueued
-  static const bool gate_off = getenv("CASYNC_NO_FWD_GATE") != nullptr;   // diagnosis only (tools/experiments/two_models.py)
-  if (!gate_off && gate.last && gate.last != h) {
-    if (!gate.last->ev_fwd) CASYNC_CHECK_HIP(hipEventCreateWithFlags(&gate.last->ev_fwd, hipEventDisableTiming));
-    if (hipEventRecord(gate.last->ev_fwd, gate.last_stream) == hipSuccess) {
-      CASYNC_CHECK_HIP(hipStreamWaitEvent(caller, gate.last->ev_fwd, 0));
-    } else {                          // (the other forward's stream is gone: its work is done or the device will tell)
-      (void)hipGetLastError();
-      CASYNC_CHECK_HIP(hipDeviceSynchronize());
-    }
-  }
-  gate.last = h;
-  gate.last_stream = caller;
+  std::unique_lock<std::mutex> gate_lock;          // held until this forward is enqueued
+  if (int st = casync_gate_enter(h->device, h, &h->ev_fwd, caller, &gate_lock)) return st;
   const bool overlap = o.overlap != 0 && !serial;
   int lanes = o.lanes < 1 ? 1 : (o.lanes > casync_engine::kMaxLanes ? casync_engine::kMaxLanes : o.lanes);
   if (A.batch < kMinLaneBatch * lanes) lanes = 1;  // small batches are latency-bound: cutting them only adds launches

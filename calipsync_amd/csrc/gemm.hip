@@ -96,7 +96,10 @@ __device__ __forceinline__ float col_const(const float* regs, const float* mem, 
 // occupancy -- of every other GEMM instance (measured: bf16 128x128 2 -> 1 waves/SIMD, -13 % at B=512).
 // RELU: epi.act = 2 (ReLU) is honoured -- compiled into the implicit-GEMM conv instances only (AudioConvWenet's conv3 / conv5):
 // a runtime slope in the shared activation cost every GEMM instance 2-4 registers, the bf16 64x64 / upsampling ones a wave per SIMD.
-template <typename T, int NT, int BM, int BN, int PAD = 4, bool SWZ = false, bool LITE = false, bool EUPS = false, bool RELU = false>
+// GELU: the activation is the exact (erf) GELU instead, whatever epi.act says -- compiled into pw_gemm_gelu_kernel only (HuBERT's
+// feed-forward and positional conv, launch_rows_gemm with act 3), for the same reason.
+template <typename T, int NT, int BM, int BN, int PAD = 4, bool SWZ = false, bool LITE = false, bool EUPS = false, bool RELU = false,
+          bool GELU = false>
 __device__ __forceinline__ void epilogue_rows_cols(const float* Cs, int m0, int n0, int M, T* __restrict__ C, int ldc,
                                                    const GemmEpilogue& epi, int tid, const EpiCols<T>& k) {
   constexpr int CPT = V16<T>::N, TPR = BN / CPT, RPP = NT / TPR, LDC_S = BN + PAD;
@@ -135,7 +138,10 @@ __device__ __forceinline__ void epilogue_rows_cols(const float* Cs, int m0, int 
 #pragma unroll
       for (int e = 0; e < CPT; ++e) v.v[e] += col_const<LITE>(k.pscale, epi.pre_scale, 1.f, n, e) * r.v[e];
     }
-    if (epi.act) {
+    if constexpr (GELU) {
+#pragma unroll
+      for (int e = 0; e < CPT; ++e) v.v[e] = gelu_erf(v.v[e]);
+    } else if (epi.act) {
 #pragma unroll
       for (int e = 0; e < CPT; ++e) v.v[e] = lrelu(v.v[e]);
       if constexpr (RELU) {   // act 2: ReLU = max(LeakyReLU(v), 0), exactly (a negative v maps to +0)
@@ -170,12 +176,12 @@ __device__ __forceinline__ void epilogue_rows_cols(const float* Cs, int m0, int 
   }
 }
 
-template <typename T, int NT, int BM, int BN, int PAD = 4, bool SWZ = false, bool EUPS = false, bool RELU = false>
+template <typename T, int NT, int BM, int BN, int PAD = 4, bool SWZ = false, bool EUPS = false, bool RELU = false, bool GELU = false>
 __device__ __forceinline__ void epilogue_rows(const float* Cs, int m0, int n0, int M, T* __restrict__ C,
                                               int ldc, const GemmEpilogue& epi, int tid) {
   EpiCols<T> k;
   k.load(epi, n0 + (tid % (BN / V16<T>::N)) * V16<T>::N);
-  epilogue_rows_cols<T, NT, BM, BN, PAD, SWZ, false, EUPS, RELU>(Cs, m0, n0, M, C, ldc, epi, tid, k);
+  epilogue_rows_cols<T, NT, BM, BN, PAD, SWZ, false, EUPS, RELU, GELU>(Cs, m0, n0, M, C, ldc, epi, tid, k);
 }
 
 template <typename T, int BM, int BN, int WM, int WN>
@@ -377,7 +383,7 @@ constexpr int glds_min_waves() {
   return sizeof(T) == 4 && BM == 64 && BN == 64 && NST == 2 && !CONV ? 5 : 1;
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int NST, bool CONV, bool EUPS>
+template <typename T, int BM, int BN, int WM, int WN, int NST, bool CONV, bool EUPS, bool GELU = false>
 __device__ __forceinline__ void glds_body(const T* __restrict__ A, int lda, const T* __restrict__ W, T* __restrict__ C,
                                           int ldc, int M, int N, int K, int n_ntiles, int nwg, int dp_tiles, int sk_wgs,
                                           int sk_per, const GemmEpilogue& epi) {
@@ -743,9 +749,9 @@ __device__ __forceinline__ void glds_body(const T* __restrict__ A, int lda, cons
         }
         __syncthreads();
       }
-      if constexpr (WK == 2) epilogue_rows_cols<T, 256, BM / WM, BN, 4, false, false, EUPS, CONV>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid, kcols);
-      else if (PREF64) epilogue_rows_cols<T, 256, BM / WM, BN, 4, false, false, EUPS, CONV>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid, kcols);
-      else epilogue_rows<T, 256, BM / WM, BN, 4, false, EUPS, CONV>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid);
+      if constexpr (WK == 2) epilogue_rows_cols<T, 256, BM / WM, BN, 4, false, false, EUPS, CONV, GELU>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid, kcols);
+      else if (PREF64) epilogue_rows_cols<T, 256, BM / WM, BN, 4, false, false, EUPS, CONV, GELU>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid, kcols);
+      else epilogue_rows<T, 256, BM / WM, BN, 4, false, EUPS, CONV, GELU>(Cs, m0 + h * (BM / WM), n0, M, C, ldc, epi, tid);
       __syncthreads();   // staging consumed before the next block / the next loads overwrite the ring
     }
   };
@@ -864,13 +870,22 @@ __global__ __launch_bounds__(256) void pw_gemm_ups_kernel(
   glds_body<T, BM, BN, WM, WN, NST, false, true>(A, lda, W, C, ldc, M, N, K, n_ntiles, nwg, dp_tiles, sk_wgs, sk_per, epi);
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int NST, bool CONV = false, bool EUPS = false>
+// ... and with the exact GELU as its activation (HuBERT: launch_rows_gemm with act 3)
+template <typename T, int BM, int BN, int WM, int WN, int NST>
+__global__ __launch_bounds__(256) void pw_gemm_gelu_kernel(
+    const T* __restrict__ A, int lda, const T* __restrict__ W, T* __restrict__ C, int ldc, int M, int N, int K, int n_ntiles,
+    int nwg, int dp_tiles, int sk_wgs, int sk_per, GemmEpilogue epi) {
+  glds_body<T, BM, BN, WM, WN, NST, false, false, true>(A, lda, W, C, ldc, M, N, K, n_ntiles, nwg, dp_tiles, sk_wgs, sk_per, epi);
+}
+
+template <typename T, int BM, int BN, int WM, int WN, int NST, bool CONV = false, bool EUPS = false, bool GELU = false>
 int launch_glds_t(const T* a, int lda, const T* w, T* c, int ldc, int m, int n, int k,
                   const GemmEpilogue& epi, hipStream_t stream, bool use_sk) {
   constexpr size_t lds = (size_t)NST * (BM + BN) * ROWB;
   static unsigned long long attr_once = 0;
   auto kern = [] {
-    if constexpr (EUPS) return pw_gemm_ups_kernel<T, BM, BN, WM, WN, NST>;
+    if constexpr (GELU) return pw_gemm_gelu_kernel<T, BM, BN, WM, WN, NST>;
+    else if constexpr (EUPS) return pw_gemm_ups_kernel<T, BM, BN, WM, WN, NST>;
     else return pw_gemm_glds_kernel<T, BM, BN, WM, WN, NST, CONV>;
   }();
   if (int st = casync_ensure_dyn_lds(&attr_once, reinterpret_cast<const void*>(kern), (int)lds)) return st;
@@ -1081,6 +1096,32 @@ int launch_pw_gemm(const void* a, int lda, const void* w, void* c, int ldc, int 
                                                    static_cast<float*>(c), ldc, m, n, k, epi, stream, false);
     default: return launch_cfg<C128x32, 4, 1>(a, lda, w, c, ldc, m, n, k, epi, stream, dtype, sk);
   }
+}
+
+// Overlapping-row GEMM (HuBERT): row m of A starts at m * lda and may overlap the next one (lda < K), which makes a
+// channels-last conv with stride s and kernel k a plain GEMM with lda = s * C and K = k * C.  fp32, the data-parallel
+// ring tiles only (no stream-K, so the bits do not depend on the chip's load), act 0 (none) or 3 (exact GELU).
+int launch_rows_gemm(const float* a, int lda, const float* w, float* c, int ldc, int m, int n, int k, const GemmEpilogue& epi,
+                     hipStream_t stream) {
+  CASYNC_REQUIRE(a && w && c, "rows_gemm: null pointer");
+  CASYNC_REQUIRE(m > 0 && n > 0 && k > 0, "rows_gemm: empty problem m=%d n=%d k=%d", m, n, k);
+  CASYNC_REQUIRE(k % 32 == 0 && n % 64 == 0, "rows_gemm: K=%d must be a multiple of 32 and N=%d of 64", k, n);
+  CASYNC_REQUIRE(lda > 0 && lda % 4 == 0, "rows_gemm: lda=%d must be a positive multiple of 4", lda);
+  CASYNC_REQUIRE(ldc >= n && ldc % 4 == 0, "rows_gemm: ldc=%d must be >= N=%d and a multiple of 4", ldc, n);
+  CASYNC_REQUIRE(((uintptr_t)a % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)c % 16) == 0,
+                 "rows_gemm: A/W/C must be 16-B aligned");
+  CASYNC_REQUIRE(epi.act == 0 || epi.act == 3, "rows_gemm: act %d (0 none, 3 GELU)", epi.act);
+  CASYNC_REQUIRE(!epi.pre_res && !epi.ups_src && !epi.acc_out && !epi.aff_s && !epi.conv_on && !epi.sk_ws,
+                 "rows_gemm: bias and a post-residual are the only epilogue terms");
+  CASYNC_REQUIRE(!epi.post_res || (epi.ld_post % 4 == 0 && (uintptr_t)epi.post_res % 16 == 0), "rows_gemm: bad post-residual");
+  CASYNC_REQUIRE(fits32(m, n, k, lda, DT_F32), "rows_gemm: operand larger than 2 GiB");
+  const long long t64 = (long long)((m + 63) / 64) * (n / 64);
+  if (t64 >= 1024) {   // several rounds of 64x64 tiles: the 128x64 tile streams fewer bytes per FLOP
+    return epi.act == 3 ? launch_glds_t<float, 128, 64, 2, 2, 2, false, false, true>(a, lda, w, c, ldc, m, n, k, epi, stream, false)
+                        : launch_glds_t<float, 128, 64, 2, 2, 2>(a, lda, w, c, ldc, m, n, k, epi, stream, false);
+  }
+  return epi.act == 3 ? launch_glds_t<float, 64, 64, 2, 2, 2, false, false, true>(a, lda, w, c, ldc, m, n, k, epi, stream, false)
+                      : launch_glds_t<float, 64, 64, 2, 2, 2>(a, lda, w, c, ldc, m, n, k, epi, stream, false);
 }
 
 // ---------------------------------------------------------------- dense 3x3 as an implicit GEMM

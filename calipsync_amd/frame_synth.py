@@ -246,10 +246,10 @@ class FrameSynthesizer:
 class VideoStreamManager:
     """Offline driver with the reference's signature (inference.py:14-20, 47): features -> frames -> file.
 
-    HuBERT extraction is outside the hot-path contract (the north star consumes
-    pre-extracted windows; no HuBERT weights ship), so ``hubert_path`` may be a callable
-    ``audio_path -> [T,2,1024] array`` or is ignored when ``audio_path`` is itself a ``.npy`` of
-    features.  The mp4 writer / ffmpeg mux (inference.py:88-110) is used when cv2 / ffmpeg exist; otherwise
+    ``hubert_path`` is what the reference takes, a HuBERT checkpoint directory: the extractor
+    (``calipsync_amd.hubert.HubertExtractor``, HubertModel on the HIP engine) is built from it on the first audio file
+    that is not a ``.npy``.  It may also be a callable ``audio_path -> [T,2,1024] array``, and it is not used when
+    ``audio_path`` is itself a ``.npy`` of features.  The mp4 writer / ffmpeg mux (inference.py:88-110) is used when cv2 / ffmpeg exist; otherwise
     the frames are written as a Motion-JPEG ``.avi`` with Pillow (``mjpeg_avi.py``; no audio track)."""
 
     def __init__(self, data_dir: str, unet_checkpoint: Optional[str], hubert_path=None, device: str = "cuda:0",
@@ -257,6 +257,8 @@ class VideoStreamManager:
         self.synthesizer = FrameSynthesizer(unet_checkpoint=unet_checkpoint, data_dir=data_dir, device=device,
                                             batch_size=batch_size, **synth_kwargs)
         self.hubert_extractor = hubert_path if callable(hubert_path) else None
+        self._hubert_dir = hubert_path if isinstance(hubert_path, (str, os.PathLike)) else None
+        self._device = device
         self.feature_sample_rate = 16000
         self.output_sample_rate = output_sample_rate
         self.fps = 25
@@ -264,10 +266,14 @@ class VideoStreamManager:
     def process_single_file(self, audio_path: str, output_path: str):
         if audio_path.endswith(".npy"):
             features = np.load(audio_path)
-        elif self.hubert_extractor is not None:
-            features = self.hubert_extractor(audio_path)
         else:
-            raise RuntimeError("no HuBERT extractor configured: pass pre-extracted features (.npy) or a callable")
+            if self.hubert_extractor is None and self._hubert_dir is not None:   # built on first use
+                from .hubert import HubertExtractor
+                self.hubert_extractor = HubertExtractor(os.fspath(self._hubert_dir), self._device).extract_from_file
+            if self.hubert_extractor is None:
+                raise RuntimeError("no HuBERT extractor configured: pass pre-extracted features (.npy), a HuBERT checkpoint "
+                                   "directory or a callable")
+            features = self.hubert_extractor(audio_path)
         frames = [info["frame"] for info in self.synthesizer.iterate_synthesized_frames(features, 0, True)]
         if not frames:
             raise ValueError("no video frame was generated")

@@ -43,7 +43,7 @@ enum {
 /* ---- introspection (callable without a GPU) --------------------------- */
 /* Bumped on every change of a prototype, struct layout or the packed-weight layout; the ctypes
  * host (calipsync_amd/_lib.py) refuses a library whose version differs from the one it binds.   */
-#define CASYNC_ABI_VERSION 7
+#define CASYNC_ABI_VERSION 8
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -296,6 +296,54 @@ int casync_op_inc(const float* x_nchw, const float* packed_inc, void* out, int l
 /* OutConv + outc_bn + sigmoid -> NCHW (module/unet.py:100-106,342-344)       */
 int casync_op_outc(const void* in, int ld_in, const float* w, const float* b,
                    float* out_nchw, int batch, casync_stream stream);
+
+/* ---- HuBERT feature extractor (ABI 8) ---------------------------------- */
+/* transformers HubertModel (hubert-large: hidden 1024, 16 heads, FFN 4096, stable layer norm,
+ * exact GELU, eps 1e-5) with any number of layers, fp32, batch 1 in the reference
+ * (image_infer_v1/utils/hubert_extractor.py:19-58: model(batch).last_hidden_state).  Its own handle,
+ * packed layout and workspace; forwards take the same cross-handle gate as casync_forward.        */
+typedef struct casync_hubert* casync_hubert_handle;
+/* Packed layout of a model with `layers` encoder layers (1..48; else 0 / NULL / -1).  Tensors start
+ * on 256-B boundaries.  Conv weights are [cout][tap][cin]; pos.w is [group][tap][n][c] with the
+ * weight norm folded; layer<l>.qkv.w stacks q, k, v projections ([3072][1024]) with q (rows and
+ * bias) pre-scaled by 1/8; linear weights are torch's [out][in].                                  */
+int         casync_hubert_packed_count(int layers);
+const char* casync_hubert_packed_name(int layers, int i);
+int64_t     casync_hubert_packed_offset(int layers, int i);
+int64_t     casync_hubert_packed_size(int layers, int i);
+int64_t     casync_hubert_packed_total(int layers);
+/* tokens of a waveform of `samples` samples (0 below one receptive field, 400 samples)           */
+int64_t     casync_hubert_tokens(int64_t samples);
+/* workspace of a forward of `batch` waveforms of `samples` samples (0 when there is no token)    */
+int64_t     casync_hubert_workspace_bytes(int batch, int64_t samples);
+int  casync_hubert_create(int device_id, int layers, casync_hubert_handle* out);
+void casync_hubert_destroy(casync_hubert_handle h);
+/* casync_hubert_packed_total(layers) floats; _device adopts a caller-owned, 256-B aligned buffer */
+int  casync_hubert_load_weights_host(casync_hubert_handle h, const float* packed, int64_t n_floats);
+int  casync_hubert_load_weights_device(casync_hubert_handle h, const float* packed_dev, int64_t n_floats);
+/* wave_dev [batch, samples] (already normalised), out_dev [batch, T, 1024] = last_hidden_state.
+ * Enqueues on `stream`, no host synchronisation, no allocation.                                 */
+int  casync_hubert_forward(casync_hubert_handle h, const float* wave_dev, int batch, int64_t samples, float* out_dev,
+                           void* workspace_dev, int64_t workspace_bytes, casync_stream stream);
+/* Debug: the same forward, stopped at `stage` and that intermediate written to out_dev:
+ * 1 = feature-encoder output [batch, T, 512], 2 = input to layer 0 (after the positional conv)
+ * [batch, T, 1024], 3 = hidden states after n_layers layers, before the final LayerNorm.          */
+int  casync_hubert_forward_tap(casync_hubert_handle h, const float* wave_dev, int batch, int64_t samples, int stage,
+                               int n_layers, float* out_dev, void* workspace_dev, int64_t workspace_bytes,
+                               casync_stream stream);
+/* single operators (tests): conv0 + LayerNorm + GELU -> [batch*T0, 512]; LayerNorm over 512 / 1024
+ * columns (+ GELU); out = x + GELU(posconv(x) + b) over [batch, T, 1024]; attention from the fused
+ * [batch*T, 3072] q|k|v buffer -> [batch*T, 1024]; GEMM with overlapping A rows (lda may be < K),
+ * act 0 or 3 (GELU), bias and post-residual [m, ld_post].                                        */
+int  casync_op_hubert_conv0(const float* wave, int batch, int samples, const float* w, const float* b, const float* g,
+                            const float* be, float* out, casync_stream stream);
+int  casync_op_hubert_layernorm(const float* in, int ldi, float* out, int ldo, int rows, int cols, const float* g,
+                                const float* b, float eps, int gelu, casync_stream stream);
+int  casync_op_hubert_posconv(const float* x, const float* w_packed, const float* bias, float* out, int batch, int T,
+                              casync_stream stream);
+int  casync_op_hubert_attention(const float* qkv, float* out, int batch, int T, casync_stream stream);
+int  casync_op_rows_gemm(const float* a, int lda, const float* w, const float* bias, float* c, int ldc, int m, int n,
+                         int k, int act, const float* post_res, int ld_post, casync_stream stream);
 
 #ifdef __cplusplus
 }
