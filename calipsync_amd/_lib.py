@@ -55,6 +55,8 @@ _PROTOS = {
     "casync_op_set_dtype": (C.c_int, [C.c_int]),
     "casync_debug_gemm_stamps": (C.c_int, [C.c_void_p]),
     "casync_debug_ir_stamps": (C.c_int, [C.c_void_p]),
+    "casync_debug_launch_log": (C.c_int, [C.c_int]),
+    "casync_debug_launched": (C.c_int, [C.c_char_p, C.c_int]),
     "casync_op_pw_gemm": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p,
                                     C.c_int, c_f32p, c_f32p, C.c_void_p]),
@@ -64,6 +66,8 @@ _PROTOS = {
                                       C.c_void_p]),
     "casync_op_pw_dw": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, c_f32p, C.c_int, C.c_void_p]),
+    "casync_op_pw_dw_rect": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_pw_gemm_ups": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_ir_fused": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
@@ -119,7 +123,7 @@ _PROTOS = {
 }
 
 EXPORTS = tuple(_PROTOS)
-ABI_VERSION = 8          # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
+ABI_VERSION = 9          # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
 
 
 def lib_path() -> str:

@@ -187,12 +187,30 @@ struct CasyncLaunchNote {
 };
 inline thread_local CasyncLaunchNote casync_launch_note;
 
+// Debug only (casync_debug_launch_log / casync_debug_launched): the distinct kernels launched on this thread since the log
+// was cleared, recorded while `on`.  Apart from the note above, which Runner::run clears around every profiled launch.
+struct CasyncLaunchLog {
+  static constexpr int kCap = 256;   // more than the library's kernel instances
+  bool on = false;
+  bool overflow = false;             // a distinct kernel found the log full
+  int n = 0;
+  const void* kernel[kCap];
+  void add(const void* k) {
+    for (int i = 0; i < n; ++i)
+      if (kernel[i] == k) return;
+    if (n < kCap) kernel[n++] = k;
+    else overflow = true;
+  }
+};
+inline thread_local CasyncLaunchLog casync_launch_log;
+
 template <typename... P, typename... A>
 int casync_launch(void (*k)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A&&... a) {
   hipLaunchKernelGGL(k, grid, block, lds, s, std::forward<A>(a)...);
   CASYNC_CHECK_HIP(hipGetLastError());
   casync_launch_note.kernel = reinterpret_cast<const void*>(k);
   ++casync_launch_note.count;
+  if (casync_launch_log.on) casync_launch_log.add(reinterpret_cast<const void*>(k));
   return CASYNC_OK;
 }
 

@@ -1374,6 +1374,25 @@ int casync_debug_gemm_stamps(void* dev_words) {
   g_gemm_stamps = static_cast<unsigned long long*>(dev_words);
   return CASYNC_OK;
 }
+int casync_debug_launch_log(int on) {
+  casync_launch_log.n = 0;
+  casync_launch_log.overflow = false;
+  casync_launch_log.on = on != 0;
+  return CASYNC_OK;
+}
+int casync_debug_launched(char* buf, int cap) {
+  CASYNC_REQUIRE(buf && cap > 0, "debug_launched: no buffer");
+  CASYNC_REQUIRE(!casync_launch_log.overflow, "debug_launched: more than %d distinct kernels", CasyncLaunchLog::kCap);
+  std::string all;
+  for (int i = 0; i < casync_launch_log.n; ++i) {
+    const char* mangled = hipKernelNameRefByPtr(casync_launch_log.kernel[i], nullptr);
+    all += mangled ? kernel_short_name(mangled) : std::string("?");
+    all += '\n';
+  }
+  CASYNC_REQUIRE((int)all.size() < cap, "debug_launched: %d bytes needed, buffer holds %d", (int)all.size() + 1, cap);
+  memcpy(buf, all.c_str(), all.size() + 1);
+  return casync_launch_log.n;
+}
 static thread_local int g_op_dtype = DT_F32;
 int casync_op_set_dtype(int dtype) {
   CASYNC_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "op_set_dtype: %d", dtype);
@@ -1442,6 +1461,12 @@ int casync_op_pw_dw(const void* a, int lda, const void* w1, const float* b1, con
     return launch_pw_dw_bf16(a, lda, w1, b1, wd, bd, d, ldd, frames, hw, stride, cin, cexp, (hipStream_t)stream, ups, ld_ups);
   }
   return launch_pw_dw(a, lda, w1, b1, wd, bd, d, ldd, frames, hw, stride, cin, cexp, (hipStream_t)stream, ups, ld_ups);
+}
+int casync_op_pw_dw_rect(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd, void* d,
+                         int ldd, int frames, int h, int w, int cin, int cexp, casync_stream stream) {
+  if (g_op_dtype == DT_BF16)
+    return launch_pw_dw_bf16_rect(a, lda, w1, b1, wd, bd, d, ldd, frames, h, w, cin, cexp, (hipStream_t)stream);
+  return launch_pw_dw_rect(a, lda, w1, b1, wd, bd, d, ldd, frames, h, w, cin, cexp, (hipStream_t)stream);
 }
 int casync_op_pw_gemm_ups(const void* a, int lda, const void* w, const float* bias, void* c, int ldc, int m, int n, int k, int act,
                           const void* ups, int ld_ups, int h, int w_, casync_stream stream) {

@@ -43,7 +43,7 @@ enum {
 /* ---- introspection (callable without a GPU) --------------------------- */
 /* Bumped on every change of a prototype, struct layout or the packed-weight layout; the ctypes
  * host (calipsync_amd/_lib.py) refuses a library whose version differs from the one it binds.   */
-#define CASYNC_ABI_VERSION 8
+#define CASYNC_ABI_VERSION 9   /* 9: casync_debug_launch_log / casync_debug_launched, casync_op_pw_dw_rect */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -198,6 +198,13 @@ int casync_op_dw3x3(const void* in, const float* w, const float* bias, void* out
  * w tap-major [9][C], out [B,h,wdt,c].  h, wdt even, c % 4 == 0, frames the LDS-slab plan takes (10..40).     */
 int casync_op_dw3x3_ups(const float* pre, const float* g, int ldg, const float* w, const float* bias, float* out,
                         int batch, int h, int wdt, int c, casync_stream stream);
+/* Debug (tests/kernel_ledger.py): casync_debug_launch_log clears this thread's launch log and switches recording on
+ * (on != 0) or off; while it is on, every kernel launch of the thread adds its kernel to the log once.  With it off a
+ * launch does nothing more than before.  casync_debug_launched writes the logged kernels' short names
+ * ("pw_gemm_kernel<__bf16, 128, 128, 2, 2>", the keys of tools/kernel_resources.py and of the profile rows), one per
+ * line, NUL-terminated, into buf; returns their count, CASYNC_ERR_ARG when buf is too small.  Never used by the engine. */
+int casync_debug_launch_log(int on);
+int casync_debug_launched(char* buf, int cap);
 /* Expand 1x1 conv + BN + LeakyReLU + depthwise 3x3 (pad 1, stride 1|2) + BN + LeakyReLU in one kernel, fp32, for the
  * inverted residuals below 32x32 (module/unet.py:17-30): the GEMM's output tile is whole frames, the depthwise conv
  * runs on it in LDS.  a [frames*hw*hw, lda], w1 [cexp][cin], b1 [cexp], wd [9][cexp] tap-major, bd [cexp],
@@ -205,6 +212,11 @@ int casync_op_dw3x3_ups(const float* pre, const float* g, int ldg, const float* 
 int casync_op_pw_dw(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd,
                     void* d, int ldd, int frames, int hw, int stride, int cin, int cexp, const void* ups, int ld_ups,
                     casync_stream stream);
+/* The same on rectangular frames (AudioConvWenet's 16x32 blocks: module/unet.py:119-133), stride 1, one whole frame per
+ * tile: a [frames*h*w, lda], d [frames*h*w, ldd], in the storage type of casync_op_set_dtype (w1 too; b1, wd, bd
+ * fp32).  h x w = 16 x 32; fp32: cin % 16 == 0, cexp % 32 == 0; bf16: cin % 32 == 0, cexp % 64 == 0.               */
+int casync_op_pw_dw_rect(const void* a, int lda, const void* w1, const float* b1, const float* wd, const float* bd,
+                         void* d, int ldd, int frames, int h, int w, int cin, int cexp, casync_stream stream);
 /* 1x1 conv + bias + [bilinear x2 upsample (align_corners=True) of a low-resolution tensor] + LeakyReLU:
  * c[m, :] = act(a[m, :] . w^T + bias + up2x(ups)[m, :]), rows m = pixels (b, y, x) of h x w frames, ups
  * [B*(h/2)*(w/2), ld_ups].  An Up block's expand conv (module/unet.py:90-96 + 17-20) with the upsample commuted behind

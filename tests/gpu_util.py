@@ -42,6 +42,23 @@ def nchw(t):     # NHWC device tensor -> NCHW on the CPU
 
 
 @contextlib.contextmanager
+def launched():
+    """Record the kernels this thread launches inside the block (casync_debug_launch_log): yields a set that holds their
+    short names (the keys of tools/kernel_resources.table()) once the block has ended."""
+    import ctypes
+    lib = _lib.load()
+    names = set()
+    _lib.check(lib.casync_debug_launch_log(1), "casync_debug_launch_log")
+    try:
+        yield names
+        buf = ctypes.create_string_buffer(1 << 16)
+        _lib.check(lib.casync_debug_launched(buf, len(buf)), "casync_debug_launched")
+        names.update(n for n in buf.value.decode().split("\n") if n)
+    finally:
+        lib.casync_debug_launch_log(0)
+
+
+@contextlib.contextmanager
 def options(target=None, **kv):
     """Set engine switches (casync_set_option) for the duration of a block and restore them: on a
     calipsync_amd.unet.Model, or on the process defaults used by the casync_op_* calls (target None)."""
