@@ -120,10 +120,23 @@ _PROTOS = {
     "casync_op_hubert_attention": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_rows_gemm": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       c_f32p, C.c_int, C.c_void_p]),
+    # HuBERT, bf16 precision (ABI 10); c_f32p is c_void_p: bf16 buffers pass the same way
+    "casync_hubert_create_ex": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "casync_hubert_workspace_bytes_h": (c_i64, [C.c_void_p, C.c_int, c_i64]),
+    "casync_op_hubert16_conv0": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p]),
+    "casync_op_hubert16_layernorm512": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, c_f32p, c_f32p, C.c_float,
+                                                  C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_hubert16_layernorm1024": (C.c_int, [c_f32p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                   c_f32p, c_f32p, C.c_float, C.c_int, C.c_void_p]),
+    "casync_op_hubert16_gelu": (C.c_int, [C.c_void_p, c_i64, C.c_void_p]),
+    "casync_op_hubert16_widen": (C.c_int, [C.c_void_p, c_f32p, c_i64, C.c_void_p]),
+    "casync_op_hubert16_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_rows_gemm_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)
-ABI_VERSION = 9          # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
+ABI_VERSION = 10         # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
 
 
 def lib_path() -> str:

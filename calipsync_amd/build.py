@@ -12,6 +12,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 LIB_PATH = os.path.join(LIB_DIR, "libcasync_hip.so")
+# Kernels of the bf16 HuBERT handle: compiled to their own object directory (tests/kernel_ledger_hb16.py is their ledger;
+# tests/kernel_ledger.py stays the ledger of lib/obj/) and linked into the same library.
+OBJ_DIR_HB16 = os.path.join(LIB_DIR, "obj_hb16")
+SOURCES_HB16 = ["hubert_bf16.hip"]
 SOURCES = ["runtime.hip", "gemm.hip", "ops.hip", "ir_fused.hip", "pw_dw.hip", "pw_dw_bf16.hip", "attention.hip", "attention_bf16.hip", "frame_ops.hip", "hubert.hip", "engine.hip"]
 HEADERS = ["common.h", "ir_common.h", "pw_dw_common.h", os.path.join("..", "..", "include", "casync_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
@@ -38,7 +42,7 @@ def _header_paths():
 def is_stale() -> bool:
     """True when the library is missing or older than any of its sources / headers.  A deployment that ships the
     library without csrc/ has nothing to be stale against: missing sources count as "not newer"."""
-    return _newer(LIB_PATH, [os.path.join(CSRC, s) for s in SOURCES] + _header_paths())
+    return _newer(LIB_PATH, [os.path.join(CSRC, s) for s in SOURCES + SOURCES_HB16] + _header_paths())
 
 
 def source_hash() -> str:
@@ -47,7 +51,7 @@ def source_hash() -> str:
     version of the kernels are never quoted for another."""
     import hashlib
     h = hashlib.sha256()
-    for path in [os.path.join(CSRC, s) for s in SOURCES] + _header_paths():
+    for path in [os.path.join(CSRC, s) for s in SOURCES + SOURCES_HB16] + _header_paths():
         h.update(os.path.basename(path).encode() + b"\0")
         with open(path, "rb") as f:
             h.update(f.read())
@@ -97,6 +101,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not is_stale():
         return LIB_PATH
     os.makedirs(OBJ_DIR, exist_ok=True)
+    os.makedirs(OBJ_DIR_HB16, exist_ok=True)
     # One builder at a time: bench.py --gpus N, torchrun ranks and pytest workers can all reach load() -> build() at
     # once after a checkout; without the lock they compile into the same obj/*.o and link over a library another rank
     # is dlopen-ing.  The link goes to a temporary name and is renamed into place (atomic on one filesystem).
@@ -115,7 +120,7 @@ def _build_locked(force: bool, verbose: bool) -> str:
     hipcc = _hipcc()
 
     def compile_one(src: str):
-        obj = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
+        obj = os.path.join(OBJ_DIR_HB16 if src in SOURCES_HB16 else OBJ_DIR, src.replace(".hip", ".o"))
         path = os.path.join(CSRC, src)
         if not force and not _newer(obj, [path] + _header_paths()):
             return obj, None
@@ -125,8 +130,9 @@ def _build_locked(force: bool, verbose: bool) -> str:
         res = subprocess.run(cmd, capture_output=True, text=True)
         return obj, (res.stdout + res.stderr if res.returncode else None)
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 4)) as pool:
-        results = list(pool.map(compile_one, SOURCES))
+    sources = SOURCES + SOURCES_HB16
+    with ThreadPoolExecutor(max_workers=min(len(sources), os.cpu_count() or 4)) as pool:
+        results = list(pool.map(compile_one, sources))
     errors = [err for _, err in results if err]
     if errors:
         raise RuntimeError("hipcc failed:\n" + "\n".join(errors))

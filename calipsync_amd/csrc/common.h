@@ -299,6 +299,26 @@ int launch_pw_gemm(const void* a, int lda, const void* w, void* c, int ldc, int 
 int launch_rows_gemm(const float* a, int lda, const float* w, float* c, int ldc, int m, int n, int k, const GemmEpilogue& epi,
                      hipStream_t stream);
 
+// ... and its bf16 form (the bf16 HuBERT handle): a, w, c bf16, bias fp32, nothing else in the epilogue; K % 64 == 0,
+// N % 64 == 0.  Existing bf16 ring instances only, data-parallel tiles, the tile a function of the shape alone.
+int launch_rows_gemm_bf16(const void* a, int lda, const void* w, const float* bias, void* c, int ldc, int m, int n, int k,
+                          hipStream_t stream);
+
+// ---- HuBERT, bf16 handle (hubert_bf16.hip; pointers named void* are bf16) ----
+int launch_hb16_conv0(const float* wave, int batch, int S, const float* w, const float* b, const float* g, const float* be,
+                      void* out, hipStream_t s);
+// 512 columns: bf16 in; bf16 out with GELU (conv stack, in == out allowed) or fp32 out without (feature projection)
+int launch_hb16_layernorm512(const void* in, int ldi, void* out, int ldo, int rows, const float* g, const float* b, float eps,
+                             bool out_f32, bool gelu, hipStream_t s);
+// 1024 columns: v = h (+ delta, bf16, optional; written back to h when store_h), out = LayerNorm(v) as bf16 or fp32
+int launch_hb16_layernorm1024(float* h, int ldh, const void* delta, int ldd, bool store_h, void* out, int ldo, int rows,
+                              const float* g, const float* b, float eps, bool out_f32, hipStream_t s);
+int launch_hb16_gelu(void* x, long long n, hipStream_t s);                     // exact GELU in place, n % 8 == 0
+int launch_hb16_widen(const void* in, float* out, long long n, hipStream_t s); // bf16 -> fp32, n % 8 == 0
+int launch_hb16_attention(const void* qkv, void* out, int batch, int T, hipStream_t s);
+// fp32 -> bf16 image of n floats (n % 4 == 0), the conversion of the bf16 U-Net handle's weight image (engine.hip)
+int launch_f32_to_bf16(const float* in, void* out, long long n, hipStream_t s);
+
 // dense 3x3 convolution + bias (+ the activation epi.act: LeakyReLU or ReLU) as an implicit GEMM on the ring kernel: no
 // im2col buffer, the taps are gathered by the LDS-DMA loads themselves.  in: [B,H,W,cin] contiguous NHWC,
 // w: [cout][(ky,kx,cin)], out: [B*Ho*Wo, ldc]; stride_h / stride_w apart (AudioConvWenet's conv3 is (1, 2)).

@@ -346,6 +346,17 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restric
   if (i < n) st4(out + i, ld4(in + i));
 }
 
+}  // namespace
+
+int launch_f32_to_bf16(const float* in, void* out, long long n, hipStream_t s) {
+  CASYNC_REQUIRE(in && out && n > 0 && n % 4 == 0, "f32_to_bf16: %lld floats (a positive multiple of 4)", n);
+  const long long blocks = (n / 4 + 255) / 256;
+  CASYNC_REQUIRE(blocks < (1ll << 31), "f32_to_bf16: too many elements");
+  return casync_launch(f32_to_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, static_cast<bf16_t*>(out), n);
+}
+
+namespace {
+
 // Short name of a mangled kernel symbol, as tools/kernel_names.py short() writes it ("pw_gemm_kernel<__bf16, 128, 128, 2, 2>"),
 // and a port of its decoder: the template arguments of this engine's kernels are float / __bf16 / int / bool literals, any
 // other shape keeps the bare name.  (Not a general demangler: binutils' does not know DF16b, the mangling of __bf16.)

@@ -1124,6 +1124,44 @@ int launch_rows_gemm(const float* a, int lda, const float* w, float* c, int ldc,
                       : launch_glds_t<float, 64, 64, 2, 2, 2>(a, lda, w, c, ldc, m, n, k, epi, stream, false);
 }
 
+// The bf16 form (the bf16 HuBERT handle): A, W, C bf16, fp32 accumulation, bias and nothing else in the epilogue.  It launches
+// only ring instances the U-Net's bf16 engine already has, data-parallel tiles only.  The tile is a function of the shape
+// alone: rounds of one tile per CU x (tile area + the bf16 tiles' fixed cost), pick_cfg's bf16 model without its options.
+// lda < K is safe on these kernels: the two-stage loop addresses A through a buffer descriptor of (m-1)*lda + k elements
+// with per-lane offsets row*lda (rows clamped to m-1), the three-stage loop through A + row*lda pointers; neither derives
+// anything else from lda, and W and C never see it.
+int launch_rows_gemm_bf16(const void* a, int lda, const void* w, const float* bias, void* c, int ldc, int m, int n, int k,
+                          hipStream_t stream) {
+  CASYNC_REQUIRE(a && w && c, "rows_gemm_bf16: null pointer");
+  CASYNC_REQUIRE(m > 0 && n > 0 && k > 0, "rows_gemm_bf16: empty problem m=%d n=%d k=%d", m, n, k);
+  CASYNC_REQUIRE(k % 64 == 0 && n % 64 == 0, "rows_gemm_bf16: K=%d and N=%d must be multiples of 64", k, n);
+  CASYNC_REQUIRE(lda > 0 && lda % 8 == 0, "rows_gemm_bf16: lda=%d must be a positive multiple of 8", lda);
+  CASYNC_REQUIRE(ldc >= n && ldc % 8 == 0, "rows_gemm_bf16: ldc=%d must be >= N=%d and a multiple of 8", ldc, n);
+  CASYNC_REQUIRE(((uintptr_t)a % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)c % 16) == 0 && (!bias || (uintptr_t)bias % 16 == 0),
+                 "rows_gemm_bf16: A/W/C/bias must be 16-B aligned");
+  CASYNC_REQUIRE(fits32(m, n, k, lda, DT_BF16), "rows_gemm_bf16: operand larger than 2 GiB");
+  GemmEpilogue e;
+  e.bias = bias;
+  const bf16_t *a16 = static_cast<const bf16_t*>(a), *w16 = static_cast<const bf16_t*>(w);
+  bf16_t* c16 = static_cast<bf16_t*>(c);
+  int best = C64x64;
+  double best_cost = 0;
+  for (const TileCfg& t : kTiles) {
+    if (t.id != C128x128 && t.id != C128x64 && t.id != C64x64) continue;
+    if (n % t.bn) continue;
+    const long long g = (long long)((m + t.bm - 1) / t.bm) * (n / t.bn);
+    const double cost = (double)((g + 255) / 256) * (t.bm * t.bn + 6000.0);
+    if (best_cost == 0 || cost < best_cost) best = t.id, best_cost = cost;
+  }
+  if (best == C128x128) {   // at most one tile per CU: the three-stage ring; more: the two-stage one, two workgroups per CU
+    const long long g = (long long)((m + 127) / 128) * (n / 128);
+    return g <= 256 ? launch_glds_t<bf16_t, 128, 128, 2, 2, 3>(a16, lda, w16, c16, ldc, m, n, k, e, stream, false)
+                    : launch_glds_t<bf16_t, 128, 128, 2, 2, 2>(a16, lda, w16, c16, ldc, m, n, k, e, stream, false);
+  }
+  if (best == C128x64) return launch_glds_t<bf16_t, 128, 64, 2, 2, 2>(a16, lda, w16, c16, ldc, m, n, k, e, stream, false);
+  return launch_glds_t<bf16_t, 64, 64, 2, 2, 2>(a16, lda, w16, c16, ldc, m, n, k, e, stream, false);
+}
+
 // ---------------------------------------------------------------- dense 3x3 as an implicit GEMM
 namespace {
 template <typename T>

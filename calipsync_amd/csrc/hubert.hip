@@ -380,13 +380,43 @@ struct HbWs {
   }
 };
 
+// The bf16 handle's arena: the conv ping-pong and the wide buffer hold bf16, the residual stream h and the feature
+// projection's output x stay fp32; once the positional conv has read x, its bytes hold the bf16 LayerNorm / attention output
+// (x16) and the bf16 delta of the out-proj / FF2 GEMM (d16).  The fp32 output of the feature projection's LayerNorm sits in
+// the wide buffer, which nothing else uses before layer 0.
+struct HbWs16 {
+  bf16_t *a, *b, *big, *x16, *d16;
+  float *h, *x;
+  int64_t bytes;
+  HbWs16(void* base_v, int batch, const HbGeom& G) {
+    char* base = static_cast<char*>(base_v);
+    const int64_t M = batch * G.tokens();
+    const int64_t na = round64(batch * G.t[1] * kConvC), nb = round64(batch * G.t[2] * kConvC), nh = round64(M * kHid);
+    const int64_t nbig = round64(M * kFF);
+    int64_t off = 0;
+    auto take = [&](int64_t n) {
+      char* p = base ? base + off : nullptr;
+      off += n;
+      return p;
+    };
+    a = reinterpret_cast<bf16_t*>(take(na * 2)), b = reinterpret_cast<bf16_t*>(take(nb * 2));
+    h = reinterpret_cast<float*>(take(nh * 4)), x = reinterpret_cast<float*>(take(nh * 4));
+    big = reinterpret_cast<bf16_t*>(take(nbig * 2));
+    x16 = reinterpret_cast<bf16_t*>(x), d16 = x ? x16 + nh : nullptr;
+    bytes = off;
+  }
+};
+
 }  // namespace
 
 struct casync_hubert {
   int device = 0;
   int layers = 0;
+  int dtype = DT_F32;         // DT_BF16: the bf16 precision (hb_run16)
   const float* w = nullptr;   // packed weights (owned or adopted)
   float* owned = nullptr;
+  bf16_t* w16 = nullptr;      // DT_BF16: bf16 image of the packed buffer (owned; the GEMM weight matrices are read from it)
+  const bf16_t* W16(const std::string& n) const { return w16 + hb_layout(layers)->off(n); }
   hipEvent_t ev_fwd = nullptr;   // FwdGate slot
   const float* W(const char* n) const { return w + hb_layout(layers)->off(n); }
   const float* W(const std::string& n) const { return w + hb_layout(layers)->off(n); }
@@ -487,6 +517,95 @@ int hb_run(casync_hubert* H, const float* wave, int batch, int64_t S, float* out
 #undef HB
   return CASYNC_OK;
 }
+
+// The bf16 precision: bf16 GEMM operands and activations, fp32 sums, fp32 residual stream.  The out-proj
+// and FF2 GEMMs write a bf16 delta; h += delta happens inside the LayerNorm that follows (LN2, the next layer's LN1, the
+// final one), so `pending` says whether d16 still has to be added to h.
+int hb_run16(casync_hubert* H, const float* wave, int batch, int64_t S, float* out, void* ws_dev, int64_t ws_bytes, hipStream_t s,
+             int stage, int n_layers) {
+  CASYNC_REQUIRE(H && wave && out && ws_dev, "hubert forward: null pointer");
+  CASYNC_REQUIRE(H->w && H->w16, "hubert forward: weights not loaded");
+  CASYNC_REQUIRE(batch > 0 && batch <= 65535, "hubert forward: batch %d", batch);
+  CASYNC_REQUIRE(S < (1ll << 31), "hubert forward: %lld samples", (long long)S);
+  const HbGeom G(S);
+  CASYNC_REQUIRE(G.tokens() >= 1, "hubert forward: %lld samples give no token (at least 400 are needed)", (long long)S);
+  CASYNC_REQUIRE(stage >= 0 && stage <= 3, "hubert forward: stage %d", stage);
+  CASYNC_REQUIRE(n_layers >= 0 && n_layers <= H->layers, "hubert forward: %d layers of %d", n_layers, H->layers);
+  CASYNC_REQUIRE((uintptr_t)wave % 4 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws_dev % 16 == 0, "hubert forward: alignment");
+  HbWs16 ws(ws_dev, batch, G);
+  if (ws_bytes < ws.bytes) {
+    casync_set_error("hubert forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)ws.bytes);
+    return CASYNC_ERR_STATE;
+  }
+  const int T = (int)G.tokens(), M = batch * T;
+  HbDeviceGuard guard(H->device);
+  CASYNC_CHECK_HIP(guard.err);
+  std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
+  if (int st = casync_gate_enter(H->device, H, &H->ev_fwd, s, &gate_lock)) return st;
+#define HB(call)                       \
+  do {                                 \
+    if (int st__ = (call)) return st__; \
+  } while (0)
+  // feature encoder: conv0 -> a, then ping-pong a <-> b (bf16)
+  HB(launch_hb16_conv0(wave, batch, (int)S, H->W("fe.conv0.w"), H->W("fe.conv0.b"), H->W("fe.ln0.g"), H->W("fe.ln0.b"), ws.a, s));
+  bf16_t *cur = ws.a, *nxt = ws.b;
+  for (int i = 1; i < 7; ++i) {
+    const int tin = (int)G.t[i], tout = (int)G.t[i + 1];
+    const std::string p = "fe.conv" + std::to_string(i), ln = "fe.ln" + std::to_string(i);
+    for (int b = 0; b < batch; ++b)
+      HB(launch_rows_gemm_bf16(cur + (size_t)b * tin * kConvC, kConvS[i] * kConvC, H->W16(p + ".w"), H->W(p + ".b"),
+                               nxt + (size_t)b * tout * kConvC, kConvC, tout, kConvC, kConvK[i] * kConvC, s));
+    HB(launch_hb16_layernorm512(nxt, kConvC, nxt, kConvC, batch * tout, H->W(ln + ".g"), H->W(ln + ".b"), kEps, false, true, s));
+    bf16_t* t = cur;
+    cur = nxt, nxt = t;
+  }
+  if (stage == 1) return launch_hb16_widen(cur, out, (long long)M * kConvC, s);
+  // feature projection and positional conv on the fp32 kernels
+  float* ln32 = reinterpret_cast<float*>(ws.big);
+  HB(launch_hb16_layernorm512(cur, kConvC, ln32, kConvC, M, H->W("fp.ln.g"), H->W("fp.ln.b"), kEps, true, false, s));
+  HB(gemm(ln32, kConvC, H->W("fp.w"), H->W("fp.b"), ws.x, kHid, M, kHid, kConvC, 0, nullptr, s));
+  HB(launch_posconv(ws.x, H->W("pos.w"), H->W("pos.b"), ws.h, batch, T, s));
+  if (stage == 2) {
+    CASYNC_CHECK_HIP(hipMemcpyAsync(out, ws.h, (size_t)M * kHid * 4, hipMemcpyDeviceToDevice, s));
+    return CASYNC_OK;
+  }
+  const int nl = stage == 3 ? n_layers : H->layers;
+  bool pending = false;
+  for (int l = 0; l < nl; ++l) {
+    const std::string p = "layer" + std::to_string(l);
+    HB(launch_hb16_layernorm1024(ws.h, kHid, pending ? ws.d16 : nullptr, kHid, true, ws.x16, kHid, M, H->W(p + ".ln1.g"),
+                                 H->W(p + ".ln1.b"), kEps, false, s));
+    HB(launch_rows_gemm_bf16(ws.x16, kHid, H->W16(p + ".qkv.w"), H->W(p + ".qkv.b"), ws.big, 3 * kHid, M, 3 * kHid, kHid, s));
+    HB(launch_hb16_attention(ws.big, ws.x16, batch, T, s));
+    HB(launch_rows_gemm_bf16(ws.x16, kHid, H->W16(p + ".o.w"), H->W(p + ".o.b"), ws.d16, kHid, M, kHid, kHid, s));
+    HB(launch_hb16_layernorm1024(ws.h, kHid, ws.d16, kHid, true, ws.x16, kHid, M, H->W(p + ".ln2.g"), H->W(p + ".ln2.b"), kEps,
+                                 false, s));
+    HB(launch_rows_gemm_bf16(ws.x16, kHid, H->W16(p + ".ff1.w"), H->W(p + ".ff1.b"), ws.big, kFF, M, kFF, kHid, s));
+    HB(launch_hb16_gelu(ws.big, (long long)M * kFF, s));
+    HB(launch_rows_gemm_bf16(ws.big, kFF, H->W16(p + ".ff2.w"), H->W(p + ".ff2.b"), ws.d16, kHid, M, kHid, kFF, s));
+    pending = true;
+  }
+  if (stage == 3) {
+    // the tap includes the pending delta: one more pass of the LayerNorm kernel folds it into h (its bf16 output is unused)
+    if (pending)
+      HB(launch_hb16_layernorm1024(ws.h, kHid, ws.d16, kHid, true, ws.x16, kHid, M, H->W("enc.ln.g"), H->W("enc.ln.b"), kEps, false, s));
+    CASYNC_CHECK_HIP(hipMemcpyAsync(out, ws.h, (size_t)M * kHid * 4, hipMemcpyDeviceToDevice, s));
+    return CASYNC_OK;
+  }
+  HB(launch_hb16_layernorm1024(ws.h, kHid, pending ? ws.d16 : nullptr, kHid, false, out, kHid, M, H->W("enc.ln.g"),
+                               H->W("enc.ln.b"), kEps, true, s));
+#undef HB
+  return CASYNC_OK;
+}
+
+// bf16 image of the packed buffer, made once at weight load (not on the forward path)
+int hb_refresh_w16(casync_hubert* h, int64_t n) {
+  if (h->dtype != DT_BF16) return CASYNC_OK;
+  if (!h->w16) CASYNC_CHECK_HIP(hipMalloc((void**)&h->w16, n * sizeof(bf16_t)));
+  if (int st = launch_f32_to_bf16(h->w, h->w16, (long long)n, 0)) return st;
+  CASYNC_CHECK_HIP(hipDeviceSynchronize());
+  return CASYNC_OK;
+}
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
@@ -519,9 +638,21 @@ int64_t casync_hubert_workspace_bytes(int batch, int64_t samples) {
   return G.tokens() > 0 ? HbWs(nullptr, batch, G).floats * 4 : 0;
 }
 
+int64_t casync_hubert_workspace_bytes_h(casync_hubert_handle h, int batch, int64_t samples) {
+  if (!h || batch <= 0 || samples <= 0) return 0;
+  const HbGeom G(samples);
+  if (G.tokens() <= 0) return 0;
+  return h->dtype == DT_BF16 ? HbWs16(nullptr, batch, G).bytes : HbWs(nullptr, batch, G).floats * 4;
+}
+
 int casync_hubert_create(int device_id, int layers, casync_hubert_handle* out) {
+  return casync_hubert_create_ex(device_id, layers, DT_F32, out);
+}
+
+int casync_hubert_create_ex(int device_id, int layers, int dtype, casync_hubert_handle* out) {
   CASYNC_REQUIRE(out, "hubert_create: null out");
   *out = nullptr;
+  CASYNC_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "hubert_create: dtype %d (0 fp32, 1 bf16)", dtype);
   CASYNC_REQUIRE(layers >= 1 && layers <= kMaxLayers, "hubert_create: %d layers (1..%d)", layers, kMaxLayers);
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
@@ -538,6 +669,7 @@ int casync_hubert_create(int device_id, int layers, casync_hubert_handle* out) {
   casync_hubert* h = new casync_hubert();
   h->device = device_id;
   h->layers = layers;
+  h->dtype = dtype;
   *out = h;
   return CASYNC_OK;
 }
@@ -547,6 +679,7 @@ void casync_hubert_destroy(casync_hubert_handle h) {
   HbDeviceGuard guard(h->device);
   casync_gate_forget(h->device, h, &h->ev_fwd);
   if (h->owned) (void)hipFree(h->owned);
+  if (h->w16) (void)hipFree(h->w16);
   delete h;
 }
 
@@ -559,7 +692,7 @@ int casync_hubert_load_weights_host(casync_hubert_handle h, const float* packed,
   if (!h->owned) CASYNC_CHECK_HIP(hipMalloc((void**)&h->owned, n_floats * sizeof(float)));
   CASYNC_CHECK_HIP(hipMemcpy(h->owned, packed, n_floats * sizeof(float), hipMemcpyHostToDevice));
   h->w = h->owned;
-  return CASYNC_OK;
+  return hb_refresh_w16(h, n_floats);
 }
 
 int casync_hubert_load_weights_device(casync_hubert_handle h, const float* packed_dev, int64_t n_floats) {
@@ -569,17 +702,22 @@ int casync_hubert_load_weights_device(casync_hubert_handle h, const float* packe
                  (long long)total);
   CASYNC_REQUIRE(((uintptr_t)packed_dev % 256) == 0, "hubert_load_weights_device: buffer must be 256-B aligned");
   h->w = packed_dev;
-  return CASYNC_OK;
+  HbDeviceGuard guard(h->device);
+  CASYNC_CHECK_HIP(guard.err);
+  return hb_refresh_w16(h, n_floats);
 }
 
 int casync_hubert_forward(casync_hubert_handle h, const float* wave_dev, int batch, int64_t samples, float* out_dev,
                           void* workspace_dev, int64_t workspace_bytes, casync_stream stream) {
+  if (h && h->dtype == DT_BF16) return hb_run16(h, wave_dev, batch, samples, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream, 0, 0);
   return hb_run(h, wave_dev, batch, samples, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream, 0, 0);
 }
 
 int casync_hubert_forward_tap(casync_hubert_handle h, const float* wave_dev, int batch, int64_t samples, int stage, int n_layers,
                               float* out_dev, void* workspace_dev, int64_t workspace_bytes, casync_stream stream) {
   CASYNC_REQUIRE(stage >= 1 && stage <= 3, "hubert_forward_tap: stage %d (1 conv stack, 2 layer-0 input, 3 after n layers)", stage);
+  if (h && h->dtype == DT_BF16)
+    return hb_run16(h, wave_dev, batch, samples, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream, stage, n_layers);
   return hb_run(h, wave_dev, batch, samples, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream, stage, n_layers);
 }
 

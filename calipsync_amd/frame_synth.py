@@ -248,12 +248,15 @@ class VideoStreamManager:
 
     ``hubert_path`` is what the reference takes, a HuBERT checkpoint directory: the extractor
     (``calipsync_amd.hubert.HubertExtractor``, HubertModel on the HIP engine) is built from it on the first audio file
-    that is not a ``.npy``.  It may also be a callable ``audio_path -> [T,2,1024] array``, and it is not used when
+    that is not a ``.npy``, in ``hubert_precision`` ("fp32", the default, or "bf16").  It may also be a callable ``audio_path -> [T,2,1024] array``, and it is not used when
     ``audio_path`` is itself a ``.npy`` of features.  The mp4 writer / ffmpeg mux (inference.py:88-110) is used when cv2 / ffmpeg exist; otherwise
     the frames are written as a Motion-JPEG ``.avi`` with Pillow (``mjpeg_avi.py``; no audio track)."""
 
     def __init__(self, data_dir: str, unet_checkpoint: Optional[str], hubert_path=None, device: str = "cuda:0",
-                 batch_size: int = 8, output_sample_rate: int = 24000, **synth_kwargs):
+                 batch_size: int = 8, output_sample_rate: int = 24000, hubert_precision: str = "fp32", **synth_kwargs):
+        from .hubert import check_precision
+        check_precision(hubert_precision)   # ValueError before anything touches the device
+        self._hubert_precision = hubert_precision
         self.synthesizer = FrameSynthesizer(unet_checkpoint=unet_checkpoint, data_dir=data_dir, device=device,
                                             batch_size=batch_size, **synth_kwargs)
         self.hubert_extractor = hubert_path if callable(hubert_path) else None
@@ -269,7 +272,8 @@ class VideoStreamManager:
         else:
             if self.hubert_extractor is None and self._hubert_dir is not None:   # built on first use
                 from .hubert import HubertExtractor
-                self.hubert_extractor = HubertExtractor(os.fspath(self._hubert_dir), self._device).extract_from_file
+                self.hubert_extractor = HubertExtractor(os.fspath(self._hubert_dir), self._device,
+                                                        self._hubert_precision).extract_from_file
             if self.hubert_extractor is None:
                 raise RuntimeError("no HuBERT extractor configured: pass pre-extracted features (.npy), a HuBERT checkpoint "
                                    "directory or a callable")

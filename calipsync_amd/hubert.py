@@ -181,24 +181,38 @@ def tokens(samples: int) -> int:
     return t
 
 
-class HubertEngine:
-    """HubertModel(...).last_hidden_state on the HIP engine (fp32): forward(wave [B,S] on the device) -> [B,T,1024]."""
+PRECISIONS = {"fp32": 0, "bf16": 1}   # -> the dtype of casync_hubert_create_ex
 
-    def __init__(self, sd: Dict[str, torch.Tensor], layers: int, device: str = "cuda:0"):
+
+def check_precision(precision: str) -> int:
+    """-> engine dtype; ValueError for anything but "fp32" / "bf16" (before any device call)."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"HuBERT precision {precision!r}; the engine has {sorted(PRECISIONS)}")
+    return PRECISIONS[precision]
+
+
+class HubertEngine:
+    """HubertModel(...).last_hidden_state on the HIP engine: forward(wave [B,S] on the device) -> [B,T,1024], fp32 in and
+    out.  precision "bf16" runs the GEMMs, the attention and the activations between them in bf16 (fp32 sums, fp32 residual
+    stream: DESIGN section 8b); "fp32" is the default."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], layers: int, device: str = "cuda:0", precision: str = "fp32"):
         import ctypes as C
         from . import _lib
+        dtype = check_precision(precision)
         self._lib = _lib.load()
         self.device = torch.device(device)
         self.layers = layers
+        self.precision = precision
         h = C.c_void_p()
-        _lib.check(self._lib.casync_hubert_create(self.device.index or 0, layers, C.byref(h)), "casync_hubert_create")
+        _lib.check(self._lib.casync_hubert_create_ex(self.device.index or 0, layers, dtype, C.byref(h)), "casync_hubert_create_ex")
         self._h = h
         buf = pack(sd, layers)
         _lib.check(self._lib.casync_hubert_load_weights_host(self._h, buf.ctypes.data, buf.size), "casync_hubert_load_weights_host")
         self._ws: Optional[torch.Tensor] = None
 
     def _workspace(self, batch: int, samples: int) -> torch.Tensor:
-        need = self._lib.casync_hubert_workspace_bytes(batch, samples)
+        need = self._lib.casync_hubert_workspace_bytes_h(self._h, batch, samples)
         if need <= 0:
             raise ValueError(f"HuBERT engine: {samples} samples give no token (at least {KERNEL} are needed)")
         if self._ws is None or self._ws.numel() * 4 < need:
@@ -321,10 +335,11 @@ def load_audio_16k(path: str) -> np.ndarray:
 class HubertExtractor:
     """The reference's HubertExtractor(hubert_path, device) on the HIP engine."""
 
-    def __init__(self, hubert_path: str, device: str = "cuda:0"):
+    def __init__(self, hubert_path: str, device: str = "cuda:0", precision: str = "fp32"):
+        check_precision(precision)
         self.device = device
         cfg, sd, self.do_normalize = load_checkpoint(hubert_path)
-        self.model = HubertEngine(sd, cfg["num_hidden_layers"], device)
+        self.model = HubertEngine(sd, cfg["num_hidden_layers"], device, precision)
 
     def _encode(self, chunks: List[torch.Tensor]) -> List[torch.Tensor]:
         if len({c.shape[1] for c in chunks}) == 1:

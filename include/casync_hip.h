@@ -43,7 +43,7 @@ enum {
 /* ---- introspection (callable without a GPU) --------------------------- */
 /* Bumped on every change of a prototype, struct layout or the packed-weight layout; the ctypes
  * host (calipsync_amd/_lib.py) refuses a library whose version differs from the one it binds.   */
-#define CASYNC_ABI_VERSION 9   /* 9: casync_debug_launch_log / casync_debug_launched, casync_op_pw_dw_rect */
+#define CASYNC_ABI_VERSION 10  /* 10: bf16 HuBERT handle (casync_hubert_create_ex, casync_hubert_workspace_bytes_h, casync_op_hubert16_*) */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -356,6 +356,33 @@ int  casync_op_hubert_posconv(const float* x, const float* w_packed, const float
 int  casync_op_hubert_attention(const float* qkv, float* out, int batch, int T, casync_stream stream);
 int  casync_op_rows_gemm(const float* a, int lda, const float* w, const float* bias, float* c, int ldc, int m, int n,
                          int k, int act, const float* post_res, int ld_post, casync_stream stream);
+
+/* ---- HuBERT, bf16 precision (ABI 10) ------------------------------------- */
+/* dtype 0 = fp32 (casync_hubert_create), 1 = bf16: bf16 GEMM operands (from a bf16 image of the packed
+ * weights made at load), bf16 activations between the kernels, fp32 sums and an fp32 residual stream;
+ * conv0, feature projection and positional conv keep their fp32 arithmetic.  Waveform in and
+ * last_hidden_state (and the debug taps) out stay fp32; forward / forward_tap serve both.          */
+int  casync_hubert_create_ex(int device_id, int layers, int dtype, casync_hubert_handle* out);
+/* workspace of a forward on THIS handle (the bf16 arena differs from the fp32 one)                */
+int64_t casync_hubert_workspace_bytes_h(casync_hubert_handle h, int batch, int64_t samples);
+/* single operators of the bf16 handle (tests); pointers declared void* are bf16.  conv0 -> bf16;
+ * layernorm512: bf16 in, bf16 out with GELU (out_f32 0, gelu 1) or fp32 out (out_f32 1, gelu 0);
+ * layernorm1024: v = h (+ delta when given; h = v when store_h), out = LayerNorm(v) as bf16 or fp32;
+ * gelu: exact GELU in place over n bf16 (n % 8 == 0); widen: bf16 -> fp32; attention from the fused bf16
+ * [batch*T, 3072] q|k|v buffer -> bf16 [batch*T, 1024]; rows_gemm_bf16: C = A W^T + bias, A rows may
+ * overlap (lda < K), K % 64 == 0, N % 64 == 0.                                                     */
+int  casync_op_hubert16_conv0(const float* wave, int batch, int samples, const float* w, const float* b, const float* g,
+                              const float* be, void* out, casync_stream stream);
+int  casync_op_hubert16_layernorm512(const void* in, int ldi, void* out, int ldo, int rows, const float* g, const float* b,
+                                     float eps, int out_f32, int gelu, casync_stream stream);
+int  casync_op_hubert16_layernorm1024(float* h, int ldh, const void* delta, int ldd, int store_h, void* out, int ldo,
+                                      int rows, const float* g, const float* b, float eps, int out_f32,
+                                      casync_stream stream);
+int  casync_op_hubert16_gelu(void* x, int64_t n, casync_stream stream);
+int  casync_op_hubert16_widen(const void* in, float* out, int64_t n, casync_stream stream);
+int  casync_op_hubert16_attention(const void* qkv, void* out, int batch, int T, casync_stream stream);
+int  casync_op_rows_gemm_bf16(const void* a, int lda, const void* w, const float* bias, void* c, int ldc, int m, int n,
+                              int k, casync_stream stream);
 
 #ifdef __cplusplus
 }

@@ -1,12 +1,15 @@
-"""HuBERT-large feature extraction throughput on one MI355X (fp32): the HIP engine against the same model restated in
-torch (tests/hubert_ref.py) on the same GPU, in one process.
+"""HuBERT-large feature extraction throughput on one MI355X: the HIP engine (fp32, bf16 or both) against the same model
+restated in torch (tests/hubert_ref.py) on the same GPU, in one process.
 
-    python tools/hubert_bench.py [--layers 24] [--steps 5] [--warmup 2]
+    python tools/hubert_bench.py [--layers 24] [--steps 5] [--warmup 2] [--precision fp32|bf16|both]
 
 Two shapes: one full chunk (B=1, 320080 samples = 1000 tokens) and a 60-s clip (its three full chunks in one batched
 forward, as HubertExtractor runs them).  One JSON line per shape: audio-seconds/s, tokens/s, achieved TFLOP/s on the
 FLOPs counted from shapes (flops() below) and its fraction of the 157.3 TFLOP/s fp32 matrix roof, for the engine and
-the torch baseline.  Per-kernel times: run this under rocprofv3 --kernel-trace --stats.
+the torch baseline.  --precision bf16 / both: the bf16 handle's line is measured against the 2.5 PFLOP/s bf16 matrix
+roof and carries `speedup_vs_fp32`, its time against the fp32 engine's in the same process (with `both` the two engines'
+timed steps alternate; with `bf16` alone the fp32 engine is timed too, only its line is not printed).  Per-kernel times: run
+this under rocprofv3 --kernel-trace --stats.
 """
 from __future__ import annotations
 
@@ -23,6 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 
 ROOF_TF = 157.3   # MI355X fp32 matrix peak, TFLOP/s
+ROOF_TF_BF16 = 2500.0   # ... and the bf16 one
 
 
 def flops(samples: int, layers: int) -> float:
@@ -51,6 +55,23 @@ def timeit(fn, steps: int, warmup: int) -> float:
     return (time.perf_counter() - t0) / steps
 
 
+def timeit_alternating(fns, steps: int, warmup: int):
+    """Per-call seconds of each of `fns`, their timed steps taken in turn (a, b, a, b, ...) so that clocks and thermals
+    treat them alike; each call is timed between two device synchronisations."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    tot = [0.0] * len(fns)
+    for _ in range(steps):
+        for i, fn in enumerate(fns):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            tot[i] += time.perf_counter() - t0
+    return [t / steps for t in tot]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=24)
@@ -58,11 +79,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-baseline", action="store_true")
     ap.add_argument("--shapes", default="chunk,clip60s", help="comma-separated subset of chunk,clip60s")
+    ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16", "both"))
     a = ap.parse_args()
     import hubert_ref
     from calipsync_amd import hubert
     sd = hubert_ref.recipe_state_dict(a.layers)
     eng = hubert.HubertEngine(sd, a.layers)
+    eng16 = hubert.HubertEngine(sd, a.layers, precision="bf16") if a.precision != "fp32" else None
     # the baseline: the restatement with its weights already on the GPU
     P = {k: torch.from_numpy(v).cuda() for k, v in hubert.packed_tensors(sd, a.layers).items()}
     hubert_ref._t = lambda x: x if isinstance(x, torch.Tensor) else torch.as_tensor(x)
@@ -78,8 +101,17 @@ def main():
         f = b * flops(hubert.CHUNK, a.layers)
         audio_s = b * hubert.CLIP / 16000.0
         tok = b * hubert.tokens(hubert.CHUNK)
-        t_eng = timeit(lambda: eng(w), a.steps, a.warmup)
-        res = {"shape": name, "batch": b, "samples": hubert.CHUNK, "layers": a.layers, "gflop": round(f / 1e9, 1),
+        if eng16 is not None:
+            t_eng, t16 = timeit_alternating([lambda: eng(w), lambda: eng16(w)], a.steps, a.warmup)
+            print(json.dumps({"shape": name, "precision": "bf16", "batch": b, "samples": hubert.CHUNK, "layers": a.layers,
+                              "gflop": round(f / 1e9, 1), "engine_ms": t16 * 1e3, "audio_s_per_s": audio_s / t16,
+                              "tokens_per_s": tok / t16, "tflops": f / t16 / 1e12, "roof_frac": f / t16 / 1e12 / ROOF_TF_BF16,
+                              "fp32_engine_ms": t_eng * 1e3, "speedup_vs_fp32": t_eng / t16}), flush=True)
+            if a.precision == "bf16":
+                continue
+        else:
+            t_eng = timeit(lambda: eng(w), a.steps, a.warmup)
+        res = {"shape": name, "precision": "fp32", "batch": b, "samples": hubert.CHUNK, "layers": a.layers, "gflop": round(f / 1e9, 1),
                "engine_ms": t_eng * 1e3, "audio_s_per_s": audio_s / t_eng, "tokens_per_s": tok / t_eng,
                "tflops": f / t_eng / 1e12, "roof_frac": f / t_eng / 1e12 / ROOF_TF}
         if not a.no_baseline:
