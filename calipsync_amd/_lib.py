@@ -133,10 +133,32 @@ _PROTOS = {
     "casync_op_hubert16_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_rows_gemm_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p]),
+    # PFLD_GhostOne landmark network (ABI 11)
+    "casync_pfld_packed_count": (C.c_int, []),
+    "casync_pfld_packed_name": (C.c_char_p, [C.c_int]),
+    "casync_pfld_packed_offset": (c_i64, [C.c_int]),
+    "casync_pfld_packed_size": (c_i64, [C.c_int]),
+    "casync_pfld_packed_total": (c_i64, []),
+    "casync_pfld_workspace_bytes": (c_i64, [C.c_int]),
+    "casync_pfld_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "casync_pfld_destroy": (None, [C.c_void_p]),
+    "casync_pfld_load_weights_host": (C.c_int, [C.c_void_p, C.c_void_p, c_i64]),
+    "casync_pfld_load_weights_device": (C.c_int, [C.c_void_p, c_f32p, c_i64]),
+    "casync_pfld_forward": (C.c_int, [C.c_void_p, c_f32p, C.c_int, c_f32p, C.c_void_p, c_i64, C.c_void_p]),
+    "casync_pfld_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_f32p, C.c_void_p, c_i64, C.c_void_p]),
+    "casync_pfld_forward_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p, c_i64,
+                                          C.c_void_p]),
+    "casync_op_pfld_stem": (C.c_int, [C.c_void_p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int,
+                                      C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_pfld_ghost": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_pfld_dw_s2": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_pfld_head": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), c_f32p, c_f32p, c_f32p,
+                                      c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)
-ABI_VERSION = 10         # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
+ABI_VERSION = 11         # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
 
 
 def lib_path() -> str:
@@ -226,3 +248,11 @@ def hubert_layout(layers: int):
     items = [(lib.casync_hubert_packed_name(layers, i).decode(), lib.casync_hubert_packed_offset(layers, i),
               lib.casync_hubert_packed_size(layers, i)) for i in range(n)]
     return items, lib.casync_hubert_packed_total(layers)
+
+
+def pfld_layout():
+    """[(name, offset, size)] in floats, and the total, of the PFLD landmark engine's packed buffer."""
+    lib = load()
+    items = [(lib.casync_pfld_packed_name(i).decode(), lib.casync_pfld_packed_offset(i), lib.casync_pfld_packed_size(i))
+             for i in range(lib.casync_pfld_packed_count())]
+    return items, lib.casync_pfld_packed_total()

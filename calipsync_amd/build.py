@@ -16,6 +16,9 @@ LIB_PATH = os.path.join(LIB_DIR, "libcasync_hip.so")
 # tests/kernel_ledger.py stays the ledger of lib/obj/) and linked into the same library.
 OBJ_DIR_HB16 = os.path.join(LIB_DIR, "obj_hb16")
 SOURCES_HB16 = ["hubert_bf16.hip"]
+# Kernels of the PFLD landmark handle (tests/kernel_ledger_lmk.py is their ledger), the same way.
+OBJ_DIR_LMK = os.path.join(LIB_DIR, "obj_lmk")
+SOURCES_LMK = ["landmark.hip"]
 SOURCES = ["runtime.hip", "gemm.hip", "ops.hip", "ir_fused.hip", "pw_dw.hip", "pw_dw_bf16.hip", "attention.hip", "attention_bf16.hip", "frame_ops.hip", "hubert.hip", "engine.hip"]
 HEADERS = ["common.h", "ir_common.h", "pw_dw_common.h", os.path.join("..", "..", "include", "casync_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
@@ -42,7 +45,7 @@ def _header_paths():
 def is_stale() -> bool:
     """True when the library is missing or older than any of its sources / headers.  A deployment that ships the
     library without csrc/ has nothing to be stale against: missing sources count as "not newer"."""
-    return _newer(LIB_PATH, [os.path.join(CSRC, s) for s in SOURCES + SOURCES_HB16] + _header_paths())
+    return _newer(LIB_PATH, [os.path.join(CSRC, s) for s in SOURCES + SOURCES_HB16 + SOURCES_LMK] + _header_paths())
 
 
 def source_hash() -> str:
@@ -51,7 +54,7 @@ def source_hash() -> str:
     version of the kernels are never quoted for another."""
     import hashlib
     h = hashlib.sha256()
-    for path in [os.path.join(CSRC, s) for s in SOURCES + SOURCES_HB16] + _header_paths():
+    for path in [os.path.join(CSRC, s) for s in SOURCES + SOURCES_HB16 + SOURCES_LMK] + _header_paths():
         h.update(os.path.basename(path).encode() + b"\0")
         with open(path, "rb") as f:
             h.update(f.read())
@@ -102,6 +105,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return LIB_PATH
     os.makedirs(OBJ_DIR, exist_ok=True)
     os.makedirs(OBJ_DIR_HB16, exist_ok=True)
+    os.makedirs(OBJ_DIR_LMK, exist_ok=True)
     # One builder at a time: bench.py --gpus N, torchrun ranks and pytest workers can all reach load() -> build() at
     # once after a checkout; without the lock they compile into the same obj/*.o and link over a library another rank
     # is dlopen-ing.  The link goes to a temporary name and is renamed into place (atomic on one filesystem).
@@ -120,7 +124,8 @@ def _build_locked(force: bool, verbose: bool) -> str:
     hipcc = _hipcc()
 
     def compile_one(src: str):
-        obj = os.path.join(OBJ_DIR_HB16 if src in SOURCES_HB16 else OBJ_DIR, src.replace(".hip", ".o"))
+        obj_dir = OBJ_DIR_HB16 if src in SOURCES_HB16 else OBJ_DIR_LMK if src in SOURCES_LMK else OBJ_DIR
+        obj = os.path.join(obj_dir, src.replace(".hip", ".o"))
         path = os.path.join(CSRC, src)
         if not force and not _newer(obj, [path] + _header_paths()):
             return obj, None
@@ -130,7 +135,7 @@ def _build_locked(force: bool, verbose: bool) -> str:
         res = subprocess.run(cmd, capture_output=True, text=True)
         return obj, (res.stdout + res.stderr if res.returncode else None)
 
-    sources = SOURCES + SOURCES_HB16
+    sources = SOURCES + SOURCES_HB16 + SOURCES_LMK
     with ThreadPoolExecutor(max_workers=min(len(sources), os.cpu_count() or 4)) as pool:
         results = list(pool.map(compile_one, sources))
     errors = [err for _, err in results if err]

@@ -150,3 +150,47 @@ def make_inputs_range(start: int, count: int, seed: int = INPUT_SEED):
         x[i] = uniform01(seed, 0x1000000 + b, x[i].size).astype(np.float32).reshape(x[i].shape)
         a[i] = normal01(seed, 0x2000000 + b, a[i].size).astype(np.float32).reshape(a[i].shape)
     return x, a
+
+
+# ---- PFLD_GhostOne landmark network (calipsync_amd/landmarks.py) ----------------------------------------------------
+PFLD_WEIGHT_SEED = 0x9F1D
+PFLD_INPUT_SEED = 0x9F1E
+
+
+def make_pfld_state_dict(seed: int = PFLD_WEIGHT_SEED) -> Dict[str, np.ndarray]:
+    """The 2090 entries of a train-form ``PFLD_GhostOne(0.5, 192, 110)`` state dict.  Each MobileOneBlock sums six conv
+    branches (+ scale + skip), so BatchNorm gammas near 1 take the activations to 5e4 within the network; this recipe keeps
+    every stage at order 1: conv weights U(+-1/sqrt(fan_in)) with fan_in = (cin/groups) k^2, plain conv biases
+    U(+-1/sqrt(256)), BN running_var U(0.75, 1.25), running_mean and bias N(0, 0.1^2), BN weight 0.4 U(0.75, 1.25) with a
+    negative sign with probability 1/4."""
+    from . import landmarks
+    sd: Dict[str, np.ndarray] = {}
+    for key, shape in landmarks.manifest("train"):
+        n = int(np.prod(shape)) if shape else 1
+        s = _stream("pfld." + key)
+        leaf = key.rsplit(".", 1)[1]
+        is_bn = ".bn." in key or ".rbr_skip." in key
+        if leaf == "num_batches_tracked":
+            sd[key] = np.zeros(shape, dtype=np.int64)
+            continue
+        if is_bn and leaf == "running_var":
+            v = 0.75 + 0.5 * uniform01(seed, s, n)
+        elif is_bn and leaf in ("running_mean", "bias"):
+            v = normal01(seed, s, n) * 0.1
+        elif is_bn and leaf == "weight":
+            sign = np.where(uniform01(seed, s, n, lane=3) < 0.25, -1.0, 1.0)
+            v = 0.4 * (0.75 + 0.5 * uniform01(seed, s, n)) * sign
+        elif leaf == "weight":
+            v = (2.0 * uniform01(seed, s, n) - 1.0) / np.sqrt(int(np.prod(shape[1:])))
+        else:                                   # conv_out.bias, localization.*.bias
+            v = (2.0 * uniform01(seed, s, n) - 1.0) / np.sqrt(256.0)
+        sd[key] = v.astype(np.float32).reshape(shape)
+    return sd
+
+
+def make_pfld_inputs(batch: int, seed: int = PFLD_INPUT_SEED) -> np.ndarray:
+    """Synthetic face crops as cv2.resize hands them over: uint8 BGR [B,192,192,3]; crop b depends only on (seed, b)."""
+    x = np.empty((batch, 192, 192, 3), dtype=np.uint8)
+    for b in range(batch):
+        x[b] = np.floor(uniform01(seed, 0x3000000 + b, x[b].size) * 256.0).astype(np.uint8).reshape(x[b].shape)
+    return x

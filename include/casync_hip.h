@@ -43,7 +43,7 @@ enum {
 /* ---- introspection (callable without a GPU) --------------------------- */
 /* Bumped on every change of a prototype, struct layout or the packed-weight layout; the ctypes
  * host (calipsync_amd/_lib.py) refuses a library whose version differs from the one it binds.   */
-#define CASYNC_ABI_VERSION 10  /* 10: bf16 HuBERT handle (casync_hubert_create_ex, casync_hubert_workspace_bytes_h, casync_op_hubert16_*) */
+#define CASYNC_ABI_VERSION 11  /* 11: PFLD_GhostOne landmark handle (casync_pfld_*, casync_op_pfld_*) */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -383,6 +383,64 @@ int  casync_op_hubert16_widen(const void* in, float* out, int64_t n, casync_stre
 int  casync_op_hubert16_attention(const void* qkv, void* out, int batch, int T, casync_stream stream);
 int  casync_op_rows_gemm_bf16(const void* a, int lda, const void* w, const float* bias, void* c, int ldc, int m, int n,
                               int k, casync_stream stream);
+
+/* ---- PFLD_GhostOne landmark network (ABI 11) ------------------------------ */
+/* PFLD_GhostOne(width_factor=0.5, input_size=192, landmark_number=110), the network behind the reference's
+ * LipDetector (utils/lip_detector/lip_detector.py:23-26,100-106; tools/pfld_mobileone.py:12-133), fp32, with every
+ * MobileOneBlock folded on the host to one conv + bias (base_module.py:329-400).  Its own handle, packed layout and
+ * workspace; forwards take the same cross-handle gate as casync_forward and casync_hubert_forward.               */
+typedef struct casync_pfld* casync_pfld_handle;
+/* Packed layout (floats; tensors start on 256-B boundaries): conv1.w [(ky,kx,ci)=27][32], conv2.w [9][32]; per
+ * bottleneck <b> in conv3_1 .. conv6 and ghost module g1 / g2: <b>.g?.pw.w [ceil16(cin)][np] and .pw.b [np],
+ * .dw.w [9][np], .dw.b [np] with np = ceil16(cout/2), zero-padded (the fp32 MFMA granule); <b>.dw.w [9][hid] of
+ * the stride-2 bottlenecks; conv7.w [(ky,kx,ci)=72][16]; conv8.w [(y,x,c)=2304][64]; conv_out.w [256][220].   */
+int         casync_pfld_packed_count(void);
+const char* casync_pfld_packed_name(int i);
+int64_t     casync_pfld_packed_offset(int i);
+int64_t     casync_pfld_packed_size(int i);
+int64_t     casync_pfld_packed_total(void);
+int64_t     casync_pfld_workspace_bytes(int batch);           /* 0 for a batch outside 1..4096 */
+/* Replaces PFLDInference().cuda() / load_state_dict / eval() (lip_detector.py:23-26). */
+int  casync_pfld_create(int device_id, casync_pfld_handle* out);
+void casync_pfld_destroy(casync_pfld_handle h);
+int  casync_pfld_load_weights_host(casync_pfld_handle h, const float* packed, int64_t n_floats);
+int  casync_pfld_load_weights_device(casync_pfld_handle h, const float* packed_dev, int64_t n_floats);
+/* Replaces self.pfld_backbone(input_img) (lip_detector.py:105; pfld_mobileone.py:99-133): x_dev [B,3,192,192] NCHW
+ * fp32 in [0,1] -> out_dev [B,220].  _u8 takes what cv2.resize hands over, [B,192,192,3] uint8 BGR HWC, and divides
+ * by 255 itself (lip_detector.py:100-102): bit-equal to casync_pfld_forward on float(u8) / 255.  Enqueues on
+ * `stream`, no host synchronisation, no allocation, no atomics: frame i of a batch has the bits of that frame alone. */
+int  casync_pfld_forward(casync_pfld_handle h, const float* x_dev, int batch, float* out_dev, void* workspace_dev,
+                         int64_t workspace_bytes, casync_stream stream);
+int  casync_pfld_forward_u8(casync_pfld_handle h, const uint8_t* crops_dev, int batch, float* out_dev,
+                            void* workspace_dev, int64_t workspace_bytes, casync_stream stream);
+/* Debug: the same forward stopped at `stage`, that intermediate written NHWC to out_dev: 0 conv1, 1 conv2 [B,96,96,32],
+ * 2-4 conv3_1..3 [B,48,48,40], 5-7 conv4_1..3 [B,24,24,48], 8-11 conv5_1..4 [B,12,12,72], 12 conv6 [B,12,12,8],
+ * 13 conv7 [B,12,12,16], 14 conv8 (x5) [B,64], 15 conv_out [B,220] (pfld_mobileone.py:100-130).  in_dev is float NCHW, or
+ * uint8 HWC when input_u8.                                                                                            */
+int  casync_pfld_forward_tap(casync_pfld_handle h, const void* in_dev, int input_u8, int batch, int stage, float* out_dev,
+                             void* workspace_dev, int64_t workspace_bytes, casync_stream stream);
+/* single operators (tests), one per kernel family, all NHWC fp32:
+ * stem: conv1 (dense 3x3 s2 p1, 3 -> 32, ReLU) + conv2 (depthwise 3x3, ReLU) of an h x w input (pfld_mobileone.py:
+ *   100-101) -> out [B,ho,wo,32], ho = (h-1)/2+1; sums [B][tiles of 8x8][32] = per-tile channel sums of out;
+ *   conv1_out (optional) [B,ho,wo,32].
+ * ghost: GhostOneModule.forward (base_module.py:117-121) with folded blocks: out[.., 0:half] = act(pw(in)),
+ *   out[.., half:2 half] = act(dw3x3(out[.., 0:half])), act = ReLU or none; in [B,h,w,ld_in], cin % 4 == 0,
+ *   half <= 128; sums (optional, half <= 64) [B][tiles of 6x6][2 half].
+ * dw_s2: the linear stride-2 depthwise 3x3, pad 1, of GhostOneBottleneck (base_module.py:136-145): in [B,h,w,c]
+ *   -> out [B,(h-1)/2+1,(w-1)/2+1,ld_out], w [9][c].
+ * head: AvgPool2d of the four stages from their per-tile sums (sums[j]: [B][tiles[j]][32|40|48|72], mean = sum /
+ *   counts[j]), conv7, conv8, cat, conv_out (pfld_mobileone.py:102,108,114,121,125-131): x6 [B,12,12,8] -> out
+ *   [B, ld_out >= 220].  sums / tiles / counts are HOST arrays of four.                                        */
+int  casync_op_pfld_stem(const void* x, int input_u8, const float* w1, const float* b1, const float* w2, const float* b2,
+                         float* out, float* sums, float* conv1_out, int batch, int h, int w, casync_stream stream);
+int  casync_op_pfld_ghost(const float* in, int ld_in, const float* wp, const float* bp, const float* wd, const float* bd,
+                          float* out, int ld_out, float* sums, int batch, int h, int w, int cin, int half, int act,
+                          casync_stream stream);
+int  casync_op_pfld_dw_s2(const float* in, const float* w, const float* bias, float* out, int ld_out, int batch, int h,
+                          int w_, int c, casync_stream stream);
+int  casync_op_pfld_head(const float* const* sums, const int* tiles, const int* counts, const float* x6, const float* w7,
+                         const float* b7, const float* w8, const float* wo, const float* bo, float* out, int ld_out,
+                         int batch, casync_stream stream);
 
 #ifdef __cplusplus
 }
