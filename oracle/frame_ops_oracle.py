@@ -287,6 +287,23 @@ def prepare_frame(img: np.ndarray, lms: np.ndarray):
     return box, resize_linear_u8(img[ymin:ymax, xmin:xmax], (168, 168))
 
 
+def blend_region(target: np.ndarray, crop: np.ndarray, final_mask: np.ndarray, mask: Optional[np.ndarray]):
+    """infer_api.py:314-345 on one crop region: the float64 blend of the synthesised ``crop`` into ``target`` under the
+    dilated polygon mask and the optional float32 frame mask; None where the shapes differ (:320-324).  The caller
+    stores the result into its uint8 frame (truncation)."""
+    final_f = final_mask / 255.0                                   # float64 0.0 / 1.0
+    final3 = np.repeat(final_f[..., np.newaxis], 3, axis=2)
+    if crop.shape != target.shape:                                 # :320-324: shapes differ -> original frame
+        return None
+    if mask is not None:
+        resized = resize_linear_f32(mask.astype(np.float32), (crop.shape[1], crop.shape[0]))
+        resized3 = np.repeat(resized[..., np.newaxis], 3, axis=2)
+        inverted = 1.0 - resized3                                  # float32
+        combined = final3 * (1.0 - inverted)                       # float64
+        return (crop * combined) + (target * (1.0 - combined))
+    return (crop * final3) + (target * (1.0 - final3))
+
+
 def paste_back(img: np.ndarray, lms: np.ndarray, mask: Optional[np.ndarray], box, crop168: np.ndarray,
                pred_u8: np.ndarray) -> np.ndarray:
     """infer_api.py:268-346 for one frame: returns the synthesised full frame (the input image, modified)."""
@@ -298,19 +315,9 @@ def paste_back(img: np.ndarray, lms: np.ndarray, mask: Optional[np.ndarray], box
     face_mask = fill_poly((ymax - ymin, xmax - xmin), face_points(lms, ymin, ymax, xmin, xmax, width))
     e = expand_pixels(int(np.sum(face_mask > 0)))
     final_mask = dilate_square(face_mask, e)
-    final_f = final_mask / 255.0                                   # float64 0.0 / 1.0
-    final3 = np.repeat(final_f[..., np.newaxis], 3, axis=2)
-    target = img[ymin:ymax, xmin:xmax]
-    if crop.shape != target.shape:                                 # :320-324: shapes differ -> original frame
+    result = blend_region(img[ymin:ymax, xmin:xmax], crop, final_mask, mask)
+    if result is None:
         return img
-    if mask is not None:
-        resized = resize_linear_f32(mask.astype(np.float32), (crop.shape[1], crop.shape[0]))
-        resized3 = np.repeat(resized[..., np.newaxis], 3, axis=2)
-        inverted = 1.0 - resized3                                  # float32
-        combined = final3 * (1.0 - inverted)                       # float64
-        result = (crop * combined) + (target * (1.0 - combined))
-    else:
-        result = (crop * final3) + (target * (1.0 - final3))
     img[ymin:ymax, xmin:xmax] = result                             # float64 -> uint8: truncation
     return img
 

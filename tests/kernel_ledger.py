@@ -712,6 +712,88 @@ def frames(with_masks):
     return _done(r, 0.0 if same and changed else float("inf"), 0.0, f"frames with_masks={with_masks}")
 
 
+def frame_ops(name):
+    """casync_frame_prepare + casync_frame_paste_back on the batch tests/frame_cases.py builds under `name`, through the C
+    ABI alone: geometry records written by hand (every frame, valid or not, has a slot of its own in synth and in the mask
+    buffers), masks in allocations of their own, the case's own `pred` in the model's place.  Every stage is held to the
+    case's expectation bit for bit -- crops168, x, synth, area (the sharp check on the fill: one pixel of one span changes
+    the count), mask_b (row pass of the dilation), mask_a (dilated mask), out_regions -- in buffers with 256 bytes of 0x5A
+    either side, which must stay; an invalid frame's synth and mask_b slots stay 0x5A too, its mask_a slot holds the
+    entry's zeros and its region comes back as it went in.  `what` names the first stage and frame that differ."""
+    torch = _t()
+    import numpy as np
+    import frame_cases
+    c = frame_cases.batch(name)
+    B, d = len(c.regions), _dev()
+    PAD, FILL = 256, 0x5A
+    geom = np.zeros((B, 12), dtype=np.uint32).view(np.int32)         # casync_frame_geom: 12 int32 words per frame
+    fmasks = [None if m is None else torch.from_numpy(np.ascontiguousarray(m)).to(d) for m in c.masks]
+    reg_off = synth_off = mask_off = 0
+    for i, r in enumerate(c.regions):
+        h, w = r.shape[:2]
+        geom[i, :7] = (reg_off, h, w, c.width[i], int(c.valid[i]), synth_off, mask_off)
+        geom[i, 7] = -1
+        if fmasks[i] is not None:
+            geom[i, 7:10] = (int(c.masks[i].dtype == np.uint8), c.masks[i].shape[0], c.masks[i].shape[1])
+            addr = fmasks[i].data_ptr()
+            geom[i, 10:12] = np.array([addr & 0xFFFFFFFF, addr >> 32], dtype=np.uint32).view(np.int32)      # low word, high word
+        reg_off, synth_off, mask_off = reg_off + h * w * 3, synth_off + c.width[i] ** 2 * 3, mask_off + h * w
+    max_h, max_w = int(geom[:, 1].max()), int(geom[:, 2].max())
+    max_width = int((geom[:, 3] * geom[:, 4]).max())
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).to(d)
+
+    def padded(nbytes):
+        return torch.full((PAD + nbytes + PAD,), FILL, dtype=torch.uint8, device=d)
+
+    regions_d, geom_d, pts_d, pred_d = up(np.concatenate([r.reshape(-1) for r in c.regions])), up(geom), up(c.pts), up(c.pred)
+    n_crop, n_x = 168 * 168 * 3, 6 * 160 * 160 * 4                  # bytes per frame of crops168 (uint8) and of x (float32)
+    sizes = {"crops168": B * n_crop, "x": B * n_x, "synth": synth_off, "mask_a": mask_off, "mask_b": mask_off,
+             "area": B * 4, "out_regions": reg_off}
+    bufs = {k: padded(n) for k, n in sizes.items()}
+    ptr = {k: b.data_ptr() + PAD for k, b in bufs.items()}
+    lib = _lib()
+    with _Run(0) as r:
+        _ok(lib.casync_frame_prepare(_p(regions_d), _p(geom_d), B, ptr["crops168"], ptr["x"], _s()), "frame_prepare")
+        _ok(lib.casync_frame_paste_back(_p(regions_d), _p(geom_d), _p(pts_d), ptr["crops168"], _p(pred_d), B, max_h, max_w, max_width,
+                                        mask_off, ptr["synth"], ptr["mask_a"], ptr["mask_b"], ptr["area"], ptr["out_regions"], _s()),
+            "frame_paste_back")
+    torch.cuda.synchronize()
+    host = {k: b.cpu().numpy() for k, b in bufs.items()}
+    got = {k: v[PAD:PAD + sizes[k]] for k, v in host.items()}
+    bad = []
+
+    def hold(stage, frame, have, want):
+        want = np.ascontiguousarray(want)
+        have = have.view(want.dtype).reshape(want.shape)
+        if not np.array_equal(have, want):
+            diff = np.abs(have.astype(np.float64) - want.astype(np.float64))
+            where = f"frame {frame} ({c.labels[frame]}, {c.regions[frame].shape[0]}x{c.regions[frame].shape[1]})" if frame >= 0 else "batch"
+            bad.append(f"{stage} of {where}: {int((diff > 0).sum())} values differ, max |d| {diff.max():g}")
+
+    for k, v in host.items():
+        hold(f"{k} margin", -1, np.concatenate([v[:PAD], v[PAD + sizes[k]:]]), np.full(2 * PAD, FILL, np.uint8))
+    for i, reg in enumerate(c.regions):
+        h, w = reg.shape[:2]
+        n, ns = h * w, c.width[i] ** 2 * 3
+        so, mo, ro = int(geom[i, 5]), int(geom[i, 6]), int(geom[i, 0])
+        hold("crops168", i, got["crops168"][i * n_crop:(i + 1) * n_crop], c.crops168[i])
+        hold("x", i, got["x"][i * n_x:(i + 1) * n_x], c.x[i])
+        hold("area (count of the fill)", i, got["area"][4 * i:4 * i + 4], np.array([c.area[i]], np.int32))
+        if c.valid[i]:
+            hold("synth", i, got["synth"][so:so + ns], c.synth[i])
+            hold("mask_b (rows dilated)", i, got["mask_b"][mo:mo + n], c.rows[i])
+            hold("mask_a (dilated)", i, got["mask_a"][mo:mo + n], c.final[i])
+        else:
+            hold("synth of an invalid frame", i, got["synth"][so:so + ns], np.full(ns, FILL, np.uint8))
+            hold("mask_b of an invalid frame", i, got["mask_b"][mo:mo + n], np.full(n, FILL, np.uint8))
+            hold("mask_a of an invalid frame", i, got["mask_a"][mo:mo + n], np.zeros(n, np.uint8))
+        hold("out_regions", i, got["out_regions"][ro:ro + 3 * n], c.out[i])
+    what = f"frame_ops {name} ({B} frames): " + (f"{bad[0]} [{len(bad)} checks failed]" if bad else "every stage equal")
+    return _done(r, float("inf") if bad else 0.0, 0.0, what)
+
+
 def bf16_weight_image(batch):
     """f32_to_bf16_kernel (the bf16 image of a bf16 handle's packed weights): two bf16 handles, one loads a packed buffer X
     whose GEMM / fused-block weights (the tensors the bf16 plan reads through the image) carry random low bits and exact
@@ -794,6 +876,10 @@ def _rows_for(kernel):
             out.append(C(rows_gemm, m, n, k, lda, act, res, *pad))
     return out
 
+
+# the branch-level batches of tests/frame_cases.py; with no valid frame the entry launches no synth kernel
+_FRAME_OPS_SYNTH = [C(frame_ops, n) for n in ("sizes", "polygons", "masks", "invalid_mixed")]
+_FRAME_OPS = _FRAME_OPS_SYNTH + [C(frame_ops, "invalid_all")]
 
 F32, BF = 0, 1
 LEDGER = {
@@ -895,15 +981,15 @@ LEDGER = {
     "ir_fused_kernel<float, 32, 128, 32, 1, 16, 2>": [C(ir_fused_up, F32, 64, 3, 20, 52, "commuted")],
     "ir_fused_kernel<float, 64, 256, 32, 1, 16, 2>": [C(ir_fused_up, F32, 128, 3, 32, 48, "commuted")],
     # ---- frame pipeline, bf16 weight image
-    "frame_resize168_kernel": [C(frames, True)],
-    "crop_to_input_kernel": [C(frames, True)],
-    "frame_synth_kernel": [C(frames, True)],
-    "frame_polyfill_kernel": [C(frames, True)],
-    "frame_polylines_kernel": [C(frames, True)],
-    "frame_area_kernel": [C(frames, True)],
-    "frame_dilate_kernel<true>": [C(frames, True)],
-    "frame_dilate_kernel<false>": [C(frames, True)],
-    "frame_blend_kernel": [C(frames, True), C(frames, False)],
+    "frame_resize168_kernel": [C(frames, True)] + _FRAME_OPS,
+    "crop_to_input_kernel": [C(frames, True)] + _FRAME_OPS,
+    "frame_synth_kernel": [C(frames, True)] + _FRAME_OPS_SYNTH,
+    "frame_polyfill_kernel": [C(frames, True)] + _FRAME_OPS,
+    "frame_polylines_kernel": [C(frames, True)] + _FRAME_OPS,
+    "frame_area_kernel": [C(frames, True)] + _FRAME_OPS,
+    "frame_dilate_kernel<true>": [C(frames, True)] + _FRAME_OPS,
+    "frame_dilate_kernel<false>": [C(frames, True)] + _FRAME_OPS,
+    "frame_blend_kernel": [C(frames, True), C(frames, False)] + _FRAME_OPS,
     "f32_to_bf16_kernel": [C(bf16_weight_image, 3)],
 }
 

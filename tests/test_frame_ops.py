@@ -3,7 +3,15 @@ frame-walk / iterator contract on the CPU; the device process_batch == oracle, b
 
 cv2 is absent from this image, so the oracle (oracle/frame_ops_oracle.py) is PARITY UNPINNED against
 the real library; what these tests pin is (a) properties any correct restatement must have and (b) that
-the HIP kernels compute exactly what the restatement computes."""
+the HIP kernels compute exactly what the restatement computes, on the whole pipeline around a model and
+on well-behaved faces (frame_data.make_frames).
+
+Branch-level coverage of csrc/frame_ops.hip lives elsewhere: tests/frame_cases.py builds the hostile
+batches (every resize branch, contour points far outside the region, both stages of clipLine, rows with
+32 crossings, every mask-resample branch, invalid frames) with the oracle's result of EVERY stage,
+tests/test_frame_cases.py checks on the CPU that each batch reaches its branch, and the ledger
+(tests/kernel_ledger.py frame_ops, run by tests/test_kernel_ledger_gpu.py) holds the kernels to them
+stage by stage through the C ABI, in sentinel-fenced buffers."""
 import os
 import random
 
