@@ -155,10 +155,35 @@ _PROTOS = {
     "casync_op_pfld_dw_s2": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_pfld_head": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), c_f32p, c_f32p, c_f32p,
                                       c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
+    # S3FD face detector (ABI 12)
+    "casync_s3fd_packed_count": (C.c_int, []),
+    "casync_s3fd_packed_name": (C.c_char_p, [C.c_int]),
+    "casync_s3fd_packed_offset": (c_i64, [C.c_int]),
+    "casync_s3fd_packed_size": (c_i64, [C.c_int]),
+    "casync_s3fd_packed_total": (c_i64, []),
+    "casync_s3fd_priors": (c_i64, [C.c_int, C.c_int]),
+    "casync_s3fd_map_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "casync_s3fd_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int]),
+    "casync_s3fd_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "casync_s3fd_destroy": (None, [C.c_void_p]),
+    "casync_s3fd_load_weights_host": (C.c_int, [C.c_void_p, C.c_void_p, c_i64]),
+    "casync_s3fd_load_weights_device": (C.c_int, [C.c_void_p, c_f32p, c_i64]),
+    "casync_s3fd_forward": (C.c_int, [C.c_void_p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p, c_i64, C.c_void_p]),
+    "casync_s3fd_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p, c_i64, C.c_void_p]),
+    "casync_s3fd_forward_tap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p,
+                                          c_i64, C.c_void_p]),
+    "casync_op_s3fd_stem": (C.c_int, [C.c_void_p, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_s3fd_maxpool": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_s3fd_im2col_dil": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_s3fd_relu": (C.c_int, [c_f32p, c_i64, C.c_void_p]),
+    "casync_op_s3fd_l2norm": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_void_p]),
+    "casync_op_s3fd_head": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_void_p]),
+    "casync_op_s3fd_decode": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)
-ABI_VERSION = 11         # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
+ABI_VERSION = 12         # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
 
 
 def lib_path() -> str:
@@ -256,3 +281,11 @@ def pfld_layout():
     items = [(lib.casync_pfld_packed_name(i).decode(), lib.casync_pfld_packed_offset(i), lib.casync_pfld_packed_size(i))
              for i in range(lib.casync_pfld_packed_count())]
     return items, lib.casync_pfld_packed_total()
+
+
+def s3fd_layout():
+    """[(name, offset, size)] in floats, and the total, of the S3FD face-detector engine's packed buffer."""
+    lib = load()
+    items = [(lib.casync_s3fd_packed_name(i).decode(), lib.casync_s3fd_packed_offset(i), lib.casync_s3fd_packed_size(i))
+             for i in range(lib.casync_s3fd_packed_count())]
+    return items, lib.casync_s3fd_packed_total()

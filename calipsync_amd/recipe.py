@@ -194,3 +194,64 @@ def make_pfld_inputs(batch: int, seed: int = PFLD_INPUT_SEED) -> np.ndarray:
     for b in range(batch):
         x[b] = np.floor(uniform01(seed, 0x3000000 + b, x[b].size) * 256.0).astype(np.uint8).reshape(x[b].shape)
     return x
+
+
+# ---- S3FD face detector (calipsync_amd/facedet.py) -------------------------------------------------------------------
+S3FD_WEIGHT_SEED = 0x53FD
+S3FD_INPUT_SEED = 0x53FE
+# Per source: the factor on conf[k]'s weights and the shift of its face-logit bias.  He-initialised heads with neither
+# saturate (scores of exactly 1.0, nearly every prior above 0.05), and a detection fixture would then hang on ties; with these
+# constants, found once, a few percent of the priors pass 0.05 and no two scores come close (tests/golden/make_s3fd_golden.py
+# asserts the margins).
+S3FD_CONF_SCALE = (6.0, 3.75, 3.0, 3.5, 4.5, 4.0)
+S3FD_CONF_SHIFT = (-11.9, -10.7, -13.1, -4.2, 0.2, -0.8)
+
+
+def make_s3fd_state_dict(seed: int = S3FD_WEIGHT_SEED) -> Dict[str, np.ndarray]:
+    """The 65 entries of an ``S3FDNet`` state dict: conv weights N(0, 2 / fan_in) (the trunk is conv + ReLU throughout, so this
+    keeps the scale from stage to stage), conv1_1 a further 1 / 25 (its input is pixels minus the mean, of order 50), biases
+    N(0, 0.05^2), L2Norm weights their constants 10 / 8 / 5 times U(0.75, 1.25) so the fold into the heads is visible, head
+    weights N(0, 1 / fan_in) -- on the normalised sources, whose elements are of order weight / sqrt(C), times sqrt(C) /
+    weight -- and the conf heads calibrated by S3FD_CONF_*."""
+    from . import facedet
+    sd: Dict[str, np.ndarray] = {}
+    gammas = (10.0, 8.0, 5.0)
+    for key, shape in facedet.manifest():
+        n = int(np.prod(shape))
+        s = _stream("s3fd." + key)
+        module, index, leaf = key.split(".") if key.count(".") == 2 else (key.split(".")[0], "", key.split(".")[1])
+        if module.startswith("L2Norm"):
+            v = gammas[[m for m, _ in facedet.L2NORMS].index(module)] * (0.75 + 0.5 * uniform01(seed, s, n))
+        elif leaf == "bias":
+            v = normal01(seed, s, n) * 0.05
+            if module == "conf":
+                v[-1] += S3FD_CONF_SHIFT[int(index)]             # the face logit is the last channel of every conf head
+        elif module in ("loc", "conf"):
+            k, cin = int(index), shape[1]
+            v = normal01(seed, s, n) / np.sqrt(9.0 * cin)
+            if k < 3:
+                v *= np.sqrt(cin) / gammas[k]
+            if module == "conf":
+                v *= S3FD_CONF_SCALE[k]
+        else:
+            v = normal01(seed, s, n) * np.sqrt(2.0 / int(np.prod(shape[1:])))
+            if key == "vgg.0.weight":
+                v /= 25.0
+        sd[key] = v.astype(np.float32).reshape(shape)
+    return sd
+
+
+def make_s3fd_inputs(batch: int, h: int = 77, w: int = 93, seed: int = S3FD_INPUT_SEED) -> np.ndarray:
+    """Synthetic frames as the detector receives them: uint8 [B,h,w,3]; frame b depends only on (seed, b, h, w).  Smooth
+    blobs over noise rather than white noise, so neighbouring priors differ."""
+    x = np.empty((batch, h, w, 3), dtype=np.uint8)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    for b in range(batch):
+        u = uniform01(seed, 0x5000000 + b, 64)
+        img = 96.0 + 64.0 * uniform01(seed, 0x6000000 + b, h * w * 3).reshape(h, w, 3)
+        for i in range(6):
+            cy, cx, r = u[4 * i] * h, u[4 * i + 1] * w, 4.0 + 12.0 * u[4 * i + 2]
+            g = np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2.0 * r * r))
+            img += (160.0 * u[4 * i + 3] - 60.0) * g[:, :, None] * (0.5 + u[32 + 3 * i:35 + 3 * i])
+        x[b] = np.clip(np.floor(img), 0, 255).astype(np.uint8)
+    return x

@@ -43,7 +43,7 @@ enum {
 /* ---- introspection (callable without a GPU) --------------------------- */
 /* Bumped on every change of a prototype, struct layout or the packed-weight layout; the ctypes
  * host (calipsync_amd/_lib.py) refuses a library whose version differs from the one it binds.   */
-#define CASYNC_ABI_VERSION 11  /* 11: PFLD_GhostOne landmark handle (casync_pfld_*, casync_op_pfld_*) */
+#define CASYNC_ABI_VERSION 12  /* 12: S3FD face detector handle (casync_s3fd_*, casync_op_s3fd_*) */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -441,6 +441,74 @@ int  casync_op_pfld_dw_s2(const float* in, const float* w, const float* bias, fl
 int  casync_op_pfld_head(const float* const* sums, const int* tiles, const int* counts, const float* x6, const float* w7,
                          const float* b7, const float* w8, const float* wo, const float* bo, float* out, int ld_out,
                          int batch, casync_stream stream);
+
+/* ---- S3FD face detector (ABI 12) ------------------------------------------ */
+/* S3FDNet, the network behind the reference's S3FDFaceDetector (utils/lip_detector/tools/detect_face.py:19-22;
+ * tools/s3fd/nets.py:28-107), fp32, on equal-sized frames of any H x W the reference itself can run.  The handle replaces
+ * S3FDNet.forward up to its call of Detect.forward (nets.py:109-171) plus PriorBox.forward and decode (box_utils.py:41-59,
+ * 195-217); Detect.forward's threshold / NMS and everything behind it stay on the host (calipsync_amd/facedet.py).  Its own
+ * handle, packed layout and workspace; forwards take the same cross-handle gate as the other three handles.            */
+typedef struct casync_s3fd* casync_s3fd_handle;
+/* Packed layout (floats; tensors start on 256-B boundaries): conv1_1.w [(ky,kx,ci)=27][64]; the dense 3x3 convs conv1_2 ..
+ * conv5_3, conv6_2, conv7_2 (extras 1, 3) as <name>.w [cout][(ky,kx,cin)]; fc6.w [1024][(ky,kx,512)]; the 1x1 convs fc7,
+ * conv6_1, conv7_1 (extras 0, 2) as [cout][cin]; every <name>.b [cout]; head<k>.w [8][(ky,kx,cin)] = loc[k] (rows 0-3) over
+ * conf[k] (rows 4-7; two zero rows for k >= 1), with the L2Norm weight of sources 0-2 folded into the cin axis, head<k>.b [8]. */
+int         casync_s3fd_packed_count(void);
+const char* casync_s3fd_packed_name(int i);
+int64_t     casync_s3fd_packed_offset(int i);
+int64_t     casync_s3fd_packed_size(int i);
+int64_t     casync_s3fd_packed_total(void);
+/* Priors of an h x w frame (nets.py:155-166: the six maps' pixels, in order; 0 for a size the handle refuses) and the size
+ * of source map k (0..5).                                                                                              */
+int64_t     casync_s3fd_priors(int h, int w);
+int         casync_s3fd_map_size(int h, int w, int k, int* map_h, int* map_w);
+/* 0 for a shape the handle refuses: batch outside 1..65536, a frame whose pooled size reaches 0 (the reference raises
+ * there too), a side above 8192, one frame whose conv1 output alone reaches 2 GiB.  No operand of one launch reaches 2 GiB:
+ * a larger batch is walked in sub-batches inside the forward, and the workspace is that of one sub-batch.               */
+int64_t     casync_s3fd_workspace_bytes(int batch, int h, int w);
+/* Replaces S3FDNet(device).to(device) / load_state_dict / eval() (main.py:20-23). */
+int  casync_s3fd_create(int device_id, casync_s3fd_handle* out);
+void casync_s3fd_destroy(casync_s3fd_handle h);
+int  casync_s3fd_load_weights_host(casync_s3fd_handle h, const float* packed, int64_t n_floats);
+int  casync_s3fd_load_weights_device(casync_s3fd_handle h, const float* packed_dev, int64_t n_floats);
+/* x_dev [B,3,H,W] NCHW fp32 as main.py:36-42 hands it over (channel c of the image as given minus (123, 117, 104)[c]) ->
+ * det_dev [B,P,5] = (face probability, x1, y1, x2, y2) of EVERY prior, normalised coordinates, no threshold: softmax(conf)
+ * [..., 1] (nets.py:170) and decode(loc, priors, [0.1, 0.2]) (box_utils.py:151).  _u8 takes the frames themselves,
+ * [B,H,W,3] uint8, and subtracts the mean on the device: bit-equal to the float form.  batch 0 does nothing.  Enqueues
+ * on `stream`, no host synchronisation, no allocation, no atomics: frame i of a batch has the bits of that frame alone. */
+int  casync_s3fd_forward(casync_s3fd_handle h, const float* x_dev, int batch, int H, int W, float* det_dev,
+                         void* workspace_dev, int64_t workspace_bytes, casync_stream stream);
+int  casync_s3fd_forward_u8(casync_s3fd_handle h, const uint8_t* frames_dev, int batch, int H, int W, float* det_dev,
+                            void* workspace_dev, int64_t workspace_bytes, casync_stream stream);
+/* Debug: the same forward stopped at `stage`, that intermediate written NHWC to out_dev, each after its ReLU and before the
+ * pool: 0 conv1_2 [B,H,W,64], 1 conv2_2, 2 conv3_3, 3 conv4_3, 4 conv5_3 (nets.py:115-131), 5 fc6, 6 fc7, 7 conv6_2,
+ * 8 conv7_2 (nets.py:135-138); 9 loc [B,P,4], 10 the conf logits [B,P,2] after conf[0]'s max-out (nets.py:141-162),
+ * 11 det [B,P,5].  in_dev is float NCHW, or uint8 HWC when input_u8.                                                */
+int  casync_s3fd_forward_tap(casync_s3fd_handle h, const void* in_dev, int input_u8, int batch, int H, int W, int stage,
+                             float* out_dev, void* workspace_dev, int64_t workspace_bytes, casync_stream stream);
+/* single operators (tests), one per kernel, all NHWC fp32:
+ * stem: vgg[0-1], Conv2d(3, 64, 3, 1, 1) + ReLU (nets.py:35-36), x float NCHW or uint8 HWC (the mean subtracted here:
+ *   main.py:38-41); w [(ky,kx,ci)=27][64] -> out [B,h,w,64].
+ * maxpool: nn.MaxPool2d(2, 2[, ceil_mode=True]) (nets.py:39,45,53,61,69): in [B,h,w,c] -> out [B,h/2,w/2,c] or
+ *   [B,(h+1)/2,(w+1)/2,c]; c % 4 == 0.
+ * im2col_dil: the [B h w][(ky,kx,c)] matrix of a 3x3 conv with padding = dilation (vgg[30], fc6: nets.py:71), zero where a
+ *   tap falls outside.
+ * relu: in place over n floats (n % 4 == 0): nets.py:72,74,136 behind the GEMMs without a ReLU epilogue.
+ * l2norm: L2Norm.forward without the weight (nets.py:21-23): out[r,:] = in[r,:] / (sqrt(sum in[r,:]^2) + 1e-10).
+ * head: loc[k] and conf[k] of one source (nets.py:141-153): in [B,h,w,c], w [8][(ky,kx,c)], bias [8] -> loc [B,priors,4] and
+ *   conf [B,priors,2] at priors first_prior + y w + x; maxout: conf = (max of rows 4-6, row 7) (nets.py:144-145), else rows
+ *   4 and 5.
+ * decode: PriorBox.forward (box_utils.py:195-212) + decode (box_utils.py:54-58) + softmax(conf)[..., 1] (nets.py:170) of an
+ *   H x W frame's priors: loc [B,P,4], conf [B,P,2] -> det [B,P,5].                                                   */
+int  casync_op_s3fd_stem(const void* x, int input_u8, const float* w, const float* bias, float* out, int batch, int h, int w_,
+                         casync_stream stream);
+int  casync_op_s3fd_maxpool(const float* in, float* out, int batch, int h, int w_, int c, int ceil_mode, casync_stream stream);
+int  casync_op_s3fd_im2col_dil(const float* in, float* out, int batch, int h, int w_, int c, int dilation, casync_stream stream);
+int  casync_op_s3fd_relu(float* x, int64_t n, casync_stream stream);
+int  casync_op_s3fd_l2norm(const float* in, float* out, int64_t rows, int c, casync_stream stream);
+int  casync_op_s3fd_head(const float* in, const float* w, const float* bias, float* loc, float* conf, int batch, int h, int w_,
+                         int c, int priors, int first_prior, int maxout, casync_stream stream);
+int  casync_op_s3fd_decode(const float* loc, const float* conf, float* det, int batch, int H, int W, casync_stream stream);
 
 #ifdef __cplusplus
 }
