@@ -180,10 +180,22 @@ _PROTOS = {
     "casync_op_s3fd_head": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_void_p]),
     "casync_op_s3fd_decode": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # S3FD, bf16 precision (ABI 13); bf16 buffers pass as c_void_p
+    "casync_s3fd_create_ex": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "casync_s3fd_precision": (C.c_int, [C.c_void_p]),
+    "casync_s3fd_workspace_bytes_ex": (c_i64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "casync_op_s3fd16_stem": (C.c_int, [C.c_void_p, C.c_int, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_s3fd16_maxpool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_s3fd16_im2col_dil": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_s3fd16_relu": (C.c_int, [C.c_void_p, c_i64, C.c_void_p]),
+    "casync_op_s3fd16_widen": (C.c_int, [C.c_void_p, c_f32p, c_i64, C.c_void_p]),
+    "casync_op_s3fd16_l2norm": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_int, C.c_void_p]),
+    "casync_op_s3fd16_head": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)
-ABI_VERSION = 12         # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
+ABI_VERSION = 13         # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
 
 
 def lib_path() -> str:

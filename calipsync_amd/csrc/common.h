@@ -319,6 +319,16 @@ int launch_hb16_attention(const void* qkv, void* out, int batch, int T, hipStrea
 // fp32 -> bf16 image of n floats (n % 4 == 0), the conversion of the bf16 U-Net handle's weight image (engine.hip)
 int launch_f32_to_bf16(const float* in, void* out, long long n, hipStream_t s);
 
+// ---- S3FD, bf16 handle (facedet_bf16.hip; pointers named void* are bf16, NHWC, C % 8 == 0) ----
+int launch_det16_stem(const void* x, bool u8, const float* w, const float* bias, void* out, int batch, int H, int W, hipStream_t s);
+int launch_det16_maxpool(const void* in, void* out, int batch, int H, int W, int C, bool ceil_mode, hipStream_t s);
+int launch_det16_im2col_dil(const void* in, void* out, int batch, int h, int w, int C, int dil, hipStream_t s);
+int launch_det16_relu(void* x, long long n, hipStream_t s);                     // in place, n % 8 == 0
+int launch_det16_widen(const void* in, float* out, long long n, hipStream_t s); // bf16 -> fp32, n % 8 == 0
+int launch_det16_l2norm(const void* in, void* out, long long rows, int C, hipStream_t s);
+int launch_det16_head(const void* in, const float* wt, const float* bias, float* loc, float* conf, int batch, int h, int w, int C, int P,
+                      int p0, bool maxout, hipStream_t s);
+
 // dense 3x3 convolution + bias (+ the activation epi.act: LeakyReLU or ReLU) as an implicit GEMM on the ring kernel: no
 // im2col buffer, the taps are gathered by the LDS-DMA loads themselves.  in: [B,H,W,cin] contiguous NHWC,
 // w: [cout][(ky,kx,cin)], out: [B*Ho*Wo, ldc]; stride_h / stride_w apart (AudioConvWenet's conv3 is (1, 2)).

@@ -15,6 +15,11 @@
 // conv1_2 .. conv5_3 and extras 1 and 3 run on the ring implicit-GEMM kernel (launch_conv3x3_gemm, ReLU epilogue), fc6 / fc7 and
 // extras 0 and 2 on the data-parallel fp32 ring GEMM (launch_rows_gemm): no stream-K, no K split.  No kernel here sums across
 // frames or uses an atomic: frame i of a batch has the bits of that frame forwarded alone.
+//
+// A handle made with precision 1 (casync_s3fd_create_ex) runs det_pass16 instead: the same walk on bf16 activations, with the
+// kernels of facedet_bf16.hip, the bf16 ring conv (launch_conv3x3_gemm, DT_BF16) and launch_rows_gemm_bf16 on a bf16 image of
+// the packed buffer made at weight load; the stem, the heads and det_decode_kernel keep fp32 weights and outputs.  The fp32
+// handle launches what it launched before that precision existed.
 #include <string.h>
 
 #include <mutex>
@@ -430,6 +435,13 @@ int det_sub_batch(int batch, int H, int W) {
   return (int)(fit < batch ? fit : batch);
 }
 
+// ... of the bf16 handle: the same rule on two bytes a value
+int det_sub_batch16(int batch, int H, int W) {
+  const long long per_frame = (long long)H * W * SC * 2;
+  const long long fit = (kMaxBytes - 1) / per_frame;
+  return (int)(fit < batch ? fit : batch);
+}
+
 struct DetWs {
   float *a, *b, *col, *loc, *conf;
   int64_t floats;
@@ -448,12 +460,34 @@ struct DetWs {
   }
 };
 
+// the bf16 handle's arena: two bf16 activations, fc6's bf16 im2col matrix, fp32 loc / conf (every part on a 256-B boundary)
+struct DetWs16 {
+  bf16_t *a, *b, *col;
+  float *loc, *conf;
+  int64_t bytes;
+  DetWs16(char* base, int nb, const DetGeom& G) {
+    int64_t off = 0;
+    auto take = [&](int64_t n_bytes) {
+      char* p = base ? base + off : nullptr;
+      off += (n_bytes + 255) / 256 * 256;
+      return p;
+    };
+    const int64_t act = (int64_t)nb * G.H * G.W * SC * 2;
+    a = reinterpret_cast<bf16_t*>(take(act)), b = reinterpret_cast<bf16_t*>(take(act));
+    col = reinterpret_cast<bf16_t*>(take((int64_t)nb * G.h[3] * G.w[3] * 9 * 512 * 2));
+    loc = reinterpret_cast<float*>(take((int64_t)nb * G.off[6] * 16)), conf = reinterpret_cast<float*>(take((int64_t)nb * G.off[6] * 8));
+    bytes = off;
+  }
+};
+
 }  // namespace
 
 struct casync_s3fd {
   int device = 0;
+  int precision = 0;             // 0 fp32, 1 bf16 (det_pass16)
   const float* w = nullptr;
   float* owned = nullptr;
+  bf16_t* w16 = nullptr;         // precision 1: bf16 image of the packed buffer (owned; the conv / GEMM matrices are read from it)
   hipEvent_t ev_fwd = nullptr;   // forward gate slot
 };
 
@@ -541,6 +575,72 @@ int det_pass(const float* w, const void* x, bool u8, int nb, const DetGeom& G, c
   return launch_det_decode(ws.loc, ws.conf, out, nb, G, s);
 }
 
+// det_pass on bf16 activations (the contract: DESIGN section 8d, "bf16 precision").  w16 is the bf16 image of w; a tap of a
+// bf16 stage is widened into `out`.
+int det_pass16(const float* w, const bf16_t* w16, const void* x, bool u8, int nb, const DetGeom& G, const DetWs16& ws, float* out, int stage,
+               hipStream_t s) {
+  const DetLayout& L = det_layout();
+  const int P = G.off[6];
+  auto widen_out = [&](const bf16_t* src, int64_t n) -> int { return launch_det16_widen(src, out, n, s); };
+  auto copy_out = [&](const float* src, int64_t floats) -> int {
+    CASYNC_CHECK_HIP(hipMemcpyAsync(out, src, (size_t)floats * 4, hipMemcpyDeviceToDevice, s));
+    return CASYNC_OK;
+  };
+  auto head = [&](int k, const bf16_t* src) -> int {
+    return launch_det16_head(src, w + L.head_w[k], w + L.head_b[k], ws.loc, ws.conf, nb, G.h[k], G.w[k], kSrcC[k], P, G.off[k], k == 0, s);
+  };
+  bf16_t *cur = ws.a, *nxt = ws.b;
+  DT(launch_det16_stem(x, u8, w + L.stem_w, w + L.stem_b, cur, nb, G.H, G.W, s));
+  int h = G.H, wd = G.W;
+  for (int i = 0; i < kNVgg; ++i) {
+    const VggStep& v = kVgg[i];
+    GemmEpilogue epi;
+    epi.bias = w + L.vgg_b[i];
+    epi.act = 2;
+    DT(launch_conv3x3_gemm(cur, w16 + L.vgg_w[i], nxt, v.c.cout, nb, h, wd, v.c.cin, v.c.cout, 1, 1, 1, epi, s, DT_BF16));
+    std::swap(cur, nxt);
+    if (v.stage == stage) return widen_out(cur, (int64_t)nb * h * wd * v.c.cout);
+    if (v.source >= 0) {
+      DT(launch_det16_l2norm(cur, nxt, (long long)nb * h * wd, v.c.cout, s));
+      DT(head(v.source, nxt));
+    }
+    if (v.pool) {
+      DT(launch_det16_maxpool(cur, nxt, nb, h, wd, v.c.cout, v.pool == 2, s));
+      std::swap(cur, nxt);
+      h = v.pool == 2 ? (h + 1) / 2 : h / 2, wd = v.pool == 2 ? (wd + 1) / 2 : wd / 2;
+    }
+  }
+  // a 1x1 conv (or fc6 on its im2col matrix) on the bf16 rows GEMM (bias only), then the ReLU pass
+  auto dense = [&](const bf16_t* a, int m, int k, int64_t w_off, int64_t b_off, bf16_t* c, int n) -> int {
+    DT(launch_rows_gemm_bf16(a, k, w16 + w_off, w + b_off, c, n, m, n, k, s));
+    return launch_det16_relu(c, (long long)m * n, s);
+  };
+  const int m = nb * h * wd;
+  DT(launch_det16_im2col_dil(cur, ws.col, nb, h, wd, 512, 6, s));
+  DT(dense(ws.col, m, 9 * 512, L.fc6_w, L.fc6_b, nxt, 1024));
+  std::swap(cur, nxt);
+  if (stage == ST_FC6) return widen_out(cur, (int64_t)m * 1024);
+  DT(dense(cur, m, 1024, L.fc7_w, L.fc7_b, nxt, 1024));
+  std::swap(cur, nxt);
+  if (stage == ST_FC7) return widen_out(cur, (int64_t)m * 1024);
+  DT(head(3, cur));
+  const int ex_c[5] = {1024, 256, 512, 128, 256};
+  for (int j = 0; j < 2; ++j) {
+    DT(dense(cur, nb * G.h[3 + j] * G.w[3 + j], ex_c[2 * j], L.ex_w[2 * j], L.ex_b[2 * j], nxt, ex_c[2 * j + 1]));
+    GemmEpilogue epi;
+    epi.bias = w + L.ex_b[2 * j + 1];
+    epi.act = 2;
+    DT(launch_conv3x3_gemm(nxt, w16 + L.ex_w[2 * j + 1], cur, ex_c[2 * j + 2], nb, G.h[3 + j], G.w[3 + j], ex_c[2 * j + 1], ex_c[2 * j + 2], 2,
+                           2, 1, epi, s, DT_BF16));
+    const int64_t n_out = (int64_t)nb * G.h[4 + j] * G.w[4 + j] * ex_c[2 * j + 2];
+    if (stage == ST_CONV6_2 + j) return widen_out(cur, n_out);
+    DT(head(4 + j, cur));
+  }
+  if (stage == ST_LOC) return copy_out(ws.loc, (int64_t)nb * P * 4);
+  if (stage == ST_CONF) return copy_out(ws.conf, (int64_t)nb * P * 2);
+  return launch_det_decode(ws.loc, ws.conf, out, nb, G, s);
+}
+
 int64_t det_stage_floats(const DetGeom& G, int stage) {   // per frame
   const int c[5] = {64, 128, 256, 512, 512};
   if (stage == 0) return (int64_t)G.H * G.W * c[0];
@@ -557,20 +657,23 @@ int64_t det_stage_floats(const DetGeom& G, int stage) {   // per frame
 int det_run(casync_s3fd* D, const void* x, bool u8, int batch, int H, int W, float* out, void* ws_dev, int64_t ws_bytes, hipStream_t s,
             int stage) {
   CASYNC_REQUIRE(D, "s3fd forward: null handle");
-  CASYNC_REQUIRE(D->w, "s3fd forward: weights not loaded");
+  const bool h16 = D->precision == 1;
+  CASYNC_REQUIRE(D->w && (!h16 || D->w16), "s3fd forward: weights not loaded");
   CASYNC_REQUIRE(batch >= 0 && batch <= 65536, "s3fd forward: batch %d (0..65536)", batch);
   CASYNC_REQUIRE(stage >= 0 && stage < kStages, "s3fd forward: stage %d (0..%d)", stage, kStages - 1);
   DetGeom G;
   CASYNC_REQUIRE(det_geometry(H, W, &G), "s3fd forward: frames of %d x %d pool to nothing (or exceed 8192): the network needs 16 x 16 at least",
                  H, W);
-  const int nb = det_sub_batch(batch, H, W);
+  const int nb = h16 ? det_sub_batch16(batch, H, W) : det_sub_batch(batch, H, W);
   CASYNC_REQUIRE(batch == 0 || nb >= 1, "s3fd forward: one %d x %d frame alone has an activation of 2 GiB or more", H, W);
   if (batch == 0) return CASYNC_OK;
   CASYNC_REQUIRE(x && out && ws_dev, "s3fd forward: null pointer");
   CASYNC_REQUIRE((uintptr_t)x % (u8 ? 1 : 4) == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws_dev % 256 == 0, "s3fd forward: alignment");
   DetWs ws(static_cast<float*>(ws_dev), nb, G);
-  if (ws_bytes < ws.floats * 4) {
-    casync_set_error("s3fd forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)ws.floats * 4);
+  DetWs16 ws16(static_cast<char*>(ws_dev), nb, G);
+  const int64_t need = h16 ? ws16.bytes : ws.floats * 4;
+  if (ws_bytes < need) {
+    casync_set_error("s3fd forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)need);
     return CASYNC_ERR_STATE;
   }
   DetDeviceGuard guard(D->device);
@@ -581,11 +684,22 @@ int det_run(casync_s3fd* D, const void* x, bool u8, int batch, int H, int W, flo
   // every pass takes the tile choices of its own frame count; the kernels' sums do not depend on it (see the header comment)
   for (int b0 = 0; b0 < batch; b0 += nb) {
     const int n = batch - b0 < nb ? batch - b0 : nb;
-    DT(det_pass(D->w, static_cast<const char*>(x) + (size_t)b0 * in_frame, u8, n, G, ws, out + (size_t)b0 * out_frame, stage, s));
+    const void* xb = static_cast<const char*>(x) + (size_t)b0 * in_frame;
+    if (h16) DT(det_pass16(D->w, D->w16, xb, u8, n, G, ws16, out + (size_t)b0 * out_frame, stage, s));
+    else DT(det_pass(D->w, xb, u8, n, G, ws, out + (size_t)b0 * out_frame, stage, s));
   }
   return CASYNC_OK;
 }
 #undef DT
+
+// bf16 image of the packed buffer, made once at weight load (not on the forward path)
+int det_refresh_w16(casync_s3fd* h, int64_t n) {
+  if (h->precision != 1) return CASYNC_OK;
+  if (!h->w16) CASYNC_CHECK_HIP(hipMalloc((void**)&h->w16, n * sizeof(bf16_t)));
+  if (int st = launch_f32_to_bf16(h->w, h->w16, (long long)n, 0)) return st;
+  CASYNC_CHECK_HIP(hipDeviceSynchronize());
+  return CASYNC_OK;
+}
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
@@ -606,16 +720,25 @@ int casync_s3fd_map_size(int h, int w, int k, int* map_h, int* map_w) {
   *map_h = G.h[k], *map_w = G.w[k];
   return CASYNC_OK;
 }
-int64_t casync_s3fd_workspace_bytes(int batch, int h, int w) {
+int64_t casync_s3fd_workspace_bytes_ex(int precision, int batch, int h, int w) {
   DetGeom G;
-  if (batch < 1 || batch > 65536 || !det_geometry(h, w, &G)) return 0;
+  if ((precision != 0 && precision != 1) || batch < 1 || batch > 65536 || !det_geometry(h, w, &G)) return 0;
+  if (precision == 1) {
+    const int nb = det_sub_batch16(batch, h, w);
+    return nb >= 1 ? DetWs16(nullptr, nb, G).bytes : 0;
+  }
   const int nb = det_sub_batch(batch, h, w);
   return nb >= 1 ? DetWs(nullptr, nb, G).floats * 4 : 0;
 }
+int64_t casync_s3fd_workspace_bytes(int batch, int h, int w) { return casync_s3fd_workspace_bytes_ex(0, batch, h, w); }
 
-int casync_s3fd_create(int device_id, casync_s3fd_handle* out) {
+int casync_s3fd_create(int device_id, casync_s3fd_handle* out) { return casync_s3fd_create_ex(device_id, 0, out); }
+int casync_s3fd_precision(casync_s3fd_handle h) { return h ? h->precision : -1; }
+
+int casync_s3fd_create_ex(int device_id, int precision, casync_s3fd_handle* out) {
   CASYNC_REQUIRE(out, "s3fd_create: null out");
   *out = nullptr;
+  CASYNC_REQUIRE(precision == 0 || precision == 1, "s3fd_create: precision %d (0 fp32, 1 bf16)", precision);
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
     casync_set_error("s3fd_create: no HIP device visible");
@@ -630,6 +753,7 @@ int casync_s3fd_create(int device_id, casync_s3fd_handle* out) {
   }
   casync_s3fd* h = new casync_s3fd();
   h->device = device_id;
+  h->precision = precision;
   *out = h;
   return CASYNC_OK;
 }
@@ -639,6 +763,7 @@ void casync_s3fd_destroy(casync_s3fd_handle h) {
   DetDeviceGuard guard(h->device);
   casync_gate_forget(h->device, h, &h->ev_fwd);
   if (h->owned) (void)hipFree(h->owned);
+  if (h->w16) (void)hipFree(h->w16);
   delete h;
 }
 
@@ -651,7 +776,7 @@ int casync_s3fd_load_weights_host(casync_s3fd_handle h, const float* packed, int
   if (!h->owned) CASYNC_CHECK_HIP(hipMalloc((void**)&h->owned, n_floats * sizeof(float)));
   CASYNC_CHECK_HIP(hipMemcpy(h->owned, packed, n_floats * sizeof(float), hipMemcpyHostToDevice));
   h->w = h->owned;
-  return CASYNC_OK;
+  return det_refresh_w16(h, n_floats);
 }
 
 int casync_s3fd_load_weights_device(casync_s3fd_handle h, const float* packed_dev, int64_t n_floats) {
@@ -660,7 +785,10 @@ int casync_s3fd_load_weights_device(casync_s3fd_handle h, const float* packed_de
                  (long long)det_layout().total);
   CASYNC_REQUIRE(((uintptr_t)packed_dev % 256) == 0, "s3fd_load_weights_device: buffer must be 256-B aligned");
   h->w = packed_dev;
-  return CASYNC_OK;
+  if (h->precision != 1) return CASYNC_OK;
+  DetDeviceGuard guard(h->device);
+  CASYNC_CHECK_HIP(guard.err);
+  return det_refresh_w16(h, n_floats);
 }
 
 int casync_s3fd_forward(casync_s3fd_handle h, const float* x_dev, int batch, int H, int W, float* det_dev, void* workspace_dev,

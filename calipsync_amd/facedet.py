@@ -39,6 +39,7 @@ _STAGE_C = (64, 128, 256, 512, 512, 1024, 1024, 512, 256)
 IMG_MEAN = np.array([123.0, 117.0, 104.0], dtype=np.float32)   # per channel of the image as given (main.py:38-41: the swaps cancel)
 # Detect() and the callers' constants (box_utils.py:131-133, main.py:57)
 CONF_THRESH, NMS_THRESH, NMS_TOP_K, TOP_K, FINAL_NMS = 0.05, 0.3, 5000, 750, 0.1
+PRECISIONS = {"fp32": 0, "bf16": 1}     # casync_s3fd_create_ex
 
 
 def manifest() -> List[Tuple[str, Tuple[int, ...]]]:
@@ -147,22 +148,26 @@ def n_priors(h: int, w: int) -> int:
 
 class S3FDEngine:
     """S3FDNet().eval() up to Detect.forward, on the HIP engine: forward(x [B,3,H,W] float, mean subtracted) or
-    forward_u8(frames [B,H,W,3] uint8) -> the dense det [B,P,5] on the device.  There is no CPU path."""
+    forward_u8(frames [B,H,W,3] uint8) -> the dense det [B,P,5] on the device.  There is no CPU path.  precision "bf16"
+    runs the network on bf16 activations; inputs, outputs and taps stay float32."""
 
-    def __init__(self, sd, device: str = "cuda:0"):
+    def __init__(self, sd, device: str = "cuda:0", precision: str = "fp32"):
         import ctypes as C
         from . import _lib
+        if precision not in PRECISIONS:
+            raise ValueError(f"S3FD engine: precision {precision!r}, expected one of {sorted(PRECISIONS)}")
+        self.precision = precision
         buf = pack(sd)                 # (checks the checkpoint before any device call)
         self._lib = _lib.load()
         self.device = torch.device(device)
         h = C.c_void_p()
-        _lib.check(self._lib.casync_s3fd_create(self.device.index or 0, C.byref(h)), "casync_s3fd_create")
+        _lib.check(self._lib.casync_s3fd_create_ex(self.device.index or 0, PRECISIONS[precision], C.byref(h)), "casync_s3fd_create_ex")
         self._h = h
         _lib.check(self._lib.casync_s3fd_load_weights_host(self._h, buf.ctypes.data, buf.size), "casync_s3fd_load_weights_host")
         self._ws: Optional[torch.Tensor] = None
 
     def workspace_bytes(self, batch: int, h: int, w: int) -> int:
-        return self._lib.casync_s3fd_workspace_bytes(batch, h, w)
+        return self._lib.casync_s3fd_workspace_bytes_ex(PRECISIONS[self.precision], batch, h, w)
 
     def _workspace(self, batch: int, h: int, w: int) -> torch.Tensor:
         need = max(self.workspace_bytes(batch, h, w), 256)     # (0: the forward itself says why it refuses the shape)
@@ -323,19 +328,22 @@ class S3FDDetector:
     one size run through one batched forward."""
 
     def __init__(self, weight_base_dir: Optional[str] = None, *, state_dict=None, conf_threshold: float = 0.1, scale: float = 0.25,
-                 device: str = "cuda:0"):
+                 device: str = "cuda:0", precision: str = "fp32"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"S3FDDetector: precision {precision!r}, expected one of {sorted(PRECISIONS)}")
         if state_dict is None:
             if weight_base_dir is None:
                 raise ValueError("S3FDDetector: weight_base_dir or state_dict is needed")
             state_dict = dict(torch.load(os.path.join(weight_base_dir, "sfd_face.pth"), map_location="cpu", weights_only=True))
         self.conf_threshold = conf_threshold
         self.scale = scale
+        self.precision = precision
         self.last_detection = None
-        self.det_net = self._make_engine(state_dict, device)
+        self.det_net = self._make_engine(state_dict, device, precision)
 
     @staticmethod
-    def _make_engine(state_dict, device):
-        return S3FDEngine(state_dict, device)
+    def _make_engine(state_dict, device, precision="fp32"):
+        return S3FDEngine(state_dict, device, precision)
 
     def dense(self, images: Sequence[np.ndarray]) -> List[np.ndarray]:
         """per image the dense det [P,5] (float32, host); equal-sized images share a forward"""

@@ -43,7 +43,8 @@ enum {
 /* ---- introspection (callable without a GPU) --------------------------- */
 /* Bumped on every change of a prototype, struct layout or the packed-weight layout; the ctypes
  * host (calipsync_amd/_lib.py) refuses a library whose version differs from the one it binds.   */
-#define CASYNC_ABI_VERSION 12  /* 12: S3FD face detector handle (casync_s3fd_*, casync_op_s3fd_*) */
+#define CASYNC_ABI_VERSION 13  /* 12: S3FD face detector handle (casync_s3fd_*, casync_op_s3fd_*); 13: its bf16 precision
+                                * (casync_s3fd_create_ex, _precision, _workspace_bytes_ex, casync_op_s3fd16_*) */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -509,6 +510,38 @@ int  casync_op_s3fd_l2norm(const float* in, float* out, int64_t rows, int c, cas
 int  casync_op_s3fd_head(const float* in, const float* w, const float* bias, float* loc, float* conf, int batch, int h, int w_,
                          int c, int priors, int first_prior, int maxout, casync_stream stream);
 int  casync_op_s3fd_decode(const float* loc, const float* conf, float* det, int batch, int H, int W, casync_stream stream);
+
+/* ---- S3FD, bf16 precision (ABI 13) ----------------------------------------- */
+/* A second precision of the handle, chosen at creation: precision 0 is the fp32 handle above (casync_s3fd_create is the _ex
+ * form with 0), 1 runs the network on bf16 activations; any other value is refused before any device call.  Precision 1:
+ * conv1_1 in fp32 from the fp32 weights with a bf16 store; conv1_2 .. conv5_3, fc6 (on its dilated im2col matrix), fc7 and
+ * the four extras with bf16 operands from a bf16 image of the packed buffer made on the device at load_weights_*, fp32
+ * accumulation, bias and ReLU, bf16 out; pooling and im2col on bf16 (exact); L2Norm with an fp32 sum of squares and a true
+ * division, bf16 out; the heads from bf16 activations with their fp32 weights, fp32 loc / conf logits; priors, decode and
+ * score as in the fp32 handle.  The packed layout is the same.  forward, forward_u8, forward_tap and load_weights_* serve
+ * both precisions: frames in and det [B,P,5] fp32 out as above, every tap of a bf16 stage widened to fp32.  Same forward
+ * properties (no allocation, synchronisation or atomics; frame i of a batch has the bits of that frame alone; sub-batches
+ * by the 2 GiB rule on the bf16 byte sizes).  _precision: 0 or 1 (-1 for a null handle).  _workspace_bytes_ex: the
+ * workspace of one precision (0 for an unknown precision or a refused shape); casync_s3fd_workspace_bytes is precision 0. */
+int     casync_s3fd_create_ex(int device_id, int precision, casync_s3fd_handle* out);
+int     casync_s3fd_precision(casync_s3fd_handle h);
+int64_t casync_s3fd_workspace_bytes_ex(int precision, int batch, int h, int w);
+/* single operators (tests), one per kernel of the bf16 precision; in / out named void* are bf16 NHWC, c % 8 == 0, weights,
+ * bias, loc and conf fp32 as in the casync_op_s3fd_* entries of the same name:
+ * stem: fp32 arithmetic as casync_op_s3fd_stem (x float NCHW or uint8 HWC, the two forms bit-equal) -> out [B,h,w,64] bf16.
+ * maxpool, im2col_dil, relu (n % 8 == 0): the bf16 forms of the fp32 entries, exact on bf16 values.
+ * widen: bf16 -> fp32 over n values (n % 8 == 0), the taps of the bf16 stages.
+ * l2norm: bf16 rows in, fp32 sum of squares, out[r,:] = bf16(in[r,:] / (sqrt(sum) + 1e-10)).
+ * head: casync_op_s3fd_head from bf16 activations: fp32 weights and sums, fp32 loc / conf.                           */
+int  casync_op_s3fd16_stem(const void* x, int input_u8, const float* w, const float* bias, void* out, int batch, int h, int w_,
+                           casync_stream stream);
+int  casync_op_s3fd16_maxpool(const void* in, void* out, int batch, int h, int w_, int c, int ceil_mode, casync_stream stream);
+int  casync_op_s3fd16_im2col_dil(const void* in, void* out, int batch, int h, int w_, int c, int dilation, casync_stream stream);
+int  casync_op_s3fd16_relu(void* x, int64_t n, casync_stream stream);
+int  casync_op_s3fd16_widen(const void* in, float* out, int64_t n, casync_stream stream);
+int  casync_op_s3fd16_l2norm(const void* in, void* out, int64_t rows, int c, casync_stream stream);
+int  casync_op_s3fd16_head(const void* in, const float* w, const float* bias, float* loc, float* conf, int batch, int h, int w_,
+                           int c, int priors, int first_prior, int maxout, casync_stream stream);
 
 #ifdef __cplusplus
 }

@@ -2,11 +2,13 @@
 fp32 torch (tests/s3fd_ref.py) on the same GPU, in one process, the two alternating round by round, profiler off.
 
     python tools/facedet_bench.py [--batches 1,8,16] [--hw 270,480] [--steps 10] [--rounds 3] [--warmup 2] [--no-baseline]
-                                  [--json profiles/facedet.json]
+                                  [--precision fp32|bf16|both] [--json profiles/facedet.json]
 
 One JSON line per batch: uint8 frames in, the dense det [B,P,5] out; ms per forward (the median of the rounds, and their
 spread) and frames/s of both, kernel launches per forward, and the TFLOP/s the engine's time means for the network's
 multiply-adds (2 x MACs of every conv, counted from the layer table).  270 x 480 is a 1080p frame at the detector's scale 0.25.
+--precision bf16 times the bf16 handle instead; both: the fp32 and the bf16 engine alternate in the same rounds of one process
+(as tools/hubert_bench.py does it), the line carries both times and their ratio, and the torch baseline is left out.
 
 The per-kernel table comes from a profiler run of its own, never timed:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/facedet_bench.py --batches 8 --no-baseline
@@ -51,7 +53,7 @@ def stats_table(directory: str, forwards: int, out_csv):
     if not paths:
         raise SystemExit(f"no *kernel_stats.csv under {directory}")
     with open(paths[-1], newline="") as f:
-        rows = [r for r in csv.DictReader(f) if "det_" in r["Name"] or "pw_gemm" in r["Name"]]
+        rows = [r for r in csv.DictReader(f) if "det_" in r["Name"] or "det16_" in r["Name"] or "pw_gemm" in r["Name"]]
     total = sum(float(r["TotalDurationNs"]) for r in rows)
     table = [{"kernel": r["Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", ""),
               "calls_per_forward": round(float(r["Calls"]) / forwards, 2),
@@ -84,6 +86,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-baseline", action="store_true")
+    ap.add_argument("--precision", choices=("fp32", "bf16", "both"), default="fp32")
     ap.add_argument("--json")
     ap.add_argument("--stats-from")
     ap.add_argument("--forwards", type=int, default=0)
@@ -111,7 +114,11 @@ def main():
     from calipsync_amd import facedet, recipe
     h, w = (int(v) for v in a.hw.split(","))
     sd = recipe.make_s3fd_state_dict()
-    eng = facedet.S3FDEngine(sd)
+    both = a.precision == "both"
+    eng = facedet.S3FDEngine(sd, precision="fp32" if both else a.precision)
+    eng16 = facedet.S3FDEngine(sd, precision="bf16") if both else None
+    if both:
+        a.no_baseline = True
     sd_dev = {k: torch.from_numpy(v).cuda() for k, v in sd.items()}
     pr = s3fd_ref.priors(h, w, facedet.map_sizes(h, w)).cuda()
     mean = torch.from_numpy(facedet.IMG_MEAN).cuda()
@@ -129,6 +136,8 @@ def main():
             return eng.forward_u8(frames)
 
         fns = [("engine", engine_forward)] + ([] if a.no_baseline else [("torch", torch_forward)])
+        if both:
+            fns.append(("bf16", lambda: eng16.forward_u8(frames)))
         for _n, fn in fns:
             for _ in range(a.warmup):
                 fn()
@@ -137,13 +146,19 @@ def main():
             for n, fn in fns:
                 times[n].append(timeit(fn, a.steps))
         t = statistics.median(times["engine"])
-        res = {"batch": b, "hw": [h, w], "priors": facedet.n_priors(h, w), "engine_ms": t * 1e3, "engine_ms_rounds": [x * 1e3 for x in times["engine"]],
+        res = {"batch": b, "hw": [h, w], "precision": eng.precision, "priors": facedet.n_priors(h, w), "engine_ms": t * 1e3, "engine_ms_rounds": [x * 1e3 for x in times["engine"]],
                "frames_per_s": b / t, "launches_per_forward": LAUNCHES, "gflop_per_frame": flops(h, w) / 1e9, "tflops": flops(h, w) * b / t / 1e12}
         if not a.no_baseline:
             tt = statistics.median(times["torch"])
             d = (torch_forward() - engine_forward()).abs().amax(dim=(0, 1))
             res.update({"torch_ms": tt * 1e3, "torch_ms_rounds": [x * 1e3 for x in times["torch"]], "torch_frames_per_s": b / tt,
                         "speedup_vs_torch": tt / t, "max_abs_diff_vs_torch": {"score": float(d[0]), "box": float(d[1:].max())}})
+        if both:
+            t16 = statistics.median(times["bf16"])
+            d = (eng16.forward_u8(frames) - engine_forward()).abs().amax(dim=(0, 1))
+            res.update({"bf16_ms": t16 * 1e3, "bf16_ms_rounds": [x * 1e3 for x in times["bf16"]], "bf16_frames_per_s": b / t16,
+                        "bf16_tflops": flops(h, w) * b / t16 / 1e12, "speedup_bf16_vs_fp32": t / t16,
+                        "max_abs_diff_bf16_vs_fp32": {"score": float(d[0]), "box": float(d[1:].max())}})
         lines.append(res)
         print(json.dumps(res), flush=True)
     if a.json:
