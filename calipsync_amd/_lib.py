@@ -192,6 +192,12 @@ _PROTOS = {
     "casync_op_s3fd16_l2norm": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_int, C.c_void_p]),
     "casync_op_s3fd16_head": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_void_p]),
+    # face pipeline between the two networks (additive to ABI 13); geom is HOST memory, everything else device
+    "casync_op_resize_linear_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                             C.c_void_p]),
+    "casync_op_face_crops192": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "casync_op_s3fd_candidates": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, c_f32p, C.c_void_p]),
+    "casync_op_landmarks_finalize": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -14,6 +14,9 @@
   ``calipsync_amd.landmarks.LandmarkDetector``.  The ``cv2.resize(fx=s, fy=s, INTER_LINEAR)`` in front of the network
   (main.py:34) uses cv2 where it imports, else Pillow's bilinear filter; cv2 is not in the build image, so that step is NOT
   pinned against the reference, like ``landmarks.resize192``.  ``scale=1`` bypasses it entirely.
+* ``S3FDDetector.detect_device`` / ``dense_device`` are the same detector on frames resident on the device (DESIGN section
+  8e): the downscale is a kernel with OpenCV's arithmetic on every box (``calipsync_amd.face_ops``), and only the rows above
+  ``CONF_THRESH`` come back to the host.
 """
 from __future__ import annotations
 
@@ -339,7 +342,9 @@ class S3FDDetector:
         self.scale = scale
         self.precision = precision
         self.last_detection = None
+        self.candidate_cap = 1024       # detect_device: rows per frame brought back compacted; a frame with more falls back to its dense rows
         self.det_net = self._make_engine(state_dict, device, precision)
+        self._stager = None
 
     @staticmethod
     def _make_engine(state_dict, device, precision="fp32"):
@@ -363,18 +368,54 @@ class S3FDDetector:
         """S3FD.detect_faces (main.py:26-60) behind the network: the rows of one image"""
         return detect_faces_rows(detect_output(dense[None])[0], image.shape[1], image.shape[0], self.conf_threshold)
 
+    def _detection(self, bboxes: np.ndarray):
+        """detect_face.py:49-75 for one image's rows: (bboxes_xywh, indices), or the last detection where there is none"""
+        if len(bboxes) == 0:                                       # detect_face.py:49-56
+            return (np.array([]), []) if self.last_detection is None else self.last_detection
+        bboxes_np = np.array([box[:-1] for box in bboxes])
+        converted = np.column_stack((bboxes_np[:, :2], bboxes_np[:, 2:] - bboxes_np[:, :2]))
+        current = (converted, list(range(len(bboxes))))
+        self.last_detection = current
+        return current
+
     def detect(self, images: Sequence[np.ndarray]):
+        return [self._detection(self.detect_faces(img, dense)) for img, dense in zip(images, self.dense(images))]
+
+    # ---- the same detector on frames resident on the device -----------------------------------------------------------
+    def frames_to_device(self, frames) -> torch.Tensor:
+        """a uint8 [B,H,W,3] device tensor as it is; equal-sized numpy frames through one pinned buffer in one copy"""
+        from . import face_ops
+        if self._stager is None:
+            self._stager = face_ops.FrameStager(self.det_net.device)
+        return self._stager.upload(frames, "S3FDDetector.detect_device", "detect / dense")
+
+    def dense_device(self, frames) -> torch.Tensor:
+        """frames -> the dense det [B,P,5] ON THE DEVICE: the downscale (cv2.resize(fx=scale, fy=scale) in OpenCV's arithmetic;
+        scale == 1 skips it) and forward_u8, nothing downloaded."""
+        from . import face_ops
+        frames = self.frames_to_device(frames)
+        small = frames if self.scale == 1 else face_ops.resize_frames_u8(frames, fx=self.scale)
+        return self.det_net.forward_u8(small)
+
+    def detect_device(self, frames):
+        """detect() for frames on the device (or equal-sized numpy frames, uploaded once): only the per-frame counts and the
+        rows above CONF_THRESH, compacted in prior order on the device, come back; the NMS and everything behind it is the host
+        code of detect() on those rows, which it would have selected from the dense tensor in the same order."""
+        from . import face_ops
+        frames = self.frames_to_device(frames)
+        b, height, width = frames.shape[:3]
+        if b == 0:
+            return []
+        det = self.dense_device(frames)
+        cap = max(1, min(int(self.candidate_cap), det.shape[1]))
+        counts_dev, rows_dev = face_ops.s3fd_candidates(det, CONF_THRESH, cap)
+        counts = counts_dev.cpu().numpy()
+        rows = rows_dev[:, :max(1, min(int(counts.max()), cap))].cpu().numpy()
         detections = []
-        for img, dense in zip(images, self.dense(images)):
-            bboxes = self.detect_faces(img, dense)
-            if len(bboxes) == 0:                                   # detect_face.py:49-56
-                detections.append((np.array([]), []) if self.last_detection is None else self.last_detection)
-                continue
-            bboxes_np = np.array([box[:-1] for box in bboxes])
-            converted = np.column_stack((bboxes_np[:, :2], bboxes_np[:, 2:] - bboxes_np[:, :2]))
-            current = (converted, list(range(len(bboxes))))
-            self.last_detection = current
-            detections.append(current)
+        for i in range(b):
+            n = int(counts[i])
+            cand = rows[i, :n] if n <= cap else det[i].cpu().numpy()        # more than cap: that frame's dense rows
+            detections.append(self._detection(detect_faces_rows(detect_output(cand[None])[0], width, height, self.conf_threshold)))
         return detections
 
     def __call__(self, images: Sequence[np.ndarray]):

@@ -9,6 +9,8 @@
 * ``LandmarkDetector`` keeps ``LipDetector.detect_landmarks``.  Face detection stays outside: boxes or a detector callable
   are handed in.  The 192 x 192 resize uses ``cv2.resize`` where cv2 imports, else Pillow's bilinear filter; cv2 is not in
   the build image, so that step is NOT pinned against the reference, like the f1 resize of the frame loop.
+* ``LandmarkDetector.detect_landmarks_device`` is the same call on frames resident on the device: crops,
+  resize and the closing arithmetic are kernels (``calipsync_amd.face_ops``) with OpenCV's resize arithmetic on every box.
 """
 from __future__ import annotations
 
@@ -329,6 +331,7 @@ class LandmarkDetector:
             raise ValueError(f"mean_face has {self.mean_face.size} values, {2 * N_LANDMARKS} are needed")
         self.face_detector = face_detector
         self.pfld_backbone = self._make_engine(state_dict, device)
+        self._stager = None             # detect_landmarks_device: the pinned upload buffer and mean_face on the device, made on first use
 
     @staticmethod
     def _make_engine(state_dict, device):
@@ -355,6 +358,27 @@ class LandmarkDetector:
             cropped = np.pad(cropped, ((dy, edy), (dx, edx)) + ((0, 0),) * (img.ndim - 2))
             y1, x1 = y1 - dy, x1 - dx
         return cropped, (x1, y1)
+
+    @staticmethod
+    def _crop_geometry(height: int, width: int, box: Sequence[float]) -> Tuple[int, int, int, int]:
+        """The integer arithmetic of _crop without the pixels -> (x1, y1, w, h): _crop(img, box) returns a crop of shape (h, w)
+        at offset (x1, y1) whose pixel (y, x) is img[y1 + y, x1 + x] inside the image and 0 outside.  That includes squares
+        that miss the image, where numpy's slice (a negative end counts from the far side) and the padding leave a crop that
+        is not square."""
+        bx, by = int(box[0]), int(box[1])
+        bw, bh = int(box[2]), int(box[3])
+        size = int(max(bw, bh) * 1.05)
+
+        def axis(lo: int, extent: int):
+            hi = lo + size
+            before, after = max(0, -lo), max(0, hi - extent)
+            lo, hi = max(0, lo), min(extent, hi)
+            kept = len(range(*slice(lo, hi).indices(extent)))        # what img[lo:hi] keeps along this axis
+            return lo - before, before + kept + after
+
+        x1, w = axis((2 * bx + bw) // 2 - size // 2, width)
+        y1, h = axis((2 * by + bh) // 2 - size // 2, height)
+        return x1, y1, w, h
 
     def landmarks_from_crops(self, crops192_u8, sizes, offsets) -> List[np.ndarray]:
         """crops192_u8 [N,192,192,3] uint8 (one forward), sizes [(w, h)] of the crops before the resize, offsets [(x, y)]
@@ -394,6 +418,41 @@ class LandmarkDetector:
                 if results[i] is None:
                     results[i] = []
                 results[i].append(lm)
+        return results
+
+    def detect_landmarks_device(self, frames, boxes=None):
+        """detect_landmarks on frames resident on the device: frames is a uint8 [B,H,W,3] device tensor, or equal-sized numpy
+        frames (uploaded once, and shared with face_detector.detect_device where the detector has it).  The crops are cut and
+        resized, PFLD runs and the landmarks are scaled and truncated on the device; one download brings the int32 landmarks
+        back.  Same return value as detect_landmarks."""
+        from . import face_ops
+        dev = self.pfld_backbone.device
+        if self._stager is None:
+            self._stager = face_ops.FrameStager(dev)
+            self._mean_face_dev = torch.from_numpy(self.mean_face).to(dev)
+        frames_dev = self._stager.upload(frames, "LandmarkDetector.detect_landmarks_device", "detect_landmarks")
+        n_frames, height, width = frames_dev.shape[:3]
+        if boxes is None:
+            if self.face_detector is None:
+                raise ValueError("detect_landmarks_device: no boxes and no face_detector")
+            if hasattr(self.face_detector, "detect_device"):
+                boxes = [[tuple(float(v) for v in box) for box in bs] for bs, _ in self.face_detector.detect_device(frames_dev)]
+            else:
+                boxes = self.face_detector(list(frames_dev.cpu().numpy()) if isinstance(frames, torch.Tensor) else list(frames))
+        geom, owner = [], []
+        for i, bs in zip(range(n_frames), boxes):
+            for box in (bs if bs is not None else []):
+                geom.append((i,) + self._crop_geometry(height, width, box))
+                owner.append(i)
+        results: List[Optional[List[np.ndarray]]] = [None] * n_frames
+        if geom:
+            table = np.asarray(geom, dtype=np.int32)
+            y = self.pfld_backbone.forward_u8(face_ops.face_crops192(frames_dev, table))
+            lms = face_ops.landmarks_finalize(y, self._mean_face_dev, table).cpu().numpy()
+            for i, lm in zip(owner, lms):
+                if results[i] is None:
+                    results[i] = []
+                results[i].append(lm.copy())
         return results
 
 

@@ -44,7 +44,9 @@ enum {
 /* Bumped on every change of a prototype, struct layout or the packed-weight layout; the ctypes
  * host (calipsync_amd/_lib.py) refuses a library whose version differs from the one it binds.   */
 #define CASYNC_ABI_VERSION 13  /* 12: S3FD face detector handle (casync_s3fd_*, casync_op_s3fd_*); 13: its bf16 precision
-                                * (casync_s3fd_create_ex, _precision, _workspace_bytes_ex, casync_op_s3fd16_*) */
+                                * (casync_s3fd_create_ex, _precision, _workspace_bytes_ex, casync_op_s3fd16_*).  The face-pipeline
+                                * operators at the end of this file (casync_op_resize_linear_u8, _face_crops192, _s3fd_candidates,
+                                * _landmarks_finalize) were added under 13: new symbols only, no prototype or layout changed */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -542,6 +544,39 @@ int  casync_op_s3fd16_widen(const void* in, float* out, int64_t n, casync_stream
 int  casync_op_s3fd16_l2norm(const void* in, void* out, int64_t rows, int c, casync_stream stream);
 int  casync_op_s3fd16_head(const void* in, const float* w, const float* bias, float* loc, float* conf, int batch, int h, int w_,
                            int c, int priors, int first_prior, int maxout, casync_stream stream);
+
+/* ---- face pipeline between S3FD and PFLD (additive to ABI 13) ---------------- */
+/* The pixel and row work that joins the two face networks, so frames resident on the device reach int32 landmarks without
+ * a pixel crossing the host.  Every entry checks its arguments before any device call (CASYNC_ERR_ARG and a message
+ * otherwise), launches on `stream` and returns without synchronising; none allocates or uses atomics.
+ *
+ * resize_linear_u8: cv2.resize(INTER_LINEAR) on uint8 (S3FD.detect_faces, tools/s3fd/main.py:34), as restated from OpenCV
+ *   4.x's resize.cpp: src [batch,sh,sw,3] -> dst [batch,dh,dw,3], both HWC.  scale_x / scale_y are source per destination,
+ *   passed in as cv2 derives them: (double)1 / ((double)dst / src) for cv2.resize(src, dsize), 1 / f for cv2.resize(src, (0, 0),
+ *   fx=f, fy=f) with dsize = (round-half-even(sw f), round-half-even(sh f)).  Equal sizes copy; (sw, sh) == (2 dw, 2 dh) is the
+ *   INTER_AREA mean (a + b + c + d + 2) >> 2 that cv::resize switches to; otherwise fx = (float)((d + 0.5) scale - 0.5), floor,
+ *   the two border clamps on columns, rows clipped with their weights kept, coefficients cvRound(c 2048),
+ *   (((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2.  batch 1..65535, sides 1..32767, scales in (0, 32768].
+ * face_crops192: LipDetector's crop and cv2.resize(crop, (192, 192)) (lip_detector.py:46-80) without the crop: frames
+ *   [n_frames,H,W,3] uint8 on the device; geom [n_crops][5] int32 = {frame, x1, y1, w, h} in HOST memory, read before the call
+ *   returns.  Record i names a virtual h x w image whose pixel (y, x) is frames[frame, y1 + y, x1 + x] inside the frame and 0
+ *   outside (x1, y1 may be negative, the window may miss the frame altogether); crops192[i] [192,192,3] is resize_linear_u8 of
+ *   it, the identity (192) and 2x (384) cases included.  w < 1, h < 1, a side above 32767, |x1| or |y1| above 2^24, or frame
+ *   outside [0, n_frames) is refused, with the record's index, before anything is launched.
+ * s3fd_candidates: Detect.forward's selection (box_utils.py:150-156) on the device: det [batch,P,5] -> rows [batch,cap,5],
+ *   rows[b, :min(counts[b], cap)] = the rows of det[b] whose score det[b,:,0] > thresh, in prior order; counts[b] is the number
+ *   of such rows even beyond cap; rows past it are not written.  A NaN score fails the comparison.  1 <= cap <= P.
+ * landmarks_finalize: lip_detector.py:106-114: y [n,220] (casync_pfld_forward's output) and mean_face [220] on the device,
+ *   geom [n][5] in HOST memory as above (frame is ignored) -> out [n,110,2] int32 = (int32)((y + mean) * {w, h} + {x1, y1}),
+ *   float32 with every operation rounded on its own, truncated toward zero.  Specified for finite results within int32.   */
+int  casync_op_resize_linear_u8(const uint8_t* src, int batch, int sh, int sw, uint8_t* dst, int dh, int dw, double scale_x,
+                                double scale_y, casync_stream stream);
+int  casync_op_face_crops192(const uint8_t* frames, int n_frames, int H, int W, const int32_t* geom, int n_crops, uint8_t* crops192,
+                             casync_stream stream);
+int  casync_op_s3fd_candidates(const float* det, int batch, int P, float thresh, int cap, int32_t* counts, float* rows,
+                               casync_stream stream);
+int  casync_op_landmarks_finalize(const float* y, const float* mean_face, const int32_t* geom, int n, int32_t* out,
+                                  casync_stream stream);
 
 #ifdef __cplusplus
 }
