@@ -198,6 +198,9 @@ _PROTOS = {
     "casync_op_face_crops192": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "casync_op_s3fd_candidates": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, c_f32p, C.c_void_p]),
     "casync_op_landmarks_finalize": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # S3FD's two NMS passes behind s3fd_candidates (additive to ABI 13); faces is float64, detect_out / detect_n may be null
+    "casync_op_s3fd_nms": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, c_f32p,
+                                     C.c_void_p, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -5,6 +5,9 @@
 * ``face_crops192(frames, geom)``: the 192 x 192 PFLD crops of the records ``{frame, x1, y1, w, h}``.
 * ``s3fd_candidates(det, thresh, cap)``: per frame the rows of the dense ``det`` above ``thresh``, in prior order.
 * ``landmarks_finalize(y, mean_face, geom)``: PFLD's output to int32 landmarks in frame pixels.
+* ``s3fd_nms(counts, rows, width, height, conf_th)``: S3FD's two NMS passes on those candidate rows (csrc/face_nms.hip): per
+  frame a status and the float64 face rows ``S3FD.detect_faces`` returns, bit for bit ``facedet.detect_output`` +
+  ``facedet.detect_faces_rows`` (tests/test_face_nms_gpu.py).
 
 The arithmetic is OpenCV's as ``oracle/frame_ops_oracle.py`` restates it (bit for bit: tests/test_face_ops_gpu.py); like the
 frame loop's, it is not pinned against the real cv2.  Every call launches on the current stream and does not synchronise.
@@ -20,6 +23,9 @@ from . import _lib
 
 FACE = 192
 GEOM_WORDS = 5          # frame, x1, y1, w, h
+NMS_TOP_K = 750         # rows of faces / detect_out per frame (Detect.top_k)
+NMS_MAX_CAP = 1024      # candidate rows per frame the NMS kernel takes
+NMS_OVER_CAP, NMS_INDEX_ERROR = -1, -2      # status of a frame with more rows than cap / on which the reference raises IndexError
 
 
 class FrameStager:
@@ -145,6 +151,49 @@ def s3fd_candidates(det: torch.Tensor, thresh: float, cap: int, counts: Optional
                                                _stream(det.device))
     _lib.check(st, "casync_op_s3fd_candidates")
     return counts, rows
+
+
+def s3fd_nms(counts: torch.Tensor, rows: torch.Tensor, width: int, height: int, conf_th: float, status: Optional[torch.Tensor] = None,
+             faces: Optional[torch.Tensor] = None, detect_out: Optional[torch.Tensor] = None, detect_n: Optional[torch.Tensor] = None):
+    """counts [B] int32 and rows [B,cap,5] float32 on the device, as s3fd_candidates wrote them -> (status [B] int32, faces
+    [B,750,5] float64): faces[b, :status[b]] = (x1, y1, x2, y2, score) of frame b in pixels of the width x height frame, what
+    facedet.detect_faces_rows(facedet.detect_output(rows[b, :counts[b]])) returns; status NMS_OVER_CAP (-1) where counts[b] >
+    cap (nothing written), NMS_INDEX_ERROR (-2) where 750 rows pass conf_th.  Rows behind status[b] are not written.
+    With detect_out [B,750,5] float32 and detect_n [B] int32 given, they also receive Detect.forward's kept rows (score, box) and
+    their number, and the call returns (status, faces, detect_out, detect_n)."""
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != 5 or not rows.is_cuda:
+        raise ValueError("s3fd_nms: rows must be a float32 [B,cap,5] device tensor")
+    b, cap = rows.shape[:2]
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or tuple(counts.shape) != (b,) or counts.device != rows.device:
+        raise ValueError(f"s3fd_nms: counts must be {b} int32 values on rows' device")
+    if not 1 <= cap <= NMS_MAX_CAP:
+        raise ValueError(f"s3fd_nms: {cap} rows per frame, the kernel takes 1..{NMS_MAX_CAP}")
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError(f"s3fd_nms: frame of {width} x {height} (w x h)")
+    rows, counts = rows.contiguous(), counts.contiguous()
+    if (detect_out is None) != (detect_n is None):
+        raise ValueError("s3fd_nms: detect_out and detect_n go together")
+    stage1 = detect_out is not None
+
+    def given(t, shape, dtype, name):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=rows.device)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or t.device != rows.device or not t.is_contiguous():
+            raise ValueError(f"s3fd_nms: {name} must be a contiguous {dtype} {list(shape)} tensor on rows' device")
+        return t
+
+    status = given(status, (b,), torch.int32, "status")
+    faces = given(faces, (b, NMS_TOP_K, 5), torch.float64, "faces")
+    if stage1:
+        detect_out = given(detect_out, (b, NMS_TOP_K, 5), torch.float32, "detect_out")
+        detect_n = given(detect_n, (b,), torch.int32, "detect_n")
+    if b:
+        st = _lib.load().casync_op_s3fd_nms(rows.data_ptr(), counts.data_ptr(), b, cap, width, height, float(conf_th), status.data_ptr(),
+                                            faces.data_ptr(), detect_out.data_ptr() if stage1 else None,
+                                            detect_n.data_ptr() if stage1 else None, _stream(rows.device))
+        _lib.check(st, "casync_op_s3fd_nms")
+    return (status, faces, detect_out, detect_n) if stage1 else (status, faces)
 
 
 def landmarks_finalize(y: torch.Tensor, mean_face: torch.Tensor, geom, out: Optional[torch.Tensor] = None) -> torch.Tensor:

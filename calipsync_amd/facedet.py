@@ -16,7 +16,8 @@
   pinned against the reference, like ``landmarks.resize192``.  ``scale=1`` bypasses it entirely.
 * ``S3FDDetector.detect_device`` / ``dense_device`` are the same detector on frames resident on the device (DESIGN section
   8e): the downscale is a kernel with OpenCV's arithmetic on every box (``calipsync_amd.face_ops``), and only the rows above
-  ``CONF_THRESH`` come back to the host.
+  ``CONF_THRESH`` come back to the host (``nms="host"``) or, with both NMS passes on the device too (``nms="device"``,
+  ``face_ops.s3fd_nms``), only the faces.
 """
 from __future__ import annotations
 
@@ -43,6 +44,8 @@ IMG_MEAN = np.array([123.0, 117.0, 104.0], dtype=np.float32)   # per channel of 
 # Detect() and the callers' constants (box_utils.py:131-133, main.py:57)
 CONF_THRESH, NMS_THRESH, NMS_TOP_K, TOP_K, FINAL_NMS = 0.05, 0.3, 5000, 750, 0.1
 PRECISIONS = {"fp32": 0, "bf16": 1}     # casync_s3fd_create_ex
+NMS_PLACES = ("device", "host")         # S3FDDetector(nms=...): where detect_device runs the two NMS passes
+NMS_HEAD = 32                           # detect_device, nms="device": face rows per frame that come back with the status in one copy
 
 
 def manifest() -> List[Tuple[str, Tuple[int, ...]]]:
@@ -328,12 +331,16 @@ class S3FDDetector:
     """The reference's S3FDFaceDetector(weight_path, conf_threshold) on the HIP engine.  weight_base_dir holds
     ``sfd_face.pth``; or pass state_dict.  detect(images) -> [(bboxes_xywh float64 [n,4], indices)] as detect_face.py:27-75;
     calling the object gives per image the list of (x, y, w, h) boxes LandmarkDetector's face_detector returns.  Images of
-    one size run through one batched forward."""
+    one size run through one batched forward.  nms says where detect_device runs the two NMS passes behind the network:
+    "device" (face_ops.s3fd_nms) or "host" (numpy on the downloaded candidate rows); the detections are the same.  The default
+    is "host" until tools/face_pipeline_bench.py --nms host,device has been run on an MI355X."""
 
     def __init__(self, weight_base_dir: Optional[str] = None, *, state_dict=None, conf_threshold: float = 0.1, scale: float = 0.25,
-                 device: str = "cuda:0", precision: str = "fp32"):
+                 device: str = "cuda:0", precision: str = "fp32", nms: str = "host"):
         if precision not in PRECISIONS:
             raise ValueError(f"S3FDDetector: precision {precision!r}, expected one of {sorted(PRECISIONS)}")
+        if nms not in NMS_PLACES:
+            raise ValueError(f"S3FDDetector: nms {nms!r}, expected one of {list(NMS_PLACES)}")
         if state_dict is None:
             if weight_base_dir is None:
                 raise ValueError("S3FDDetector: weight_base_dir or state_dict is needed")
@@ -341,6 +348,7 @@ class S3FDDetector:
         self.conf_threshold = conf_threshold
         self.scale = scale
         self.precision = precision
+        self.nms = nms
         self.last_detection = None
         self.candidate_cap = 1024       # detect_device: rows per frame brought back compacted; a frame with more falls back to its dense rows
         self.det_net = self._make_engine(state_dict, device, precision)
@@ -398,17 +406,26 @@ class S3FDDetector:
         return self.det_net.forward_u8(small)
 
     def detect_device(self, frames):
-        """detect() for frames on the device (or equal-sized numpy frames, uploaded once): only the per-frame counts and the
-        rows above CONF_THRESH, compacted in prior order on the device, come back; the NMS and everything behind it is the host
-        code of detect() on those rows, which it would have selected from the dense tensor in the same order."""
-        from . import face_ops
+        """detect() for frames on the device (or equal-sized numpy frames, uploaded once).  nms == "host": only the per-frame
+        counts and the rows above CONF_THRESH, compacted in prior order on the device, come back; the NMS and everything behind
+        it is the host code of detect() on those rows, which it would have selected from the dense tensor in the same order.
+        nms == "device": both NMS passes run on those rows where they are and only each frame's face rows come back
+        (_faces_device); _detection, with its last_detection state, is the same host code frame by frame."""
         frames = self.frames_to_device(frames)
-        b, height, width = frames.shape[:3]
-        if b == 0:
+        if frames.shape[0] == 0:
             return []
-        det = self.dense_device(frames)
+        return self.detections_from_dense(self.dense_device(frames), frames.shape[2], frames.shape[1])
+
+    def detections_from_dense(self, det: torch.Tensor, width: int, height: int):
+        """detect_device behind the network: the dense det [B,P,5] on the device, of frames of width x height -> detections"""
+        from . import face_ops
+        if self.nms not in NMS_PLACES:
+            raise ValueError(f"S3FDDetector: nms {self.nms!r}, expected one of {list(NMS_PLACES)}")
+        b = det.shape[0]
         cap = max(1, min(int(self.candidate_cap), det.shape[1]))
         counts_dev, rows_dev = face_ops.s3fd_candidates(det, CONF_THRESH, cap)
+        if self.nms == "device":
+            return self._faces_device(det, counts_dev, rows_dev, width, height)
         counts = counts_dev.cpu().numpy()
         rows = rows_dev[:, :max(1, min(int(counts.max()), cap))].cpu().numpy()
         detections = []
@@ -416,6 +433,32 @@ class S3FDDetector:
             n = int(counts[i])
             cand = rows[i, :n] if n <= cap else det[i].cpu().numpy()        # more than cap: that frame's dense rows
             detections.append(self._detection(detect_faces_rows(detect_output(cand[None])[0], width, height, self.conf_threshold)))
+        return detections
+
+    def _faces_device(self, det: torch.Tensor, counts_dev: torch.Tensor, rows_dev: torch.Tensor, width: int, height: int):
+        """detect_device behind the candidate rows with the NMS on the device: ONE download of [B, 1 + NMS_HEAD * 5] float64 =
+        each frame's status and its first NMS_HEAD face rows; a frame with more faces costs one more copy, a frame with more
+        candidates than the kernel takes (status -1) goes through the host code on its dense rows, as with nms == "host"."""
+        from . import face_ops
+        b = det.shape[0]
+        rows_dev = rows_dev[:, :face_ops.NMS_MAX_CAP]            # (a larger candidate_cap: frames beyond 1024 rows fall back)
+        status_dev, faces_dev = face_ops.s3fd_nms(counts_dev, rows_dev, width, height, self.conf_threshold)
+        head = torch.empty((b, 1 + NMS_HEAD * 5), dtype=torch.float64, device=det.device)
+        head[:, 0].copy_(status_dev)
+        head[:, 1:].unflatten(1, (NMS_HEAD, 5)).copy_(faces_dev[:, :NMS_HEAD])
+        head = head.cpu().numpy()
+        detections = []
+        for i in range(b):
+            n = int(head[i, 0])
+            if n == face_ops.NMS_INDEX_ERROR:
+                raise IndexError(f"index {TOP_K} is out of bounds for axis 1 with size {TOP_K}")     # (the host walk's own error)
+            if n == face_ops.NMS_OVER_CAP:
+                faces = detect_faces_rows(detect_output(det[i].cpu().numpy()[None])[0], width, height, self.conf_threshold)
+            elif n <= NMS_HEAD:
+                faces = head[i, 1:1 + n * 5].reshape(n, 5)
+            else:
+                faces = faces_dev[i, :n].cpu().numpy()
+            detections.append(self._detection(faces))
         return detections
 
     def __call__(self, images: Sequence[np.ndarray]):

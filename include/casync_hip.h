@@ -46,7 +46,7 @@ enum {
 #define CASYNC_ABI_VERSION 13  /* 12: S3FD face detector handle (casync_s3fd_*, casync_op_s3fd_*); 13: its bf16 precision
                                 * (casync_s3fd_create_ex, _precision, _workspace_bytes_ex, casync_op_s3fd16_*).  The face-pipeline
                                 * operators at the end of this file (casync_op_resize_linear_u8, _face_crops192, _s3fd_candidates,
-                                * _landmarks_finalize) were added under 13: new symbols only, no prototype or layout changed */
+                                * _landmarks_finalize) and casync_op_s3fd_nms were added under 13: new symbols only, no prototype or layout changed */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -577,6 +577,30 @@ int  casync_op_s3fd_candidates(const float* det, int batch, int P, float thresh,
                                casync_stream stream);
 int  casync_op_landmarks_finalize(const float* y, const float* mean_face, const int32_t* geom, int n, int32_t* out,
                                   casync_stream stream);
+
+/* ---- S3FD's two NMS passes on the device (additive to ABI 13: a new symbol, nothing else changed) ---------------- */
+/* What the reference runs on the host behind the network, on the rows casync_op_s3fd_candidates wrote: Detect.forward's nms
+ * (box_utils.py:62-173), S3FD.detect_faces' walk, scaling and rows (main.py:45-58) and Girshick's nms_ (box_utils.py:7-38).
+ * rows [batch,cap,5] float32 = (score, x1, y1, x2, y2) in prior order and counts [batch] int32, both on the device; per frame
+ * b with n = counts[b]:
+ *   n > cap:  status[b] = -1 and nothing else of the frame is written (the caller takes that frame's dense rows to the host);
+ *   stage 1 (float32): area = (x2 - x1) * (y2 - y1); rows are visited by descending score, among equal scores the higher row
+ *     index first (the stable ascending argsort popped from its end); the first surviving row i is kept and a later row j
+ *     survives iff inter / ((area[j] - inter) + area[i]) <= 0.3f with inter = max(min(x2) - max(x1), 0) * max(min(y2) -
+ *     max(y1), 0) (a NaN from 0 / 0 drops the row); at most 750 rows are kept.  detect_out [batch,750,5] float32 and detect_n
+ *     [batch] int32 (both null, or both given) receive the kept rows (score, box) and their number: Detect.forward's output
+ *     for the face class; rows behind detect_n[b] are not written.  (nms_top_k = 5000 cannot bite at cap <= 1024.)
+ *   stage 2: the leading kept rows with score > conf_th (float32; behind the kept rows the reference's array holds zeros); if
+ *     all 750 pass, status[b] = -2 (the reference's IndexError).  Else pt = box * (width, height, width, height) in float32,
+ *     widened with the score to float64; areas = (x2 - x1) * (y2 - y1); visited by descending score, among equal scores the
+ *     higher index first (argsort(kind="stable")[::-1]; the reference's default argsort leaves ties open); j survives iff
+ *     inter / ((areas[i] + areas[j]) - inter) <= 0.1.  faces[b, :status[b]] float64 = (x1, y1, x2, y2, score) in keep order,
+ *     status[b] = their number (0 for a frame without candidates); faces [batch,750,5], rows behind status[b] not written.
+ * Every operation is the IEEE one of its type, so the result equals calipsync_amd.facedet's numpy restatement bit for bit
+ * (finite boxes, no NaN score).  One 256-lane workgroup per frame, static LDS only, no atomics, no allocation, no
+ * synchronisation.  batch 1..65535, cap 1..1024, width and height >= 1.                                                   */
+int  casync_op_s3fd_nms(const float* rows, const int32_t* counts, int batch, int cap, int width, int height, float conf_th,
+                        int32_t* status, double* faces, float* detect_out, int32_t* detect_n, casync_stream stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,77 @@
+"""The ledger rule for the seventh object directory, calipsync_amd/lib/obj_nms/ (no GPU): every kernel compiled from
+csrc/face_nms.hip has a case in tests/kernel_ledger_nms.py and the other way round, no kernel name occurs in another object
+directory or another ledger, the kernel uses no scratch, and the build's op_sel check stays clean on the object."""
+import os
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_resources  # noqa: E402
+
+import kernel_ledger  # noqa: E402
+import kernel_ledger_det  # noqa: E402
+import kernel_ledger_det16  # noqa: E402
+import kernel_ledger_face  # noqa: E402
+import kernel_ledger_hb16  # noqa: E402
+import kernel_ledger_lmk  # noqa: E402
+import kernel_ledger_nms  # noqa: E402
+from calipsync_amd import build  # noqa: E402
+
+pytestmark = pytest.mark.skipif(not kernel_resources.tools_available(), reason="llvm binutils of the ROCm image not found")
+
+OTHER_DIRS = (build.OBJ_DIR, build.OBJ_DIR_HB16, build.OBJ_DIR_LMK, build.OBJ_DIR_DET, build.OBJ_DIR_DET16, build.OBJ_DIR_FACE)
+
+
+@pytest.fixture(scope="module")
+def objects():
+    build.build()                      # no-op when the library is up to date
+    d = build.OBJ_DIR_NMS
+    if not os.path.isdir(d) or not any(f.endswith(".o") for f in os.listdir(d)):
+        build.build(force=True)        # a library shipped without its objects: compile them
+    return [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(".o")]
+
+
+@pytest.fixture(scope="module")
+def table(objects):
+    return kernel_resources.table(build.OBJ_DIR_NMS)
+
+
+def test_the_nms_object_is_in_its_own_directory(objects):
+    assert [os.path.basename(o) for o in objects] == ["face_nms.o"]
+    for d in OTHER_DIRS:
+        assert not os.path.exists(os.path.join(d, "face_nms.o")), d
+
+
+def test_every_nms_kernel_has_a_ledger_case(table):
+    assert table, "no kernel found in lib/obj_nms"
+    missing = sorted(set(table) - set(kernel_ledger_nms.LEDGER))
+    stale = sorted(set(kernel_ledger_nms.LEDGER) - set(table))
+    assert not missing, f"kernel instances without a case in tests/kernel_ledger_nms.py: {missing}"
+    assert not stale, f"ledger entries for kernels lib/obj_nms no longer has: {stale}"
+    empty = [k for k, cs in kernel_ledger_nms.LEDGER.items() if not cs or not all(isinstance(c, kernel_ledger.Case) for c in cs)]
+    assert not empty, empty
+
+
+def test_no_kernel_name_is_in_another_directory_or_ledger(table):
+    other_ledgers = set(kernel_ledger.LEDGER) | set(kernel_ledger_hb16.LEDGER) | set(kernel_ledger_lmk.LEDGER) | \
+        set(kernel_ledger_det.LEDGER) | set(kernel_ledger_det16.LEDGER) | set(kernel_ledger_face.LEDGER)
+    others = set(other_ledgers)
+    for d in OTHER_DIRS:
+        others |= set(kernel_resources.table(d))
+    both = sorted(set(table) & others)
+    assert not both, both
+    assert not set(kernel_ledger_nms.LEDGER) & other_ledgers
+
+
+def test_the_nms_kernel_uses_no_scratch_and_little_lds(table):
+    spills = {k: v["scratch"] for k, v in table.items() if v["scratch"]}
+    assert not spills, spills
+    assert all(0 < v["static_lds"] < 48 * 1024 for v in table.values()), table      # static LDS only, well under the 64 KB of a workgroup
+
+
+def test_nms_object_is_free_of_the_op_sel_erratum(objects):
+    assert objects
+    for obj in objects:
+        assert build.erratum_instructions(obj) == [], obj
