@@ -201,6 +201,11 @@ _PROTOS = {
     # S3FD's two NMS passes behind s3fd_candidates (additive to ABI 13); faces is float64, detect_out / detect_n may be null
     "casync_op_s3fd_nms": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, c_f32p,
                                      C.c_void_p, C.c_void_p]),
+    # a clip resident on the device (additive to ABI 13); rec is HOST memory: [batch][8] int32 = {frame, y0, x0, h, w, valid, region
+    # byte offset, 0}
+    "casync_op_clip_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_i64, C.c_void_p]),
+    "casync_op_clip_compose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_i64, C.c_void_p,
+                                         C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

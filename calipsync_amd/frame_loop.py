@@ -143,6 +143,23 @@ def crop_box(lms, height: int, img_width: int):
     return ymin, ymax, xmin, xmax, width
 
 
+def frame_geometry(lms, height: int, img_width: int):
+    """What the host computes for one frame (infer_api.py:206-231, 281-289): (crop box, pts, valid).  The crop box is
+    ``crop_box``'s; ``pts`` [33,2] int32 are the contour points shifted into the box, scaled to the synthesised square and
+    truncated, or None where the box is empty (``cv2.resize`` would fail: the batch goes back unchanged); ``valid`` is 1 when
+    the box is the width x width square the synthesised crop is pasted into (infer_api.py:320-324)."""
+    ymin, ymax, xmin, xmax, width = crop_box(lms, height, img_width)
+    h, w = ymax - ymin, xmax - xmin
+    if h <= 0 or w <= 0 or width <= 0:
+        return (ymin, ymax, xmin, xmax, width), None, 0
+    fp = np.asarray(lms[:33], dtype=np.float64).copy()          # infer_api.py:281-289
+    fp[:, 0] -= xmin
+    fp[:, 1] -= ymin
+    fp[:, 0] *= width / (xmax - xmin)
+    fp[:, 1] *= width / (ymax - ymin)
+    return (ymin, ymax, xmin, xmax, width), fp.astype(np.int32), int(width == h and width == w)
+
+
 _POOL = None
 
 
@@ -272,6 +289,42 @@ def _mask_kind(mask: np.ndarray) -> int:
     return 0
 
 
+def regions_through_net(net, p_regions: int, p_geom: int, p_pts: int, geom: np.ndarray, regions_bytes: int, *, windows=None,
+                        features=None, frame_indices=None) -> torch.Tensor:
+    """The device work of a batch between its crop regions and its blended regions, enqueued on the current stream of
+    ``net``'s device: ``casync_frame_prepare`` -> ``net`` (``windows``) or ``net.forward_windows`` (``features`` +
+    ``frame_indices``) -> ``casync_frame_paste_back``.  ``p_regions`` / ``p_geom`` / ``p_pts``: device addresses of the packed
+    regions, the [B,12] geometry records and the [B,33,2] points; ``geom`` is the host copy of the records (sizes are taken
+    from it).  Returns ``out_regions`` (``regions_bytes`` uint8, the layout of the regions)."""
+    lib = _lib.load()
+    dev = net._device()
+    stream = _stream(dev)
+    B = geom.shape[0]
+    max_h, max_w = int(geom[:, 1].max()), int(geom[:, 2].max())
+    max_width = int((geom[:, 3] * geom[:, 4]).max())
+    mask_off = int((geom[:, 1].astype(np.int64) * geom[:, 2]).sum())
+    synth_off = int((geom[:, 3].astype(np.int64) * geom[:, 3] * 3 * geom[:, 4]).sum())
+    with torch.cuda.device(dev):
+        crops = torch.empty((B, 168, 168, 3), dtype=torch.uint8, device=dev)
+        x = torch.empty((B, 6, 160, 160), dtype=torch.float32, device=dev)
+        _lib.check(lib.casync_frame_prepare(p_regions, p_geom, B, crops.data_ptr(), x.data_ptr(),
+                                            stream), "casync_frame_prepare")
+        if windows is not None:
+            pred = net(x, windows)
+        else:
+            pred = net.forward_windows(x, features, frame_indices)
+        synth = torch.empty(max(synth_off, 16), dtype=torch.uint8, device=dev)
+        mask_a = torch.empty(mask_off, dtype=torch.uint8, device=dev)
+        mask_b = torch.empty(mask_off, dtype=torch.uint8, device=dev)
+        area = torch.empty(B, dtype=torch.int32, device=dev)
+        out_regions = torch.empty(regions_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.casync_frame_paste_back(
+            p_regions, p_geom, p_pts, crops.data_ptr(), pred.data_ptr(), B, max_h, max_w,
+            max_width, mask_off, synth.data_ptr(), mask_a.data_ptr(), mask_b.data_ptr(), area.data_ptr(),
+            out_regions.data_ptr(), stream), "casync_frame_paste_back")
+    return out_regions
+
+
 def process_batch_device(net, batch_images, batch_landmarks, batch_masks, *, windows=None, features=None,
                          frame_indices=None, copy_frames=True, mask_keys=None):
     """``FrameSynthesizer.process_batch`` with everything between the crop box and the pasted-back frame on the
@@ -319,19 +372,13 @@ def submit_batch_device(net, batch_images, batch_landmarks, batch_masks, *, wind
     for i, (img, lms, mask) in enumerate(zip(batch_images, batch_landmarks, batch_masks)):
         if img is None or img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
             raise ValueError(f"frame {i}: expected a uint8 HxWx3 image")
-        ymin, ymax, xmin, xmax, width = crop_box(lms, img.shape[0], img.shape[1])
+        (ymin, ymax, xmin, xmax, width), fp, valid = frame_geometry(lms, img.shape[0], img.shape[1])
         h, w = ymax - ymin, xmax - xmin
-        if h <= 0 or w <= 0 or width <= 0:
+        if fp is None:
             raise ValueError(f"frame {i}: empty crop box {(ymin, ymax, xmin, xmax)} (cv2.resize would fail)")
         boxes.append((ymin, ymax, xmin, xmax, width))
         regions.append(img[ymin:ymax, xmin:xmax])
-        fp = np.asarray(lms[:33], dtype=np.float64).copy()          # infer_api.py:281-289
-        fp[:, 0] -= xmin
-        fp[:, 1] -= ymin
-        fp[:, 0] *= width / (xmax - xmin)
-        fp[:, 1] *= width / (ymax - ymin)
-        pts[i] = fp.astype(np.int32)
-        valid = int(width == h and width == w)
+        pts[i] = fp
         g = geom[i]
         g[0], g[1], g[2], g[3], g[4], g[5], g[6] = reg_off, h, w, width, valid, synth_off, mask_off
         if mask is not None:
@@ -355,8 +402,6 @@ def submit_batch_device(net, batch_images, batch_landmarks, batch_masks, *, wind
             synth_off += width * width * 3
         if reg_off >= 2 ** 31:
             raise ValueError("batch too large for 32-bit region offsets")
-    max_h, max_w = int(geom[:, 1].max()), int(geom[:, 2].max())
-    max_width = int((geom[:, 3] * geom[:, 4]).max())
     stream = _stream(dev)
     # ONE pinned staging buffer, ONE upload: [crop regions | geom | pts | face masks], 16-B aligned parts
     al = lambda n: (n + 15) & ~15
@@ -406,23 +451,8 @@ def submit_batch_device(net, batch_images, batch_landmarks, batch_masks, *, wind
         # blend kernel was still going to read).
         while cache is not None and net._mask_cache_bytes > _MASK_CACHE_CAP and len(cache) > 1:
             net._mask_cache_bytes -= cache.popitem(last=False)[1].numel()
-        crops = torch.empty((B, 168, 168, 3), dtype=torch.uint8, device=dev)
-        x = torch.empty((B, 6, 160, 160), dtype=torch.float32, device=dev)
-        _lib.check(lib.casync_frame_prepare(p_regions, p_geom, B, crops.data_ptr(), x.data_ptr(),
-                                            stream), "casync_frame_prepare")
-        if windows is not None:
-            pred = net(x, windows)
-        else:
-            pred = net.forward_windows(x, features, frame_indices)
-        synth = torch.empty(max(synth_off, 16), dtype=torch.uint8, device=dev)
-        mask_a = torch.empty(mask_off, dtype=torch.uint8, device=dev)
-        mask_b = torch.empty(mask_off, dtype=torch.uint8, device=dev)
-        area = torch.empty(B, dtype=torch.int32, device=dev)
-        out_regions = torch.empty(reg_off, dtype=torch.uint8, device=dev)
-        _lib.check(lib.casync_frame_paste_back(
-            p_regions, p_geom, p_pts, crops.data_ptr(), pred.data_ptr(), B, max_h, max_w,
-            max_width, mask_off, synth.data_ptr(), mask_a.data_ptr(), mask_b.data_ptr(), area.data_ptr(),
-            out_regions.data_ptr(), stream), "casync_frame_paste_back")
+        out_regions = regions_through_net(net, p_regions, p_geom, p_pts, geom, reg_off, windows=windows, features=features,
+                                          frame_indices=frame_indices)
         host = _acquire_pinned(reg_off)                      # the ONE download of the batch, into pinned memory
         host[:reg_off].copy_(out_regions, non_blocking=True)
         done = torch.cuda.Event()

@@ -58,9 +58,9 @@ def _imread(path: str, gray: bool = False) -> Optional[np.ndarray]:
 
 
 class FrameSynthesizer:
-    def __init__(self, unet_checkpoint: Optional[str], data_dir: str, device: str = "cuda:0", batch_size: int = 8, *,
+    def __init__(self, unet_checkpoint: Optional[str], data_dir: Optional[str], device: str = "cuda:0", batch_size: int = 8, *,
                  seed: Optional[int] = None, precision: str = "fp32", net: Optional[Model] = None,
-                 batches_in_flight: Optional[int] = None):
+                 batches_in_flight: Optional[int] = None, resident: Optional[bool] = None, clip=None):
         """Same positional arguments as the reference (infer_api.py:13-14).  Keyword-only extensions:
         ``seed`` (reproducible frame walk), ``precision`` (engine storage type), ``net`` (an already
         loaded ``Model`` instead of a checkpoint path), ``batches_in_flight`` (default 1, or the
@@ -69,7 +69,19 @@ class FrameSynthesizer:
         ``batch_size`` frames, the reference's ``_load_batch_frames``) behind the device work; 0 is the reference's own
         batch-by-batch order.  With frames already in memory there is nothing to hide, and on a small host share the
         queued batch's host copies compete with the one being collected: ``bench.py``'s synthetic ``e2e`` block
-        measures both (4.4-4.5 k with one in flight, 4.8-4.9 k batch by batch on 16 cores) -- pick 0 there."""
+        measures both (4.4-4.5 k with one in flight, 4.8-4.9 k batch by batch on 16 cores) -- pick 0 there.
+
+        ``resident`` (default False, or the ``CASYNC_RESIDENT_CLIP`` environment variable): keep the clip on the device
+        (``resident_clip.ResidentClip``): ``data_dir`` is read once, on the first ``iterate_synthesized_frames``, and a batch
+        sends only its records up; the frames yielded are those of ``resident=False`` byte for byte.  ``clip``: a
+        ``ResidentClip`` made elsewhere (``from_frames``: no directory at all); ``data_dir`` may then be None."""
+        if resident is None:
+            resident = clip is not None or os.environ.get("CASYNC_RESIDENT_CLIP", "0").lower() not in ("", "0", "false")
+        if clip is not None and not resident:
+            raise ValueError("clip= is the resident path: resident=False contradicts it")
+        if clip is None and data_dir is None:
+            raise ValueError("data_dir may only be None with clip=")
+        self.resident, self._clip = bool(resident), clip
         if batches_in_flight is None:
             batches_in_flight = int(os.environ.get("CASYNC_BATCHES_IN_FLIGHT", "1"))
         if batches_in_flight < 0:
@@ -78,13 +90,17 @@ class FrameSynthesizer:
         self.device = device
         self.data_dir = data_dir
         self.batch_size = batch_size
-        self.frames_dir = os.path.join(data_dir, "frames")
-        self.positions_dir = os.path.join(data_dir, "positions")
-        self.masks_dir = os.path.join(data_dir, "masks")
-        # infer_api.py:34 counts the .jpg frames; .npy frames are accepted too (synthetic data sets)
-        names = os.listdir(self.frames_dir)
-        self._ext = ".jpg" if any(f.endswith(".jpg") for f in names) else ".npy"
-        self.total_frames = len([f for f in names if f.endswith(self._ext)])
+        if clip is not None:
+            self.frames_dir = self.positions_dir = self.masks_dir = self._ext = None
+            self.total_frames = len(clip)
+        else:
+            self.frames_dir = os.path.join(data_dir, "frames")
+            self.positions_dir = os.path.join(data_dir, "positions")
+            self.masks_dir = os.path.join(data_dir, "masks")
+            # infer_api.py:34 counts the .jpg frames; .npy frames are accepted too (synthetic data sets)
+            names = os.listdir(self.frames_dir)
+            self._ext = ".jpg" if any(f.endswith(".jpg") for f in names) else ".npy"
+            self.total_frames = len([f for f in names if f.endswith(self._ext)])
         self.executor = ThreadPoolExecutor(max_workers=self.batch_size)   # infer_api.py:38
         if net is None:                                                   # infer_api.py:41-43
             net = Model(6, "hubert", precision=precision).to(device)
@@ -163,15 +179,23 @@ class FrameSynthesizer:
             print(f"process_batch failed, returning the original frames: {exc!r}")
             return None, batch_images
 
-    @staticmethod
-    def _collect(pending, originals) -> list:
-        if pending is None:
-            return originals
+    def _submit_resident(self, frame_sequence, features_dev, indices):
+        """The same on the resident clip: the originals are fetched from the device only if they are needed."""
+        originals = lambda: self._clip.fetch(frame_sequence).result()
         try:
-            return pending.result()
+            return self._clip.submit(self.net, frame_sequence, features=features_dev, frame_indices=indices), originals
         except Exception as exc:
             print(f"process_batch failed, returning the original frames: {exc!r}")
-            return originals
+            return None, originals
+
+    @staticmethod
+    def _collect(pending, originals) -> list:
+        if pending is not None:
+            try:
+                return pending.result()
+            except Exception as exc:
+                print(f"process_batch failed, returning the original frames: {exc!r}")
+        return originals() if callable(originals) else originals
 
     # ------------------------------------------------------------------ the loop (infer_api.py:359-451)
     def iterate_synthesized_frames(self, features: np.ndarray, start_frame_idx: int = 0,
@@ -186,10 +210,26 @@ class FrameSynthesizer:
                 t0 = time.time()   # one upload of the whole [T,2,1024] array replaces B x 128 KB per batch
                 features_dev = torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32)).to(self.device)
                 time_stats["get_audio"] += time.time() - t0
+            if self.resident and self._clip is None and total_frames:
+                from .resident_clip import ResidentClip
+                t0 = time.time()   # the whole directory, once: kept for the life of this object
+                self._clip = ResidentClip.from_data_dir(self.data_dir, self.device, io_workers=self.batch_size)
+                time_stats["load_frame"] += time.time() - t0
             for batch_start in range(0, total_frames, self.batch_size):
                 try:
                     batch_end = min(batch_start + self.batch_size, total_frames)    # variable last batch
                     frame_sequence = self._generate_frame_sequence(batch_end - batch_start)
+                    if self.resident:
+                        t0 = time.time()
+                        if not is_generate_sync_frame:      # pass-through mode: the stored frames, from the device
+                            yield from self._emit(self._clip.fetch(frame_sequence).result(), frame_sequence)
+                            continue
+                        pending, originals = self._submit_resident(frame_sequence, features_dev, list(range(batch_start, batch_end)))
+                        in_flight.append((pending, originals, frame_sequence))
+                        time_stats["process_batch"] += time.time() - t0
+                        while len(in_flight) > self.batches_in_flight:
+                            yield from self._drain_one(in_flight, time_stats)
+                        continue
                     t0 = time.time()
                     batch_images, batch_landmarks, batch_masks = self._load_batch_frames(
                         frame_sequence, raw_masks=is_generate_sync_frame)

@@ -46,7 +46,7 @@ enum {
 #define CASYNC_ABI_VERSION 13  /* 12: S3FD face detector handle (casync_s3fd_*, casync_op_s3fd_*); 13: its bf16 precision
                                 * (casync_s3fd_create_ex, _precision, _workspace_bytes_ex, casync_op_s3fd16_*).  The face-pipeline
                                 * operators at the end of this file (casync_op_resize_linear_u8, _face_crops192, _s3fd_candidates,
-                                * _landmarks_finalize) and casync_op_s3fd_nms were added under 13: new symbols only, no prototype or layout changed */
+                                * _landmarks_finalize), casync_op_s3fd_nms and casync_op_clip_gather / _compose were added under 13: new symbols only, no prototype or layout changed */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -601,6 +601,27 @@ int  casync_op_landmarks_finalize(const float* y, const float* mean_face, const 
  * synchronisation.  batch 1..65535, cap 1..1024, width and height >= 1.                                                   */
 int  casync_op_s3fd_nms(const float* rows, const int32_t* counts, int batch, int cap, int width, int height, float conf_th,
                         int32_t* status, double* faces, float* detect_out, int32_t* detect_n, casync_stream stream);
+
+/* ---- a clip resident on the device (additive to ABI 13: two new symbols, nothing else changed) ---------------- */
+/* The byte moves between the stored frames of a clip, frames [n_frames,H,W,3] uint8 on the device, and the packed `regions`
+ * layout of casync_frame_prepare / casync_frame_paste_back, so that a batch of the frame loop needs no pixel from the host.
+ * rec [batch][8] int32 in HOST memory, read before the call returns:
+ *   { frame, y0, x0, h, w, valid, region byte offset, 0 }
+ * frame indexes `frames`; (y0, x0, h, w) is the crop box img[y0:y0+h, x0:x0+w] (frame_loop.crop_box); region byte offset is
+ * word 0 of the frame's geometry record, where its h x w x 3 bytes lie in `regions` (any alignment, gaps allowed).
+ *   clip_gather:  regions[offset .. offset + h w 3) = frames[frame, y0:y0+h, x0:x0+w] for every record, whatever `valid` says.
+ *   clip_compose: out [batch,H,W,3]; out[b] = frames[rec[b].frame], and where rec[b].valid the box is replaced by the h x w x 3
+ *     bytes of out_regions at the record's offset.  out_regions may be NULL when no record is valid (the plain fetch of stored
+ *     frames).  out must not overlap frames.  An output byte has one writer: a byte inside a valid box comes from out_regions only.
+ * Refused with CASYNC_ERR_ARG before anything is launched or touched: a null pointer, H or W < 1, batch < 0 (batch 0 returns
+ * 0), frame outside [0, n_frames), a box with h or w < 1 or not inside the frame, an offset < 0 or offset + h w 3 >
+ * regions_bytes, a valid record with out_regions NULL.  clip_compose checks the box and the offset of valid records only.
+ * One wave per row, 16-byte accesses where source and destination are 16-byte aligned together and narrower ones elsewhere
+ * (no vector crosses a box edge); byte offsets are 64-bit.  No LDS, no atomics, no allocation, no synchronisation.            */
+int  casync_op_clip_gather(const uint8_t* frames, int n_frames, int H, int W, const int32_t* rec, int batch, uint8_t* regions,
+                           int64_t regions_bytes, casync_stream stream);
+int  casync_op_clip_compose(const uint8_t* frames, int n_frames, int H, int W, const int32_t* rec, int batch,
+                            const uint8_t* out_regions, int64_t regions_bytes, uint8_t* out, casync_stream stream);
 
 #ifdef __cplusplus
 }
