@@ -88,6 +88,9 @@ _PROTOS = {
                                    C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_conv3x3_ex": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # host only: (tile, tap) pairs of that conv with all nine taps / as walked with conv_skip
+    "casync_conv3x3_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(c_i64),
+                                     C.POINTER(c_i64)]),
     "casync_op_audio_windows": (C.c_int, [c_f32p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_crop_to_input": (C.c_int, [C.c_void_p, c_f32p, C.c_int, C.c_void_p]),
     "casync_op_pred_to_u8": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_void_p]),

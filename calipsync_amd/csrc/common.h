@@ -109,7 +109,8 @@ struct CasyncOptions {
                              //   lanes join before the fusion MLP and the trunk runs as one stream-K lane)
   int lane_skew = 0;         // CASYNC_LANE_SKEW: two lanes of batch/2 + skew and batch/2 - skew frames (experiment)
   int overlap = 1;           // CASYNC_OVERLAP: audio encoder on its own stream per lane
-  int gemm_streamk = 1;      // CASYNC_GEMM_STREAMK: K may be split (stream-K remainders, the small-M tile) in single-lane runs; 0 = batch-invariant bits
+  int gemm_streamk = 1;      // CASYNC_GEMM_STREAMK: K may be split (stream-K remainders, the small-M tile) in single-lane runs, and the shared pixel
+                             //   tile of pw_dw's 10x10 frame pair between its two waves; 0 = batch-invariant bits
   int gemm_glds = 2;         // CASYNC_GEMM_GLDS: LDS-DMA ring GEMM: 0 off, 1 bf16 only, 2 both types
   int gemm_cfg = -1;         // CASYNC_GEMM_CFG: force one tile configuration
   int gemm_ring128 = 0;      // CASYNC_GEMM_RING128: bf16 128x128 launches of more than 256 tiles on a two-stage LDS-DMA ring, two workgroups per CU
@@ -157,6 +158,8 @@ struct CasyncOptions {
                              //   fp32-MFMA kernel of attention.hip on bf16 storage
   int kv_early = 1;          // CASYNC_KV_EARLY: the attention K/V projection GEMM runs on the audio stream beside the face encoder:
                              //   1 = in single-lane runs (small batches), 2 = always, 0 = never (between fusion MLP and attention)
+  int conv_skip = 1;         // CASYNC_CONV_SKIP: the dense 3x3 convs walk, per tile of position-major rows, only the taps that some row of the
+                             //   tile has inside the image (audio conv5: 65 % of the k-tiles at B = 32); 0 = all nine taps, same row order, same bits
 };
 CasyncOptions& casync_default_options();      // process defaults (environment read once, thread-safe)
 const CasyncOptions& casync_opts();           // options of the call in progress on this thread
@@ -284,7 +287,23 @@ struct GemmEpilogue {
   // pixel (b, oy, ox), column k = (ky*3 + kx)*C + c reads in[b, oy*conv_sh+ky-pad, ox*conv_sw+kx-pad, c]
   // (zero outside the image); W is [N][(ky,kx,c)].  K = 9*C, C a multiple of the 128-B k-tile.
   int conv_on = 0, conv_h = 0, conv_w = 0, conv_c = 0, conv_ho = 0, conv_wo = 0, conv_sh = 0, conv_sw = 0, conv_pad = 0;
+  // conv_tab (conv3x3_positions; null = the rows above): the rows are POSITION-major instead, row r = (position conv_tab[r / B],
+  // frame r % B) with the output positions sorted by their valid-tap mask, so that the rows of a tile share their padding
+  // and the kernel walks only the taps some row of the tile has (conv_skip; 0 = all nine).  The output stays frame-major.
+  const struct ConvPos* conv_tab = nullptr;
+  int conv_b = 0, conv_skip = 1;
 };
+// One output position of a 3x3 conv geometry: pos = oy * Wo + ox, mask = bit (ky * 3 + kx) set where that tap lies inside the
+// image, in_off = input pixel (iy0 * W + ix0) of tap (0, 0), possibly negative.
+struct alignas(16) ConvPos { int pos, mask, in_off, pad; };
+// The device table of a geometry: positions sorted by (mask, position).  Built on
+// first use (allocates and copies: engines ask at create time, never inside a forward), cached per device for the process.
+// Null (and the error set) on failure.
+const ConvPos* conv3x3_positions(int h, int w, int stride_h, int stride_w, int pad);
+// (M-tile, tap) pairs the launcher walks for this conv: `full` with all nine taps, `run` with conv_skip; has_sk / concurrent as
+// GemmEpilogue's sk_ws != null / concurrent (stream-K remainder tiles walk all nine).  Host only.
+int conv3x3_plan(int batch, int h, int w, int cin, int cout, int stride_h, int stride_w, int pad, bool has_sk, bool concurrent, int dtype,
+                 long long* full, long long* run);
 constexpr int kStreamKWgs = 256;                                  // stream-K workgroups (one per CU)
 constexpr long long kStreamKFloats = 2ll * kStreamKWgs * 128 * 64;  // two partial tiles per workgroup, up to 128x64
 constexpr int kStreamKCounters = 256;

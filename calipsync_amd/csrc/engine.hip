@@ -522,8 +522,18 @@ struct Plan {
       ep.sk_ws = reinterpret_cast<float*>(ctx);
       ep.sk_cnt = reinterpret_cast<unsigned*>(ctx + kStreamKFloats * 4);
     }
+    // fp32: position-major rows and the tap walk of conv_skip (gemm.hip): the table was built by casync_create_mode, and the
+    // FLOPs booked are the executed ones -- the share of (tile, tap) pairs the launcher walks.  The bf16 engine keeps frame-major
+    // rows (its convs are bound by data movement: measured 0.4 % slower at B = 512 with the rows regrouped, profiles/padwork_ab.txt).
+    const bool by_position = dt() == DT_F32;
+    if (by_position) ep.conv_tab = conv3x3_positions(h, w, stride_h, stride_w, pad);
+    long long kt_full = 1, kt_run = 1;
+    const int plan_st = !by_position ? CASYNC_OK : ep.conv_tab ? conv3x3_plan(B, h, w, cin, cout, stride_h, stride_w, pad, ep.sk_ws != nullptr, concurrent, dt(), &kt_full, &kt_run)
+                                    : CASYNC_ERR_HIP;
     const double es = dtype_size(dt());
-    r.run(tag.c_str(), 2.0 * m * cout * 9 * cin, es * ((double)B * h * w * cin + (double)m * cout + 9.0 * cin * cout), [&] {
+    r.run(tag.c_str(), 2.0 * m * cout * 9 * cin * ((double)kt_run / (double)kt_full),
+          es * ((double)B * h * w * cin + (double)m * cout + 9.0 * cin * cout), [&] {
+      if (plan_st) return plan_st;
       return launch_conv3x3_gemm(in, e.WG(wname), out, cout, B, h, w, cin, cout, stride_h, stride_w, pad, ep, r.s, dt());
     });
   }
@@ -1057,6 +1067,13 @@ int casync_create_mode(int device_id, int dtype, int audio_mode, casync_handle* 
       delete e;
       return CASYNC_ERR_HIP;
     }
+    // the position tables of audio conv3 / conv5 (Plan::conv3x3, fp32), so that no forward allocates or copies
+    const bool wenet = audio_mode == CASYNC_AUDIO_WENET;
+    if (dtype == DT_F32 && !((wenet ? conv3x3_positions(16, 32, 1, 2, 1) : conv3x3_positions(32, 32, 2, 2, 1)) && conv3x3_positions(16, 16, 2, 2, 3))) {
+      (void)hipFree(e->sk);
+      delete e;
+      return CASYNC_ERR_HIP;
+    }
   }
   *out = e;
   return CASYNC_OK;
@@ -1454,8 +1471,23 @@ int casync_op_conv3x3_ex(const void* in, const void* w, const float* bias, void*
   GemmEpilogue e;
   e.bias = bias;
   e.act = act;
+  if (g_op_dtype == DT_F32) {   // (fp32 only, as in the engine)
+    e.conv_tab = conv3x3_positions(h, wdt, stride_h, stride_w, pad);   // cached per geometry: built on its first call
+    if (!e.conv_tab) return CASYNC_ERR_ARG;
+  }
   return launch_conv3x3_gemm(in, w, out, cout, batch, h, wdt, cin, cout, stride_h, stride_w, pad, e, (hipStream_t)stream,
                              g_op_dtype);
+}
+// What that launch walks at the process options, outside an engine (no stream-K scratch, no second lane): (tile, tap) pairs
+// with all nine taps and with conv_skip.  Host only: needs no device.
+int casync_conv3x3_plan(int batch, int h, int wdt, int cin, int cout, int stride_h, int stride_w, int pad, int64_t* ktile_groups_full,
+                        int64_t* ktile_groups_run) {
+  long long full = 0, run = 0;
+  if (int st = conv3x3_plan(batch, h, wdt, cin, cout, stride_h, stride_w, pad, false, false, g_op_dtype, &full, &run)) return st;
+  CASYNC_REQUIRE(ktile_groups_full && ktile_groups_run, "conv3x3_plan: null out");
+  *ktile_groups_full = full;
+  *ktile_groups_run = run;
+  return CASYNC_OK;
 }
 int casync_op_dw3x3(const void* in, const float* w, const float* bias, void* out, int batch, int h,
                     int wdt, int c, int stride, casync_stream stream) {

@@ -28,6 +28,12 @@
 // coalesced row segment, instead of 4-B-per-lane scatter in the MFMA C layout.
 #include <stdlib.h>
 
+#include <algorithm>
+#include <array>
+#include <map>
+#include <mutex>
+#include <vector>
+
 #include <type_traits>
 #include <utility>
 
@@ -109,6 +115,13 @@ __device__ __forceinline__ void epilogue_rows_cols(const float* Cs, int m0, int 
   for (int p = 0; p < BM / RPP; ++p) {
     const int row = rr + RPP * p, m = m0 + row;
     if (m >= M) break;
+    size_t mo = (size_t)m;   // row of C and of the residuals
+    if constexpr (RELU) {    // (= the conv instances) position-major rows (GemmEpilogue::conv_tab) -> the frame-major output pixel
+      if (epi.conv_tab) {
+        const int cp = m / epi.conv_b;
+        mo = (size_t)(m - cp * epi.conv_b) * (size_t)(epi.conv_ho * epi.conv_wo) + (size_t)epi.conv_tab[cp].pos;
+      }
+    }
     V16<T> v;
 #pragma unroll
     for (int e = 0; e < CPT; e += 4) {
@@ -134,7 +147,7 @@ __device__ __forceinline__ void epilogue_rows_cols(const float* Cs, int m0, int 
       }
     }
     if (epi.pre_res) {
-      const V16<T> r = ld16(static_cast<const T*>(epi.pre_res) + (size_t)m * epi.ld_pre + n);
+      const V16<T> r = ld16(static_cast<const T*>(epi.pre_res) + mo * epi.ld_pre + n);
 #pragma unroll
       for (int e = 0; e < CPT; ++e) v.v[e] += col_const<LITE>(k.pscale, epi.pre_scale, 1.f, n, e) * r.v[e];
     }
@@ -152,7 +165,7 @@ __device__ __forceinline__ void epilogue_rows_cols(const float* Cs, int m0, int 
       }
     }
     if (epi.post_res) {
-      const V16<T> r = ld16(static_cast<const T*>(epi.post_res) + (size_t)m * epi.ld_post + n);
+      const V16<T> r = ld16(static_cast<const T*>(epi.post_res) + mo * epi.ld_post + n);
 #pragma unroll
       for (int e = 0; e < CPT; ++e) v.v[e] += r.v[e];
     }
@@ -161,9 +174,9 @@ __device__ __forceinline__ void epilogue_rows_cols(const float* Cs, int m0, int 
       for (int e = 0; e < CPT; ++e)
         v.v[e] = lrelu(v.v[e] * col_const<LITE>(k.as, epi.aff_s, 1.f, n, e) + col_const<LITE>(k.at, epi.aff_t, 0.f, n, e));
     }
-    st16(C + (size_t)m * ldc + n, v);
+    st16(C + mo * ldc + n, v);
     if (epi.acc_out) {
-      V16<T> sacc = ld16(static_cast<const T*>(epi.acc_in) + (size_t)m * epi.ld_acc + n);
+      V16<T> sacc = ld16(static_cast<const T*>(epi.acc_in) + mo * epi.ld_acc + n);
 #pragma unroll
       for (int e = 0; e < CPT; ++e) sacc.v[e] += v.v[e];
       if (epi.aff_s && epi.aff_on_acc) {
@@ -171,7 +184,7 @@ __device__ __forceinline__ void epilogue_rows_cols(const float* Cs, int m0, int 
         for (int e = 0; e < CPT; ++e)
           sacc.v[e] = lrelu(sacc.v[e] * col_const<LITE>(k.as, epi.aff_s, 1.f, n, e) + col_const<LITE>(k.at, epi.aff_t, 0.f, n, e));
       }
-      st16(static_cast<T*>(epi.acc_out) + (size_t)m * epi.ld_acc + n, sacc);
+      st16(static_cast<T*>(epi.acc_out) + mo * epi.ld_acc + n, sacc);
     }
   }
 }
@@ -421,10 +434,28 @@ __device__ __forceinline__ void glds_body(const T* __restrict__ A, int lda, cons
   int m0 = 0, n0 = 0;
   auto tile_origin = [&](int tile) {   // XCD-aware bijection tile -> (m0, n0)
     const int q = nwg >> 3, r = nwg & 7, xcd = tile & 7, idx = tile >> 3;
-    const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    // position-major conv rows are sorted by their tap mask, the nine-tap positions last: tiles in reverse launch order, so
+    // that the heavy M-tiles start first, the short ones fill the tail, and every XCD gets its share of each weight (the
+    // bijection above would hand one XCD the nine-tap tiles and another the empty ones)
+    if (CONV && epi.conv_tab) bid = nwg - 1 - tile;
     const int mt = bid / n_ntiles;
     m0 = mt * BM;
     n0 = (bid - mt * n_ntiles) * BN;
+  };
+  // CONV: the taps run_k walks, ascending, one nibble each (conv_ntap of them): all nine, or with position-major rows and
+  // conv_skip the union of the valid-tap masks of the tile's rows -- workgroup-uniform, from m0 alone
+  [[maybe_unused]] unsigned long long conv_taps = 0x876543210ull;
+  [[maybe_unused]] int conv_ntap = 9;
+  auto conv_tile_taps = [&] {
+    if (!(epi.conv_tab && epi.conv_skip)) return;
+    const int last = (m0 + BM < M ? m0 + BM : M) - 1;
+    int um = 0;
+    for (int p = m0 / epi.conv_b; p <= last / epi.conv_b; ++p) um |= epi.conv_tab[p].mask;
+    um = __builtin_amdgcn_readfirstlane(um);
+    conv_taps = 0, conv_ntap = 0;
+    for (int t = 0; t < 9; ++t)
+      if ((um >> t) & 1) conv_taps |= (unsigned long long)t << (4 * conv_ntap++);
   };
   auto zero_acc = [&] {
 #pragma unroll
@@ -448,35 +479,44 @@ __device__ __forceinline__ void glds_body(const T* __restrict__ A, int lda, cons
         int row = m0 + r;
         row = row < M ? row : M - 1;
         if constexpr (CONV) {
-          // row = output pixel (b, oy, ox); src = its tap (0,0) -- possibly outside the buffer, only
-          // dereferenced for taps the mask marks valid
-          const int hw = epi.conv_ho * epi.conv_wo;
-          const int b = row / hw, rem = row - b * hw;
-          const int oy = rem / epi.conv_wo, ox = rem - oy * epi.conv_wo;
-          const int iy0 = oy * epi.conv_sh - epi.conv_pad, ix0 = ox * epi.conv_sw - epi.conv_pad;
-          src[j] = A + (((long long)b * epi.conv_h + iy0) * epi.conv_w + ix0) * (long long)epi.conv_c + cs * E16;
-          int mk = 0;
+          if (epi.conv_tab) {
+            // row = (position, frame), frame innermost; the position's mask and tap (0,0) come from the table
+            const int p = row / epi.conv_b, b = row - p * epi.conv_b;
+            const ConvPos e = epi.conv_tab[p];
+            src[j] = A + ((long long)b * epi.conv_h * epi.conv_w + e.in_off) * (long long)epi.conv_c + cs * E16;
+            tapmask[j] = e.mask;
+          } else {
+            // row = output pixel (b, oy, ox); src = its tap (0,0) -- possibly outside the buffer, only
+            // dereferenced for taps the mask marks valid
+            const int hw = epi.conv_ho * epi.conv_wo;
+            const int b = row / hw, rem = row - b * hw;
+            const int oy = rem / epi.conv_wo, ox = rem - oy * epi.conv_wo;
+            const int iy0 = oy * epi.conv_sh - epi.conv_pad, ix0 = ox * epi.conv_sw - epi.conv_pad;
+            src[j] = A + (((long long)b * epi.conv_h + iy0) * epi.conv_w + ix0) * (long long)epi.conv_c + cs * E16;
+            int mk = 0;
 #pragma unroll
-          for (int t = 0; t < 9; ++t) {
-            const int iy = iy0 + t / 3, ix = ix0 + t % 3;
-            mk |= (iy >= 0 && iy < epi.conv_h && ix >= 0 && ix < epi.conv_w) ? 1 << t : 0;
+            for (int t = 0; t < 9; ++t) {
+              const int iy = iy0 + t / 3, ix = ix0 + t % 3;
+              mk |= (iy >= 0 && iy < epi.conv_h && ix >= 0 && ix < epi.conv_w) ? 1 << t : 0;
+            }
+            tapmask[j] = mk;
           }
-          tapmask[j] = mk;
         } else {
           src[j] = A + (size_t)row * lda + cs * E16 + (size_t)k0 * BK;
         }
       } else {
-        src[j] = W + (size_t)(n0 + r - BM) * K + cs * E16 + (size_t)k0 * BK;
+        src[j] = W + (size_t)(n0 + r - BM) * K + cs * E16 + (CONV ? 0 : (size_t)k0 * BK);   // (CONV: issue_part adds the k-tile)
       }
     }
     // LDS-DMA pieces [LPT*part/4, LPT*(part+1)/4) of k-tile kt (part 0..3; issue() = all four)
     auto issue_part = [&](int kt, int part) {
       char* st = ring + (kt % NST) * STAGE;
-      [[maybe_unused]] int tap = 0, tap_off = 0;
-      if constexpr (CONV) {   // k-tile -> (tap, channel offset): C / BK k-tiles per tap
-        const int kpt = epi.conv_c / BK, kg = k0 + kt;
-        tap = kg / kpt;
-        tap_off = ((tap / 3) * epi.conv_w + tap % 3) * epi.conv_c + (kg - tap * kpt) * BK;
+      [[maybe_unused]] int tap = 0, tap_off = 0, kw = kt;
+      if constexpr (CONV) {   // k-tile of the walk -> (tap, channel offset): C / BK k-tiles per tap of conv_taps
+        const int kpt = epi.conv_c / BK, kg = k0 + kt, ti = kg / kpt;
+        tap = (int)(conv_taps >> (4 * ti)) & 15;
+        tap_off = ((tap / 3) * epi.conv_w + tap % 3) * epi.conv_c + (kg - ti * kpt) * BK;
+        kw = tap * kpt + (kg - ti * kpt);   // its k-tile of W
       }
 #pragma unroll
       for (int j = 0; j < LPT; ++j) {
@@ -487,7 +527,7 @@ __device__ __forceinline__ void glds_body(const T* __restrict__ A, int lda, cons
           p = (tapmask[CONV ? j : 0] >> tap) & 1 ? src[j] + tap_off
                                                  : reinterpret_cast<const T*>(g_zero_page) + (lcol ^ ((r >> 1) & 7)) * E16;
         } else {
-          p = src[j] + (size_t)kt * BK;
+          p = src[j] + (size_t)kw * BK;
         }
         __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)p,
                                          (void __attribute__((address_space(3)))*)(st + (j * 4 + wave) * 8 * ROWB),
@@ -777,7 +817,7 @@ __device__ __forceinline__ void glds_body(const T* __restrict__ A, int lda, cons
     it += cnt;
     tile_origin(dp_tiles + t);
     if (PREF64) kcols.load(epi, n0 + (tid % (BN / V16<T>::N)) * V16<T>::N);   // (as in the data-parallel part below)
-    run_k(k0, cnt);
+    run_k(k0, cnt);   // (CONV: a stream-K run cuts the walk over all nine taps)
     if (cnt != nk) {
       float* slot = epi.sk_ws + (size_t)(2 * g + seg) * SLOT + tid;
 #pragma unroll
@@ -843,7 +883,12 @@ __device__ __forceinline__ void glds_body(const T* __restrict__ A, int lda, cons
     // MFMAs: the loop is no longer free of vector instructions); the two-lane B=64 schedule, which never takes this
     // branch, measured +0.7 % with that code (profiles/r4_ab_small_batch.txt), so it stays.
     else if (PREF64) kcols.load(epi, n0 + (tid % (BN / V16<T>::N)) * V16<T>::N);
-    run_k(0, nk);
+    if constexpr (CONV) {
+      conv_tile_taps();
+      run_k(0, conv_ntap * (epi.conv_c / BK));   // no tap inside the image: no k loop, the tile is act(bias)
+    } else {
+      run_k(0, nk);
+    }
     if (done < 2) stamp(1 + 2 * done);
     epilogue();
     if (done < 2) stamp(2 + 2 * done);
@@ -1164,17 +1209,111 @@ int launch_rows_gemm_bf16(const void* a, int lda, const void* w, const float* bi
 
 // ---------------------------------------------------------------- dense 3x3 as an implicit GEMM
 namespace {
+// tile height and stream-K use of a conv launch (one place: the launcher and conv3x3_plan)
+struct ConvShape { int bm; bool sk; };
+ConvShape conv_shape(int m, int n, int k, bool has_sk, bool concurrent, int dtype) {
+  bool sk = false;
+  // the ring kernel's two 48-KB-class tiles; the A "leading dimension" is unused (rows are gathered)
+  const int cfg = pick_cfg(m, n, k, 0, has_sk, dtype, &sk, concurrent, false);
+  const bool small = cfg == C64x64 || cfg == C64x32 || n % 64 || m <= 4096;
+  return small ? ConvShape{64, sk && cfg == C64x64} : ConvShape{128, sk && cfg == C128x64};
+}
+
 template <typename T>
 int launch_conv_t(const T* in, const T* w, T* out, int ldc, int m, int n, int k, const GemmEpilogue& epi,
                   hipStream_t stream, int dtype) {
-  bool sk = false;
-  // the ring kernel's two 48-KB-class tiles; the A "leading dimension" is unused (rows are gathered)
-  const int cfg = pick_cfg(m, n, k, 0, epi.sk_ws != nullptr, dtype, &sk, epi.concurrent != 0, false);
-  const bool small = cfg == C64x64 || cfg == C64x32 || n % 64 || m <= 4096;
-  return small ? launch_glds_t<T, 64, 64, 2, 2, 2, true>(in, 0, w, out, ldc, m, n, k, epi, stream, sk && cfg == C64x64)
-               : launch_glds_t<T, 128, 64, 2, 2, 2, true>(in, 0, w, out, ldc, m, n, k, epi, stream, sk && cfg == C128x64);
+  const ConvShape cs = conv_shape(m, n, k, epi.sk_ws != nullptr, epi.concurrent != 0, dtype);
+  return cs.bm == 64 ? launch_glds_t<T, 64, 64, 2, 2, 2, true>(in, 0, w, out, ldc, m, n, k, epi, stream, cs.sk)
+                     : launch_glds_t<T, 128, 64, 2, 2, 2, true>(in, 0, w, out, ldc, m, n, k, epi, stream, cs.sk);
+}
+
+// Output positions of a geometry with their valid-tap masks, sorted by (mask, position): positions with the same padding are
+// neighbours, the nine-tap ones (mask 0x1ff) last -- so a ragged last tile is a heavy one and the kernel starts from the end.
+std::vector<ConvPos> conv_positions_build(int h, int w, int sh, int sw, int pad) {
+  const int ho = (h + 2 * pad - 3) / sh + 1, wo = (w + 2 * pad - 3) / sw + 1;
+  std::vector<ConvPos> v((size_t)ho * wo);
+  for (int oy = 0; oy < ho; ++oy)
+    for (int ox = 0; ox < wo; ++ox) {
+      const int iy0 = oy * sh - pad, ix0 = ox * sw - pad;
+      int mk = 0;
+      for (int t = 0; t < 9; ++t) {
+        const int iy = iy0 + t / 3, ix = ix0 + t % 3;
+        if (iy >= 0 && iy < h && ix >= 0 && ix < w) mk |= 1 << t;
+      }
+      v[(size_t)oy * wo + ox] = ConvPos{oy * wo + ox, mk, iy0 * w + ix0, 0};
+    }
+  std::sort(v.begin(), v.end(), [](const ConvPos& a, const ConvPos& b) { return a.mask != b.mask ? a.mask < b.mask : a.pos < b.pos; });
+  return v;
+}
+
+// ... built once per geometry and kept (a forward asks for its convs' plan on the launching thread)
+const std::vector<ConvPos>& conv_positions_host(int h, int w, int sh, int sw, int pad) {
+  static std::mutex mu;
+  static std::map<std::array<int, 5>, std::vector<ConvPos>> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  std::vector<ConvPos>& v = cache[{h, w, sh, sw, pad}];
+  if (v.empty()) v = conv_positions_build(h, w, sh, sw, pad);
+  return v;   // (map nodes do not move)
+}
+
+bool conv_geometry_ok(int h, int w, int sh, int sw, int pad) {
+  return h > 0 && w > 0 && sh >= 1 && sw >= 1 && pad >= 0 && h + 2 * pad >= 3 && w + 2 * pad >= 3 && (long long)h * w < (1ll << 30);
 }
 }  // namespace
+
+const ConvPos* conv3x3_positions(int h, int w, int stride_h, int stride_w, int pad) {
+  static std::mutex mu;
+  static std::map<std::array<int, 6>, ConvPos*> tabs;   // (device, geometry) -> device table, kept for the life of the process
+  if (!conv_geometry_ok(h, w, stride_h, stride_w, pad)) {
+    casync_set_error("conv3x3: geometry");
+    return nullptr;
+  }
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) {
+    casync_set_error("conv3x3: no device");
+    return nullptr;
+  }
+  std::lock_guard<std::mutex> lock(mu);
+  ConvPos*& slot = tabs[{dev, h, w, stride_h, stride_w, pad}];
+  if (!slot) {
+    const std::vector<ConvPos>& v = conv_positions_host(h, w, stride_h, stride_w, pad);
+    ConvPos* d = nullptr;
+    if (hipMalloc(&d, v.size() * sizeof(ConvPos)) != hipSuccess || hipMemcpy(d, v.data(), v.size() * sizeof(ConvPos), hipMemcpyHostToDevice) != hipSuccess) {
+      if (d) (void)hipFree(d);
+      casync_set_error("conv3x3: position table of %dx%d: %s", h, w, hipGetErrorString(hipGetLastError()));
+      return nullptr;
+    }
+    slot = d;
+  }
+  return slot;
+}
+
+int conv3x3_plan(int batch, int h, int w, int cin, int cout, int stride_h, int stride_w, int pad, bool has_sk, bool concurrent, int dtype,
+                 long long* full, long long* run) {
+  CASYNC_REQUIRE(full && run && batch > 0 && conv_geometry_ok(h, w, stride_h, stride_w, pad), "conv3x3_plan: bad args");
+  CASYNC_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "conv3x3_plan: dtype %d", dtype);
+  const int bk = ROWB / dtype_size(dtype);
+  CASYNC_REQUIRE(cin > 0 && cin % bk == 0 && cout > 0 && cout % 64 == 0, "conv3x3_plan: cin=%d must be a multiple of %d, cout=%d of 64", cin, bk, cout);
+  const std::vector<ConvPos>& v = conv_positions_host(h, w, stride_h, stride_w, pad);
+  const long long m = (long long)batch * (long long)v.size();
+  CASYNC_REQUIRE(m < (1ll << 31), "conv3x3_plan: too many output pixels");
+  const ConvShape cs = conv_shape((int)m, cout, 9 * cin, has_sk, concurrent, dtype);
+  const long long n_mt = (m + cs.bm - 1) / cs.bm, n_nt = cout / 64, nwg = n_mt * n_nt;
+  const long long dp = stream_k_split(nwg, 9 * cin / bk, cs.bm * 64, has_sk && cs.sk).dp_tiles;
+  const bool skip = casync_opts().conv_skip != 0 && dtype == DT_F32;   // (bf16 launches keep frame-major rows: all nine taps)
+  *full = 9 * nwg;
+  *run = 0;
+  for (long long mt = 0; mt < n_mt; ++mt) {
+    const long long last = std::min(m, (mt + 1) * cs.bm) - 1;
+    int um = 0;
+    for (long long p = mt * cs.bm / batch; p <= last / batch; ++p) um |= v[(size_t)p].mask;
+    // M-tile mt holds the output tiles mt * n_nt ..; launch order is the reverse, so the first nwg - dp of them are the
+    // stream-K remainder (all nine taps)
+    const long long lo = mt * n_nt, n_dp = std::max(0ll, std::min(n_nt, lo + n_nt - (nwg - dp)));
+    *run += n_dp * (skip ? __builtin_popcount(um) : 9) + (n_nt - n_dp) * 9;
+  }
+  return CASYNC_OK;
+}
 
 int launch_conv3x3_gemm(const void* in, const void* w, void* out, int ldc, int batch, int h, int wdt, int cin,
                         int cout, int stride_h, int stride_w, int pad, const GemmEpilogue& epi_in, hipStream_t stream, int dtype) {
@@ -1195,6 +1334,8 @@ int launch_conv3x3_gemm(const void* in, const void* w, void* out, int ldc, int b
   epi.conv_wo = (wdt + 2 * pad - 3) / stride_w + 1;
   const long long m = (long long)batch * epi.conv_ho * epi.conv_wo;
   CASYNC_REQUIRE(m < (1ll << 31), "conv3x3: too many output pixels");
+  epi.conv_b = batch;
+  epi.conv_skip = casync_opts().conv_skip != 0;
   if (dtype == DT_BF16)
     return launch_conv_t<bf16_t>(static_cast<const bf16_t*>(in), static_cast<const bf16_t*>(w), static_cast<bf16_t*>(out),
                                  ldc, (int)m, cout, 9 * cin, epi, stream, dtype);

@@ -54,6 +54,7 @@ struct ETile {
 template <int HW, int F, int BN, int KF, int S = 1, int NST_ = 2, int WD = HW>
 struct FTGeom {
   static constexpr int NST = NST_;                             // ring stages
+  static constexpr int FR = F;                                 // frames per tile
   static constexpr int ROWB = KF * 4, RPI = 1024 / ROWB;       // row bytes; rows one LDS-DMA instruction fills (8 / 16)
   static constexpr int P = HW * WD, M = F * P, MT = (M + 15) / 16, M_PAD = 16 * MT;
   static constexpr int NT = BN / 16, WPN = 4 / NT;             // n-tiles; waves that share an n-tile
@@ -121,13 +122,40 @@ __device__ __forceinline__ f32x4 ups_at_lds(const float* sG, int gy0, int y, int
          (ty.l1 * tx.l1) * at(ty.i1, tx.i1);
 }
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// Two waves share a channel tile (BN = 32) and the pixel tiles do not divide between them: the last one is shared, each wave
+// computing half of its K (pw_dw_gemm), so that no wave issues MFMAs for a tile it does not own.
+template <class G>
+constexpr bool pw_dw_ksplit = G::WPN == 2 && G::MT % 2 == 1;
+// A tile of several frames (the 10x10 frame pair) puts the LAST frame's last pixels into the shared tile, so a frame's rounding would
+// depend on its place in the launch: there the split is a launch argument, off where bits must not depend on the batch
+// (pw_dw_ksplit_on); one-frame tiles and strips split the same pixels of every frame and always do.
+template <class G>
+constexpr bool pw_dw_ksplit_runtime = pw_dw_ksplit<G> && G::FR > 1;
+
+// Epilogue 1 of the shared tile.  Wave wm = 1 parks its partial sum in the E image at the pixel's own place -- no extra LDS; nobody
+// else writes there, the zero columns lie outside the frame -- and after one barrier wave wm = 0 adds it to its own and hands the
+// sum to `finish`, which writes the pixel's E value over it.  Every thread of the workgroup must call this (barrier).
+// `ks` off (workgroup-uniform): the first wave's sum is the whole tile (pw_dw_gemm), nothing to add.
+template <class Fin>
+__device__ __forceinline__ void shared_tile_sum(float* slot, bool valid, int wm, bool ks, const f32x4& part, Fin&& finish) {
+  if (!ks) {
+    if (wm == 0 && valid) finish(part);
+    return;
+  }
+  if (wm == 1 && valid) *reinterpret_cast<f32x4*>(slot) = part;
+  __syncthreads();
+  if (wm == 0 && valid) finish(part + *reinterpret_cast<const f32x4*>(slot));
+}
+
 // The GEMM part both kernels share: acc[i] (i-th pixel tile of this wave) = W1 tile x A rows over the whole K, k-tiles
 // arriving by LDS-DMA into a two-stage ring.  voff[j]: this lane's source offset of the wave's j-th LDS-DMA instruction
 // (rows [0, M_PAD) of a stage are A rows, then BN rows of W1); ends with the ring consumed (barrier).
 template <class G, int BN, int KF>
 __device__ __forceinline__ void pw_dw_gemm(char* ring, const float* __restrict__ A, const float* __restrict__ W1, unsigned a_bytes,
                                            unsigned w_bytes, const int (&voff)[G::LPT], int nk, int wave, int l15, int q,
-                                           f32x4 (&acc)[G::MTW]) {
+                                           f32x4 (&acc)[G::MTW], bool ks) {
   constexpr int ROWB = G::ROWB, RPI = G::RPI;
   auto issue = [&](int kt, int stage) __attribute__((always_inline)) {
 #pragma unroll
@@ -145,27 +173,53 @@ __device__ __forceinline__ void pw_dw_gemm(char* ring, const float* __restrict__
   for (int g = 0; g < KF / 16; ++g) frag[g] = l15 * ROWB + (((4 * g + q) ^ key) << 4);
 #pragma unroll
   for (int i = 0; i < G::MTW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // An odd tile count over a wave pair (KS): each wave has MTW - 1 whole tiles, and the last tile is SHARED, split along K:
+  // of a lane's four floats per 16-float k-group wave wm = 0 multiplies floats {0, 1} (s-steps 0, 1), wave wm = 1 floats
+  // {2, 3}, each read as the 8 B at 8 wm of the fragment.  acc[MTW - 1] of both waves is a partial sum of that tile; epilogue 1
+  // adds them (shared_tile_sum).  The second wave used to recompute the whole tile and drop it: 4 MTW instead of 4 MTW - 2
+  // MFMAs per k-group, 28 instead of 26 for the 13 tiles of a 10x10 frame pair.
+  // Where the split is a launch argument and off (`ks`, uniform), both waves run the shared tile's four s-steps in order -- the
+  // second pair behind a uniform branch -- and the first wave's sum is used alone: the bits of the unsplit kernel.
+  constexpr bool KS = pw_dw_ksplit<G>, KSR = pw_dw_ksplit_runtime<G>;
+  constexpr int MTF = KS ? G::MTW - 1 : G::MTW;           // whole tiles of this wave
+  const int half = ks ? 8 * wm : 0;                       // byte offset of this wave's float pair inside a 16-B fragment
 
   // the MFMAs of one k-tile: all its fragments are requested up front, then the MFMAs run back to back: s outer, tile
   // inner, so an accumulator is reused only every MTW instructions (no dependent-issue stalls)
   auto compute = [&](const char* st) __attribute__((always_inline)) {
-    f32x4 fw[KF / 16], fa[KF / 16][G::MTW];
+    f32x4 fw[KF / 16], fa[KF / 16][MTF];
+    [[maybe_unused]] f32x2 fws[KF / 16], fas[KF / 16];     // KS: this wave's half of the shared tile's fragments
 #pragma unroll
     for (int g = 0; g < KF / 16; ++g) {
       fw[g] = *reinterpret_cast<const f32x4*>(st + (G::M_PAD + 16 * wn) * ROWB + frag[g]);
 #pragma unroll
-      for (int i = 0; i < G::MTW; ++i) {
-        // a tile index past the end (BN = 32, second wave of the pair) recomputes the last tile and never stores it
-        const int t = wm + G::WPN * i < G::MT ? wm + G::WPN * i : G::MT - 1;
+      for (int i = 0; i < MTF; ++i) {
+        // (no tile index runs past the end any more; the clamp stays where KS is off so that those instances' code does not move)
+        const int t = KS || wm + G::WPN * i < G::MT ? wm + G::WPN * i : G::MT - 1;
         fa[g][i] = *reinterpret_cast<const f32x4*>(st + 16 * t * ROWB + frag[g]);
+      }
+      if constexpr (KS) {
+        fws[g] = *reinterpret_cast<const f32x2*>(st + (G::M_PAD + 16 * wn) * ROWB + frag[g] + half);
+        fas[g] = *reinterpret_cast<const f32x2*>(st + 16 * (G::MT - 1) * ROWB + frag[g] + half);
       }
     }
 #pragma unroll
-    for (int g = 0; g < KF / 16; ++g)
+    for (int g = 0; g < KF / 16; ++g) {
 #pragma unroll
-      for (int s = 0; s < 4; ++s)
+      for (int s = 0; s < 4; ++s) {
 #pragma unroll
-        for (int i = 0; i < G::MTW; ++i) acc[i] = mfma16(fw[g][s], fa[g][i][s], acc[i]);
+        for (int i = 0; i < MTF; ++i) acc[i] = mfma16(fw[g][s], fa[g][i][s], acc[i]);
+        if constexpr (KS)
+          if (s < 2) acc[MTF] = mfma16(fws[g][s], fas[g][s], acc[MTF]);
+      }
+      if constexpr (KSR) {
+        if (!ks) {   // s-steps 2, 3 of the shared tile
+          const f32x2 a2 = *reinterpret_cast<const f32x2*>(st + 16 * (G::MT - 1) * ROWB + frag[g] + 8);
+          acc[MTF] = mfma16(fw[g][2], a2[0], acc[MTF]);
+          acc[MTF] = mfma16(fw[g][3], a2[1], acc[MTF]);
+        }
+      }
+    }
   };
   if constexpr (G::NST == 2) {
     issue(0, 0);
@@ -238,7 +292,7 @@ template <int HW, int F, int BN, int KF, int S, int NST, int WD>
 __device__ __forceinline__ void pw_dw_body(
     const float* __restrict__ A, int lda, const float* __restrict__ W1, const float* __restrict__ b1,
     const float* __restrict__ wd, const float* __restrict__ bd, float* __restrict__ D, int ldd, int frames, int K, int N,
-    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes) {
+    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes, int ksplit) {
   using G = FTGeom<HW, F, BN, KF, S, NST, WD>;
   using E = typename G::E;
   constexpr int ROWB = G::ROWB, RPI = G::RPI, CPR = ROWB / 16;   // 16-B columns per row
@@ -276,7 +330,8 @@ __device__ __forceinline__ void pw_dw_body(
   }
   const int wn = wave % G::NT, wm = wave / G::NT;
   f32x4 acc[G::MTW];
-  pw_dw_gemm<G, BN, KF>(ring, A, W1, a_bytes, w_bytes, voff, nk, wave, l15, q, acc);
+  const bool ks = pw_dw_ksplit_runtime<G> ? ksplit != 0 : pw_dw_ksplit<G>;
+  pw_dw_gemm<G, BN, KF>(ring, A, W1, a_bytes, w_bytes, voff, nk, wave, l15, q, acc, ks);
 
   // ---- epilogue 1: + b1, LeakyReLU -> the zero-bordered E image ----
   float* sE = reinterpret_cast<float*>(ring);
@@ -287,10 +342,16 @@ __device__ __forceinline__ void pw_dw_body(
     for (int i = 0; i < G::MTW; ++i) {
       const int t = wm + G::WPN * i;
       const int px = 16 * t + l15;
+      if (pw_dw_ksplit<G> && i == G::MTW - 1) continue;   // the shared tile: below
       if (t < G::MT && px < m_valid) {
         const int f = px / G::P, rem = px - f * G::P, y = rem / WD, x = rem - y * WD;
         *reinterpret_cast<f32x4*>(sE + E::at(f * HW + y, x, 4 * wn + q)) = lrelu4(acc[i] + bias);
       }
+    }
+    if constexpr (pw_dw_ksplit<G>) {
+      const int px = 16 * (G::MT - 1) + l15, f = px / G::P, rem = px - f * G::P, y = rem / WD, x = rem - y * WD;
+      float* slot = sE + E::at(f * HW + y, x, 4 * wn + q);
+      shared_tile_sum(slot, px < m_valid, wm, ks, acc[G::MTW - 1], [&](f32x4 sum) { *reinterpret_cast<f32x4*>(slot) = lrelu4(sum + bias); });
     }
   }
   __syncthreads();
@@ -321,7 +382,7 @@ template <int HW, int F, int BN, int KF, int S, int NST = 2>
 __global__ __launch_bounds__(256, (FTGeom<HW, F, BN, KF, S, NST>::occ)) void pw_dw_kernel(
     const float* __restrict__ A, int lda, const float* __restrict__ W1, const float* __restrict__ b1,
     const float* __restrict__ wd, const float* __restrict__ bd, float* __restrict__ D, int ldd, int frames, int K, int N,
-    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes, const float* __restrict__ ups, int ld_ups) {
+    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes, const float* __restrict__ ups, int ld_ups, int ksplit) {
   using G = FTGeom<HW, F, BN, KF, S, NST>;
   using E = typename G::E;
   constexpr int ROWB = G::ROWB, RPI = G::RPI, CPR = ROWB / 16;   // 16-B columns per row
@@ -363,7 +424,8 @@ __global__ __launch_bounds__(256, (FTGeom<HW, F, BN, KF, S, NST>::occ)) void pw_
   float* sG = reinterpret_cast<float*>(ring + G::lds);
   if (ups) ups_tile_load<HW / 2>(sG, ups + (size_t)f0 * (HW / 2) * (HW / 2) * ld_ups + n0, ld_ups, 0, HW / 2, wave, lane);
   f32x4 acc[G::MTW];
-  pw_dw_gemm<G, BN, KF>(ring, A, W1, a_bytes, w_bytes, voff, nk, wave, l15, q, acc);
+  const bool ks = pw_dw_ksplit_runtime<G> ? ksplit != 0 : pw_dw_ksplit<G>;
+  pw_dw_gemm<G, BN, KF>(ring, A, W1, a_bytes, w_bytes, voff, nk, wave, l15, q, acc, ks);
 
   // ---- epilogue 1: + b1, LeakyReLU -> the zero-bordered E image ----
   float* sE = reinterpret_cast<float*>(ring);
@@ -374,6 +436,7 @@ __global__ __launch_bounds__(256, (FTGeom<HW, F, BN, KF, S, NST>::occ)) void pw_
     for (int i = 0; i < G::MTW; ++i) {
       const int t = wm + G::WPN * i;
       const int px = 16 * t + l15;
+      if (pw_dw_ksplit<G> && i == G::MTW - 1) continue;   // the shared tile: below
       if (t < G::MT && px < m_valid) {
         const int f = px / G::P, rem = px - f * G::P, y = rem / HW, x = rem - y * HW;
         f32x4 v = acc[i] + bias;
@@ -384,6 +447,15 @@ __global__ __launch_bounds__(256, (FTGeom<HW, F, BN, KF, S, NST>::occ)) void pw_
         }
         *reinterpret_cast<f32x4*>(sE + E::at(f * HW + y, x, 4 * wn + q)) = lrelu4(v);
       }
+    }
+    if constexpr (pw_dw_ksplit<G>) {
+      const int px = 16 * (G::MT - 1) + l15, f = px / G::P, rem = px - f * G::P, y = rem / HW, x = rem - y * HW;
+      float* slot = sE + E::at(f * HW + y, x, 4 * wn + q);
+      shared_tile_sum(slot, px < m_valid, wm, ks, acc[G::MTW - 1], [&](f32x4 sum) {
+        f32x4 v = sum + bias;
+        if (ups) v += ups_at_lds<HW>(sG, 0, y, x, 4 * wn + q);
+        *reinterpret_cast<f32x4*>(slot) = lrelu4(v);
+      });
     }
   }
   __syncthreads();
@@ -416,8 +488,8 @@ template <int H, int W, int BN, int KF>
 __global__ __launch_bounds__(256, (FTGeom<H, 1, BN, KF, 1, 2, W>::occ)) void pw_dw_rect_kernel(
     const float* __restrict__ A, int lda, const float* __restrict__ W1, const float* __restrict__ b1,
     const float* __restrict__ wd, const float* __restrict__ bd, float* __restrict__ D, int ldd, int frames, int K, int N,
-    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes, const float* __restrict__ ups, int ld_ups) {
-  pw_dw_body<H, 1, BN, KF, 1, 2, W>(A, lda, W1, b1, wd, bd, D, ldd, frames, K, N, n_ntiles, nwg, a_bytes, w_bytes);
+    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes, const float* __restrict__ ups, int ld_ups, int ksplit) {
+  pw_dw_body<H, 1, BN, KF, 1, 2, W>(A, lda, W1, b1, wd, bd, D, ldd, frames, K, N, n_ntiles, nwg, a_bytes, w_bytes, ksplit);
 }
 
 // ---- 40 x 40 frames: a whole frame does not fit a tile (1600 pixels x 32 channels = 200 KB), so the tile is a STRIP of
@@ -428,6 +500,7 @@ __global__ __launch_bounds__(256, (FTGeom<H, 1, BN, KF, 1, 2, W>::occ)) void pw_
 template <int HW, int SR, int STRIDE, int BN, int KF>
 struct FSGeom {
   static constexpr int NST = 2;
+  static constexpr int FR = 1;                                 // (a strip of one frame)
   static constexpr int ROWB = KF * 4, RPI = 1024 / ROWB;
   static constexpr int P = HW * HW, RIN = (SR - 1) * STRIDE + 3, M = RIN * HW, MT = (M + 15) / 16, M_PAD = 16 * MT;
   static constexpr int HO = (HW + 2 - 3) / STRIDE + 1, NS = (HO + SR - 1) / SR;   // output rows / strips per frame
@@ -449,7 +522,7 @@ template <int HW, int SR, int STRIDE, int BN, int KF>
 __global__ __launch_bounds__(256, (FSGeom<HW, SR, STRIDE, BN, KF>::occ)) void pw_dw_strip_kernel(
     const float* __restrict__ A, int lda, const float* __restrict__ W1, const float* __restrict__ b1,
     const float* __restrict__ wd, const float* __restrict__ bd, float* __restrict__ D, int ldd, int frames, int K, int N,
-    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes, const float* __restrict__ ups, int ld_ups) {
+    int n_ntiles, int nwg, unsigned a_bytes, unsigned w_bytes, const float* __restrict__ ups, int ld_ups, int ksplit) {
   using G = FSGeom<HW, SR, STRIDE, BN, KF>;
   constexpr int ROWB = G::ROWB, RPI = G::RPI, CPR = ROWB / 16;
   extern __shared__ __attribute__((aligned(16))) char ring[];
@@ -490,7 +563,8 @@ __global__ __launch_bounds__(256, (FSGeom<HW, SR, STRIDE, BN, KF>::occ)) void pw
   const int gy0 = ups_tap((float)(HW / 2 - 1) / (float)(HW - 1), y0 < 0 ? 0 : y0, HW / 2).i0;
   if (ups) ups_tile_load<HW / 2>(sG, ups + (size_t)fr * (HW / 2) * (HW / 2) * ld_ups + n0, ld_ups, gy0, kUpsTileBytes / (HW / 2 * 128), wave, lane);
   f32x4 acc[G::MTW];
-  pw_dw_gemm<G, BN, KF>(ring, A, W1, a_bytes, w_bytes, voff, nk, wave, l15, q, acc);
+  const bool ks = pw_dw_ksplit_runtime<G> ? ksplit != 0 : pw_dw_ksplit<G>;
+  pw_dw_gemm<G, BN, KF>(ring, A, W1, a_bytes, w_bytes, voff, nk, wave, l15, q, acc, ks);
 
   // ---- epilogue 1: + b1 (+ the upsampled addend), LeakyReLU -> the E image; rows outside the frame are zero ----
   using E = typename G::E;
@@ -502,6 +576,7 @@ __global__ __launch_bounds__(256, (FSGeom<HW, SR, STRIDE, BN, KF>::occ)) void pw
     for (int i = 0; i < G::MTW; ++i) {
       const int t = wm + G::WPN * i;
       const int px = 16 * t + l15;
+      if (pw_dw_ksplit<G> && i == G::MTW - 1) continue;   // the shared tile: below
       if (t < G::MT && px < G::M) {
         const int yl = px / HW, x = px - yl * HW, y = y0 + yl;
         const bool inside = y >= 0 && y < HW;
@@ -511,6 +586,16 @@ __global__ __launch_bounds__(256, (FSGeom<HW, SR, STRIDE, BN, KF>::occ)) void pw
         }
         *reinterpret_cast<f32x4*>(sE + E::at(yl, x, 4 * wn + q)) = inside ? lrelu4(v) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
+    }
+    if constexpr (pw_dw_ksplit<G>) {
+      const int px = 16 * (G::MT - 1) + l15, yl = px / HW, x = px - yl * HW, y = y0 + yl;
+      const bool inside = y >= 0 && y < HW;
+      float* slot = sE + E::at(yl, x, 4 * wn + q);
+      shared_tile_sum(slot, px < G::M, wm, ks, acc[G::MTW - 1], [&](f32x4 sum) {
+        f32x4 v = sum + bias;
+        if (ups && inside) v += ups_at_lds<HW>(sG, gy0, y, x, 4 * wn + q);
+        *reinterpret_cast<f32x4*>(slot) = inside ? lrelu4(v) : f32x4{0.f, 0.f, 0.f, 0.f};
+      });
     }
   }
   __syncthreads();
@@ -538,6 +623,10 @@ __global__ __launch_bounds__(256, (FSGeom<HW, SR, STRIDE, BN, KF>::occ)) void pw
   }
 }
 
+// The K split of the frame-pair tile's shared pixel tile: with gemm_streamk = 0 (bits that do not depend on the batch: a frame
+// is the first of its pair in one launch and the second in another) both waves keep the unsplit order.
+inline int pw_dw_ksplit_on() { return casync_opts().gemm_streamk != 0; }
+
 template <int HW, int SR, int STRIDE, int BN, int KF>
 int launch_fs(const float* a, int lda, const float* w1, const float* b1, const float* wd, const float* bd, float* d, int ldd,
               int frames, int k, int n, const float* ups, int ld_ups, hipStream_t stream) {
@@ -553,7 +642,7 @@ int launch_fs(const float* a, int lda, const float* w1, const float* b1, const f
   CASYNC_REQUIRE((long long)frames * G::P < (1ll << 24) && (long long)lda * 4 < (1ll << 24),
                  "pw_dw: %lld rows of %d floats exceed the kernel's 24-bit row arithmetic", (long long)frames * G::P, lda);
   return casync_launch(kern, dim3((unsigned)nwg), dim3(256), G::lds + (ups ? kUpsTileBytes : 0), stream, a, lda, w1, b1, wd, bd, d, ldd, frames, k, n, n_nt,
-                       (int)nwg, (unsigned)ab, (unsigned)wb, ups, ld_ups);
+                       (int)nwg, (unsigned)ab, (unsigned)wb, ups, ld_ups, pw_dw_ksplit_on());
 }
 
 template <int HW, int F, int BN, int KF, int S, int NST = 2, int WD = HW>
@@ -576,7 +665,7 @@ int launch_ft(const float* a, int lda, const float* w1, const float* b1, const f
   CASYNC_REQUIRE((long long)frames * G::P < (1ll << 24) && (long long)lda * 4 < (1ll << 24),
                  "pw_dw: %lld rows of %d floats exceed the kernel's 24-bit row arithmetic", (long long)frames * G::P, lda);
   return casync_launch(kern, dim3((unsigned)nwg), dim3(256), G::lds + (ups ? kUpsTileBytes : 0), stream, a, lda, w1, b1, wd, bd, d, ldd, frames, k, n, n_nt,
-                       (int)nwg, (unsigned)ab, (unsigned)wb, ups, ld_ups);
+                       (int)nwg, (unsigned)ab, (unsigned)wb, ups, ld_ups, pw_dw_ksplit_on());
 }
 
 }  // namespace

@@ -51,6 +51,7 @@ const OptField kFields[] = {
     {"dw_lds_bytes", &CasyncOptions::dw_lds_bytes},
     {"att_nz", &CasyncOptions::att_nz},
     {"kv_early", &CasyncOptions::kv_early},
+    {"conv_skip", &CasyncOptions::conv_skip},
 };
 
 thread_local const CasyncOptions* t_current = nullptr;

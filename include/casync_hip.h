@@ -188,6 +188,15 @@ int casync_op_conv3x3(const void* in, const void* w, const float* bias, void* ou
 int casync_op_conv3x3_ex(const void* in, const void* w, const float* bias, void* out, int batch, int h, int w_,
                          int cin, int cout, int stride_h, int stride_w, int pad, int act, casync_stream stream);
 
+/* What that convolution executes (host only, no device needed).  In fp32 its GEMM rows are position-major -- output positions
+ * sorted by which of their nine taps lie inside the image, frames innermost -- and each 64-row tile walks only the taps
+ * that some row of it has (option conv_skip, default 1; results are bit-identical with 0).  ktile_groups_full: (output
+ * tile, tap) pairs with all nine taps; ktile_groups_run: the pairs walked at the current process options and dtype.
+ * Audio conv5 (16x16, stride 2, pad 3) at batch 32: run / full = 0.649; bf16 launches keep frame-major rows and run == full.
+ * Additive to ABI 13. */
+int casync_conv3x3_plan(int batch, int h, int w_, int cin, int cout, int stride_h, int stride_w, int pad,
+                        int64_t* ktile_groups_full, int64_t* ktile_groups_run);
+
 /* Depthwise 3x3, pad 1, stride 1|2, + bias + LeakyReLU on NHWC.
  * Replaces nn.Conv2d(groups=C,k=3)+BN+LeakyReLU (module/unet.py:21-30).
  * w is tap-major [9][C].                                                    */
