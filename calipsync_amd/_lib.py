@@ -209,6 +209,12 @@ _PROTOS = {
     "casync_op_clip_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_i64, C.c_void_p]),
     "casync_op_clip_compose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_i64, C.c_void_p,
                                          C.c_void_p]),
+    # baseline JPEG of finished frames (additive to ABI 13); jpeg_header is host only and returns the header's length, scratch is
+    # casync_op_jpeg_workspace_bytes long, offsets int64 [batch + 1] and status int32 [batch] on the device
+    "casync_op_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "casync_op_jpeg_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int, c_i64]),
+    "casync_op_jpeg_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -39,7 +39,11 @@ SOURCES_NMS = ["face_nms.hip"]
 # directory, its source an entry of SOURCES in the same way.
 OBJ_DIR_CLIP = os.path.join(LIB_DIR, "obj_clip")
 SOURCES_CLIP = ["clip_ops.hip"]
-SOURCES = ["runtime.hip", "gemm.hip", "ops.hip", "ir_fused.hip", "pw_dw.hip", "pw_dw_bf16.hip", "attention.hip", "attention_bf16.hip", "frame_ops.hip", "hubert.hip", "engine.hip"] + SOURCES_DET + SOURCES_DET16 + SOURCES_FACE + SOURCES_NMS + SOURCES_CLIP
+# The baseline JPEG encoder of finished frames (tests/kernel_ledger_jpeg.py is its ledger): a ninth object directory, its source an
+# entry of SOURCES in the same way.
+OBJ_DIR_JPEG = os.path.join(LIB_DIR, "obj_jpeg")
+SOURCES_JPEG = ["jpeg_enc.hip"]
+SOURCES = ["runtime.hip", "gemm.hip", "ops.hip", "ir_fused.hip", "pw_dw.hip", "pw_dw_bf16.hip", "attention.hip", "attention_bf16.hip", "frame_ops.hip", "hubert.hip", "engine.hip"] + SOURCES_DET + SOURCES_DET16 + SOURCES_FACE + SOURCES_NMS + SOURCES_CLIP + SOURCES_JPEG
 HEADERS = ["common.h", "ir_common.h", "pw_dw_common.h", os.path.join("..", "..", "include", "casync_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 
@@ -131,6 +135,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ_DIR_FACE, exist_ok=True)
     os.makedirs(OBJ_DIR_NMS, exist_ok=True)
     os.makedirs(OBJ_DIR_CLIP, exist_ok=True)
+    os.makedirs(OBJ_DIR_JPEG, exist_ok=True)
     # One builder at a time: bench.py --gpus N, torchrun ranks and pytest workers can all reach load() -> build() at
     # once after a checkout; without the lock they compile into the same obj/*.o and link over a library another rank
     # is dlopen-ing.  The link goes to a temporary name and is renamed into place (atomic on one filesystem).
@@ -151,7 +156,7 @@ def _build_locked(force: bool, verbose: bool) -> str:
     def compile_one(src: str):
         obj_dir = OBJ_DIR_HB16 if src in SOURCES_HB16 else OBJ_DIR_LMK if src in SOURCES_LMK else OBJ_DIR_DET if src in SOURCES_DET else \
             OBJ_DIR_DET16 if src in SOURCES_DET16 else OBJ_DIR_FACE if src in SOURCES_FACE else OBJ_DIR_NMS if src in SOURCES_NMS else \
-            OBJ_DIR_CLIP if src in SOURCES_CLIP else OBJ_DIR
+            OBJ_DIR_CLIP if src in SOURCES_CLIP else OBJ_DIR_JPEG if src in SOURCES_JPEG else OBJ_DIR
         obj = os.path.join(obj_dir, src.replace(".hip", ".o"))
         path = os.path.join(CSRC, src)
         if not force and not _newer(obj, [path] + _header_paths()):

@@ -60,7 +60,8 @@ def _imread(path: str, gray: bool = False) -> Optional[np.ndarray]:
 class FrameSynthesizer:
     def __init__(self, unet_checkpoint: Optional[str], data_dir: Optional[str], device: str = "cuda:0", batch_size: int = 8, *,
                  seed: Optional[int] = None, precision: str = "fp32", net: Optional[Model] = None,
-                 batches_in_flight: Optional[int] = None, resident: Optional[bool] = None, clip=None):
+                 batches_in_flight: Optional[int] = None, resident: Optional[bool] = None, clip=None, output: str = "frames",
+                 jpeg_quality: int = 95):
         """Same positional arguments as the reference (infer_api.py:13-14).  Keyword-only extensions:
         ``seed`` (reproducible frame walk), ``precision`` (engine storage type), ``net`` (an already
         loaded ``Model`` instead of a checkpoint path), ``batches_in_flight`` (default 1, or the
@@ -74,13 +75,25 @@ class FrameSynthesizer:
         ``resident`` (default False, or the ``CASYNC_RESIDENT_CLIP`` environment variable): keep the clip on the device
         (``resident_clip.ResidentClip``): ``data_dir`` is read once, on the first ``iterate_synthesized_frames``, and a batch
         sends only its records up; the frames yielded are those of ``resident=False`` byte for byte.  ``clip``: a
-        ``ResidentClip`` made elsewhere (``from_frames``: no directory at all); ``data_dir`` may then be None."""
+        ``ResidentClip`` made elsewhere (``from_frames``: no directory at all); ``data_dir`` may then be None.
+
+        ``output`` ("frames", the default, or "jpeg"; "jpeg" needs the resident path): the items of
+        ``iterate_synthesized_frames`` carry ``'jpeg'``, the frame as a complete baseline JPEG file of ``jpeg_quality``
+        encoded on the device (``jpeg.encode_jpeg_device``), in place of ``'frame'``; no raw frame crosses to the host."""
         if resident is None:
             resident = clip is not None or os.environ.get("CASYNC_RESIDENT_CLIP", "0").lower() not in ("", "0", "false")
         if clip is not None and not resident:
             raise ValueError("clip= is the resident path: resident=False contradicts it")
         if clip is None and data_dir is None:
             raise ValueError("data_dir may only be None with clip=")
+        if output not in ("frames", "jpeg"):
+            raise ValueError(f"output must be 'frames' or 'jpeg', got {output!r}")
+        if output == "jpeg":
+            if not resident:
+                raise ValueError("output='jpeg' encodes the frames where they lie on the device: it needs resident=True or clip=")
+            from . import jpeg
+            jpeg.quant_tables(jpeg_quality)         # ValueError for a quality outside 1..100
+        self.output, self.jpeg_quality = output, int(jpeg_quality)
         self.resident, self._clip = bool(resident), clip
         if batches_in_flight is None:
             batches_in_flight = int(os.environ.get("CASYNC_BATCHES_IN_FLIGHT", "1"))
@@ -181,18 +194,22 @@ class FrameSynthesizer:
 
     def _submit_resident(self, frame_sequence, features_dev, indices):
         """The same on the resident clip: the originals are fetched from the device only if they are needed."""
-        originals = lambda: self._clip.fetch(frame_sequence).result()
+        raw = self.output != "jpeg"                  # the raw download is left out when only the JPEG bytes are wanted
+        originals = lambda: self._result(self._clip.fetch(frame_sequence, download=raw))
         try:
-            return self._clip.submit(self.net, frame_sequence, features=features_dev, frame_indices=indices), originals
+            return self._clip.submit(self.net, frame_sequence, features=features_dev, frame_indices=indices, download=raw), originals
         except Exception as exc:
             print(f"process_batch failed, returning the original frames: {exc!r}")
             return None, originals
 
-    @staticmethod
-    def _collect(pending, originals) -> list:
+    def _result(self, pending) -> list:
+        """What a batch of the resident clip hands out: its frames, or (output="jpeg") their JPEG files."""
+        return pending.result_jpeg(self.jpeg_quality) if self.output == "jpeg" else pending.result()
+
+    def _collect(self, pending, originals) -> list:
         if pending is not None:
             try:
-                return pending.result()
+                return self._result(pending)
             except Exception as exc:
                 print(f"process_batch failed, returning the original frames: {exc!r}")
         return originals() if callable(originals) else originals
@@ -222,7 +239,8 @@ class FrameSynthesizer:
                     if self.resident:
                         t0 = time.time()
                         if not is_generate_sync_frame:      # pass-through mode: the stored frames, from the device
-                            yield from self._emit(self._clip.fetch(frame_sequence).result(), frame_sequence)
+                            yield from self._emit(self._result(self._clip.fetch(frame_sequence, download=self.output != "jpeg")),
+                                                  frame_sequence)
                             continue
                         pending, originals = self._submit_resident(frame_sequence, features_dev, list(range(batch_start, batch_end)))
                         in_flight.append((pending, originals, frame_sequence))
@@ -257,7 +275,11 @@ class FrameSynthesizer:
                 yield from self._drain_one(in_flight, time_stats)
         except Exception as exc:                # fatal: one black frame so the consumer does not hang (:438-446)
             print(f"frame iterator failed: {exc!r}")
-            yield from self._emit([np.zeros((480, 640, 3), dtype=np.uint8)], [0])
+            black = np.zeros((480, 640, 3), dtype=np.uint8)
+            if self.output == "jpeg":
+                from . import jpeg
+                black = jpeg.encode_jpeg_host(black, self.jpeg_quality)
+            yield from self._emit([black], [0])
         finally:
             total_time = sum(time_stats.values())
             if total_time > 0:
@@ -276,7 +298,7 @@ class FrameSynthesizer:
         """The iterator's items (infer_api.py:400-405): consecutive logical indices over whatever is handed out."""
         for frame, physical in zip(frames, physical_indices):
             self.last_logical_index += 1
-            yield {"frame": frame, "index": self.last_logical_index, "physical_index": physical}
+            yield {"jpeg" if self.output == "jpeg" else "frame": frame, "index": self.last_logical_index, "physical_index": physical}
 
     def __del__(self):
         if hasattr(self, "executor"):
@@ -290,7 +312,9 @@ class VideoStreamManager:
     (``calipsync_amd.hubert.HubertExtractor``, HubertModel on the HIP engine) is built from it on the first audio file
     that is not a ``.npy``, in ``hubert_precision`` ("fp32", the default, or "bf16").  It may also be a callable ``audio_path -> [T,2,1024] array``, and it is not used when
     ``audio_path`` is itself a ``.npy`` of features.  The mp4 writer / ffmpeg mux (inference.py:88-110) is used when cv2 / ffmpeg exist; otherwise
-    the frames are written as a Motion-JPEG ``.avi`` with Pillow (``mjpeg_avi.py``; no audio track)."""
+    the frames are written as a Motion-JPEG ``.avi`` with Pillow (``mjpeg_avi.py``; no audio track).  With ``output="jpeg",
+    resident=True`` (passed on to ``FrameSynthesizer``) the frames are JPEG-encoded on the device and ``<stem>.avi`` is written
+    from those bytes, wherever cv2 exists or not: no raw frame is held on the host."""
 
     def __init__(self, data_dir: str, unet_checkpoint: Optional[str], hubert_path=None, device: str = "cuda:0",
                  batch_size: int = 8, output_sample_rate: int = 24000, hubert_precision: str = "fp32", **synth_kwargs):
@@ -318,6 +342,16 @@ class VideoStreamManager:
                 raise RuntimeError("no HuBERT extractor configured: pass pre-extracted features (.npy), a HuBERT checkpoint "
                                    "directory or a callable")
             features = self.hubert_extractor(audio_path)
+        if self.synthesizer.output == "jpeg":
+            from . import mjpeg_avi
+            files = [info["jpeg"] for info in self.synthesizer.iterate_synthesized_frames(features, 0, True)]
+            if not files:
+                raise ValueError("no video frame was generated")
+            out = os.path.splitext(output_path)[0] + ".avi"
+            print(f"VideoStreamManager: output='jpeg' -- writing {out} (Motion-JPEG AVI of the device-encoded frames, {self.fps} fps, "
+                  f"NO audio track) instead of {output_path}")
+            mjpeg_avi.write_mjpeg_avi(out, files, fps=self.fps)
+            return out
         frames = [info["frame"] for info in self.synthesizer.iterate_synthesized_frames(features, 0, True)]
         if not frames:
             raise ValueError("no video frame was generated")

@@ -34,11 +34,31 @@ def encode_jpeg(frame_bgr: np.ndarray, quality: int = 95) -> bytes:
     return buf.getvalue()
 
 
+def jpeg_size(data) -> tuple:
+    """(height, width) of an encoded JPEG, from its SOF0..SOF2 segment (a walk over the marker segments ahead of the scan)."""
+    d = bytes(data[:2]) if len(data) >= 2 else b""
+    if d != b"\xff\xd8":
+        raise ValueError("an encoded frame must be a JPEG file (no SOI marker)")
+    pos, n = 2, len(data)
+    while pos + 4 <= n:
+        if data[pos] != 0xFF:
+            break
+        marker, length = data[pos + 1], (data[pos + 2] << 8) | data[pos + 3]
+        if marker in (0xC0, 0xC1, 0xC2) and pos + 9 <= n:
+            return (data[pos + 5] << 8) | data[pos + 6], (data[pos + 7] << 8) | data[pos + 8]
+        if marker == 0xDA:
+            break
+        pos += 2 + length
+    raise ValueError("an encoded frame has no SOF segment ahead of its scan")
+
+
 RIFF_LIMIT = (1 << 32) - (1 << 20)     # 32-bit RIFF sizes (plain AVI, no OpenDML segments): stop a MiB short of 4 GiB
 
 
 def write_mjpeg_avi(path: str, frames: Iterable[np.ndarray], fps: float = 25.0, quality: int = 95) -> int:
-    """Write `frames` (BGR uint8, all the same size) to `path` as Motion-JPEG AVI; returns the frame count.
+    """Write `frames` (BGR uint8, all the same size) to `path` as Motion-JPEG AVI; returns the frame count.  An item that is
+    `bytes` / `bytearray` / `memoryview` is an already encoded JPEG (``jpeg.encode_jpeg_device``): it is stored as it is, its
+    size read from its SOF segment; arrays and encoded items may be mixed.
 
     Frames are encoded and written one at a time (one JPEG in memory, not the clip); the header fields that depend on
     the whole clip (frame count, largest chunk, RIFF / LIST sizes) are patched when the last frame is on disk.  The
@@ -52,8 +72,10 @@ def write_mjpeg_avi(path: str, frames: Iterable[np.ndarray], fps: float = 25.0, 
     fh = None
     try:
         for f in frames:
+            encoded = isinstance(f, (bytes, bytearray, memoryview))
+            size = jpeg_size(f) if encoded else tuple(f.shape[:2])
             if width is None:
-                height, width = f.shape[:2]
+                height, width = size
                 fh = open(path, "wb")
                 # header with the clip-dependent fields zeroed: patched below (positions recorded as they are written)
                 avih = struct.pack("<14I", usec, 0, 0, 0x10, 0, 0, 1, 0, width, height, 0, 0, 0, 0)   # 0x10 = AVIF_HASINDEX
@@ -64,9 +86,9 @@ def write_mjpeg_avi(path: str, frames: Iterable[np.ndarray], fps: float = 25.0, 
                 movi_at = fh.tell()
                 fh.write(b"LIST" + struct.pack("<I", 0) + b"movi")
                 off = 4                                              # idx1 offsets count from the 'movi' fourcc
-            elif f.shape[:2] != (height, width):
+            elif size != (height, width):
                 raise ValueError("all frames of a video must have the same size")
-            j = encode_jpeg(f, quality)
+            j = bytes(f) if encoded else encode_jpeg(f, quality)
             chunk = _chunk(b"00dc", j)
             if fh.tell() + len(chunk) + 16 * (n + 1) + 8 > RIFF_LIMIT:
                 raise ValueError(f"{path}: the clip passes the 4 GiB limit of a plain AVI file at frame {n} "

@@ -9,6 +9,7 @@ crop geometry is computed ONCE, and a batch sends a few KB of records up:
     pending = clip.submit(net, indices, features=features_dev, frame_indices=[...])
     frames = pending.result()               # B new [H,W,3] uint8 arrays, ONE download
     frames_dev = pending.result_device()    # or the [B,H,W,3] uint8 device tensor, no download
+    files = pending.result_jpeg(95)         # or B JPEG files encoded on the device (jpeg.py); submit with download=False
 
 ``casync_op_clip_gather`` cuts the crop boxes out of the resident frames into the packed ``regions`` layout,
 ``frame_loop.regions_through_net`` (the tail ``submit_batch_device`` runs too) blends them, ``casync_op_clip_compose``
@@ -127,6 +128,14 @@ class PendingClipBatch:
             host, self._host = self._host, None
             self._frames = _hand_out(host, b, h, w)
         return self._frames
+
+    def result_jpeg(self, quality: int = 95) -> List[bytes]:
+        """The finished frames as B complete baseline JPEG files (4:4:4, one restart interval per block row), encoded on the
+        device where ``result_device()`` lies (``jpeg.encode_jpeg_device``, on torch's current stream): what crosses to the
+        host is the compressed bytes.  The raw download is not run; when this is the only result wanted, submit with
+        ``download=False``."""
+        from . import jpeg
+        return jpeg.encode_jpeg_device(self._out, quality)
 
 
 class _Chunks:

@@ -46,7 +46,7 @@ enum {
 #define CASYNC_ABI_VERSION 13  /* 12: S3FD face detector handle (casync_s3fd_*, casync_op_s3fd_*); 13: its bf16 precision
                                 * (casync_s3fd_create_ex, _precision, _workspace_bytes_ex, casync_op_s3fd16_*).  The face-pipeline
                                 * operators at the end of this file (casync_op_resize_linear_u8, _face_crops192, _s3fd_candidates,
-                                * _landmarks_finalize), casync_op_s3fd_nms and casync_op_clip_gather / _compose were added under 13: new symbols only, no prototype or layout changed */
+                                * _landmarks_finalize), casync_op_s3fd_nms, casync_op_clip_gather / _compose and casync_op_jpeg_* were added under 13: new symbols only, no prototype or layout changed */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -631,6 +631,34 @@ int  casync_op_clip_gather(const uint8_t* frames, int n_frames, int H, int W, co
                            int64_t regions_bytes, casync_stream stream);
 int  casync_op_clip_compose(const uint8_t* frames, int n_frames, int H, int W, const int32_t* rec, int batch,
                             const uint8_t* out_regions, int64_t regions_bytes, uint8_t* out, casync_stream stream);
+
+/* ---- baseline JPEG of finished frames (additive to ABI 13: three new symbols, nothing else changed) ---------------- */
+/* uint8 BGR frames [batch,H,W,3] on the device -> `batch` complete JFIF files in one contiguous device buffer.  The stream:
+ * SOI, APP0 (JFIF 1.1, density 1 x 1), DQT 0 and 1 (8-bit, zigzag), SOF0 (4:4:4, tables 0, 1, 1), the four Annex K DHT, DRI (one
+ * restart interval per row of 8 x 8 blocks), SOS: 629 bytes for any size and quality; then the scan, every block row padded
+ * with 1-bits and closed by RSTn (n counts rows from 0, modulo 8), the last one by EOI.  The arithmetic is libjpeg's integer
+ * baseline path (16-bit fixed-point colour, accurate integer DCT, round-half-away quantisation by 8 Q), so the bytes are those
+ * of libjpeg-turbo for quality q, no subsampling and one restart interval per block row (calipsync_amd/jpeg.py holds the numpy
+ * twin; tests/golden/jpeg_cases.npz the recorded bytes).
+ *   jpeg_header:          HOST ONLY.  Writes the 629 header bytes to out (host memory, cap >= 629) and returns their number.
+ *   jpeg_workspace_bytes: the scratch a batch needs: the row lengths, then one slot of slot_bytes per block row of every frame.
+ *     slot_bytes 0 = the default, twice the raw bytes of a block row: 2 * 8 * 3 * 8 * ceil(W / 8).
+ *   jpeg_encode:          scratch (4-byte aligned, scratch_bytes >= jpeg_workspace_bytes), out [out_cap], offsets int64 [batch + 1]
+ *     and status int32 [batch] are device memory.  out[offsets[i] .. offsets[i+1]) is frame i's complete file when status[i] == 0.
+ *     status 1: a block row outgrew its slot (uniform noise at quality 100 is about 1.4 x its raw size; the worst case of a block
+ *     is far larger); status 2: the frame would pass out_cap.  A failed frame contributes zero bytes (offsets[i+1] == offsets[i]),
+ *     the frames behind it follow on; no frame writes outside its slots or past out[offsets[batch]].  The two quantisation tables
+ *     and the header are computed on the host and travel as kernel arguments.
+ * Refused with a negative status before anything is launched: H or W outside 1..65535, quality outside 1..100, batch < 0,
+ * slot_bytes < 0, out_cap < 0, a null or misaligned pointer, a scratch that is too small.  batch 0 returns 0 and touches nothing.
+ * One wave per block row (colour, DCT and quantisation in registers, the code bits through a 32 KB LDS buffer), one workgroup
+ * for the prefix over rows and frames, one workgroup per row for the compaction.  The output is a pure function of the input:
+ * no global atomics, one writer per byte.  No allocation, no synchronisation.                                            */
+int     casync_op_jpeg_header(int H, int W, int quality, uint8_t* out, int cap);
+int64_t casync_op_jpeg_workspace_bytes(int batch, int H, int W, int64_t slot_bytes);
+int     casync_op_jpeg_encode(const uint8_t* frames_bgr, int batch, int H, int W, int quality, int64_t slot_bytes, uint8_t* scratch,
+                              int64_t scratch_bytes, uint8_t* out, int64_t out_cap, int64_t* offsets, int32_t* status,
+                              casync_stream stream);
 
 #ifdef __cplusplus
 }
