@@ -8,6 +8,8 @@ import ctypes as C
 import os
 from typing import Optional
 
+import numpy as np
+
 from . import build as _build
 
 _lib: Optional[C.CDLL] = None
@@ -284,43 +286,52 @@ def check(status: int, what: str) -> int:
 AUDIO_MODES = {"hubert": 0, "wenet": 1}
 
 
-def packed_layout(mode: str = "hubert"):
-    """[(name, offset, size)] in floats, and the total, of one audio mode -- the engine owns the layout."""
+def _layout(prefix: str, *args, suffix: str = ""):
+    """[(name, offset, size)] in floats, and the total, of the packed buffer that
+    casync_<prefix>packed_{count,name,offset,size,total}<suffix>(*args, ...) describe."""
     lib = load()
-    m = AUDIO_MODES[mode]
-    if m == 0:
-        n = lib.casync_packed_count()
-        items = [(lib.casync_packed_name(i).decode(), lib.casync_packed_offset(i),
-                  lib.casync_packed_size(i)) for i in range(n)]
-        return items, lib.casync_packed_total()
-    n = lib.casync_packed_count_m(m)
-    items = [(lib.casync_packed_name_m(m, i).decode(), lib.casync_packed_offset_m(m, i),
-              lib.casync_packed_size_m(m, i)) for i in range(n)]
-    return items, lib.casync_packed_total_m(m)
+    count, name, offset, size, total = (getattr(lib, f"casync_{prefix}packed_{f}{suffix}")
+                                        for f in ("count", "name", "offset", "size", "total"))
+    return [(name(*args, i).decode(), offset(*args, i), size(*args, i)) for i in range(count(*args))], total(*args)
+
+
+def packed_layout(mode: str = "hubert"):
+    """The layout of one audio mode of the U-Net -- the engine owns the layout."""
+    return _layout("", AUDIO_MODES[mode], suffix="_m")
 
 
 def hubert_layout(layers: int):
-    """[(name, offset, size)] in floats, and the total, of the HuBERT engine's packed buffer for `layers` layers."""
-    lib = load()
-    n = lib.casync_hubert_packed_count(layers)
-    if n <= 0:
+    """The layout of the HuBERT engine's packed buffer for `layers` layers."""
+    if load().casync_hubert_packed_count(layers) <= 0:
         raise ValueError(f"HuBERT engine: no packed layout for {layers} layers")
-    items = [(lib.casync_hubert_packed_name(layers, i).decode(), lib.casync_hubert_packed_offset(layers, i),
-              lib.casync_hubert_packed_size(layers, i)) for i in range(n)]
-    return items, lib.casync_hubert_packed_total(layers)
+    return _layout("hubert_", layers)
 
 
 def pfld_layout():
-    """[(name, offset, size)] in floats, and the total, of the PFLD landmark engine's packed buffer."""
-    lib = load()
-    items = [(lib.casync_pfld_packed_name(i).decode(), lib.casync_pfld_packed_offset(i), lib.casync_pfld_packed_size(i))
-             for i in range(lib.casync_pfld_packed_count())]
-    return items, lib.casync_pfld_packed_total()
+    """The layout of the PFLD landmark engine's packed buffer."""
+    return _layout("pfld_")
 
 
 def s3fd_layout():
-    """[(name, offset, size)] in floats, and the total, of the S3FD face-detector engine's packed buffer."""
-    lib = load()
-    items = [(lib.casync_s3fd_packed_name(i).decode(), lib.casync_s3fd_packed_offset(i), lib.casync_s3fd_packed_size(i))
-             for i in range(lib.casync_s3fd_packed_count())]
-    return items, lib.casync_s3fd_packed_total()
+    """The layout of the S3FD face-detector engine's packed buffer."""
+    return _layout("s3fd_")
+
+
+def pack_named(named: dict, layout) -> np.ndarray:
+    """{name: array} -> the flat float32 buffer of `layout` (items, total).  `named` is emptied; ValueError for a tensor of
+    another size than the layout's and for names the layout does not hold."""
+    items, total = layout
+    buf = np.zeros(total, dtype=np.float32)
+    for name, off, size in items:
+        a = named.pop(name).reshape(-1)
+        if a.size != size:
+            raise ValueError(f"packed tensor {name}: {a.size} floats, the engine expects {size}")
+        buf[off:off + size] = a
+    if named:
+        raise ValueError(f"tensors the engine layout does not name: {sorted(named)}")
+    return buf
+
+
+def unpack_named(buf: np.ndarray, layout) -> dict:
+    """Inverse of pack_named (flat shapes, views of buf)."""
+    return {name: buf[off:off + size] for name, off, size in layout[0]}

@@ -44,7 +44,7 @@ SOURCES_CLIP = ["clip_ops.hip"]
 OBJ_DIR_JPEG = os.path.join(LIB_DIR, "obj_jpeg")
 SOURCES_JPEG = ["jpeg_enc.hip"]
 SOURCES = ["runtime.hip", "gemm.hip", "ops.hip", "ir_fused.hip", "pw_dw.hip", "pw_dw_bf16.hip", "attention.hip", "attention_bf16.hip", "frame_ops.hip", "hubert.hip", "engine.hip"] + SOURCES_DET + SOURCES_DET16 + SOURCES_FACE + SOURCES_NMS + SOURCES_CLIP + SOURCES_JPEG
-HEADERS = ["common.h", "ir_common.h", "pw_dw_common.h", os.path.join("..", "..", "include", "casync_hip.h")]
+HEADERS = ["common.h", "handle.h", "ir_common.h", "pw_dw_common.h", os.path.join("..", "..", "include", "casync_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 
 

@@ -335,7 +335,7 @@ int launch_hb16_layernorm1024(float* h, int ldh, const void* delta, int ldd, boo
 int launch_hb16_gelu(void* x, long long n, hipStream_t s);                     // exact GELU in place, n % 8 == 0
 int launch_hb16_widen(const void* in, float* out, long long n, hipStream_t s); // bf16 -> fp32, n % 8 == 0
 int launch_hb16_attention(const void* qkv, void* out, int batch, int T, hipStream_t s);
-// fp32 -> bf16 image of n floats (n % 4 == 0), the conversion of the bf16 U-Net handle's weight image (engine.hip)
+// fp32 -> bf16 image of n floats (n % 4 == 0): the weight image of every bf16 handle (PackedWeights, handle.h); kernel in engine.hip
 int launch_f32_to_bf16(const float* in, void* out, long long n, hipStream_t s);
 
 // ---- S3FD, bf16 handle (facedet_bf16.hip; pointers named void* are bf16, NHWC, C % 8 == 0) ----

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.h"
+#include "handle.h"
 
 // ------------------------------------------------------------------ error text
 static thread_local char g_err[512] = "";
@@ -71,49 +72,31 @@ constexpr int kBlocks = 4;          // attention blocks
 constexpr int kKV = 64 + 512;       // per-block [K | V] projection columns
 
 // ------------------------------------------------------------------ packed weights
-struct Packed {
-  std::string name;
-  int64_t offset, size;
-};
+void add_ir(PackedLayout& l, const IR& b) {
+  const std::string p = b.prefix;
+  l.add(p + ".pw1.w", (int64_t)b.cexp() * b.cin);
+  l.add(p + ".pw1.b", b.cexp());
+  l.add(p + ".dw.w", 9 * (int64_t)b.cexp());
+  l.add(p + ".dw.b", b.cexp());
+  l.add(p + ".pw2.w", (int64_t)b.cout * b.cexp());
+  l.add(p + ".pw2.b", b.cout);
+}
 
-struct Layout {
-  std::vector<Packed> items;
-  int64_t total = 0;
-  void add(const std::string& name, int64_t size) {
-    items.push_back({name, total, size});
-    total += (size + 63) / 64 * 64;  // 256-B aligned tensors
-  }
-  void add_ir(const IR& b) {
-    const std::string p = b.prefix;
-    add(p + ".pw1.w", (int64_t)b.cexp() * b.cin);
-    add(p + ".pw1.b", b.cexp());
-    add(p + ".dw.w", 9 * (int64_t)b.cexp());
-    add(p + ".dw.b", b.cexp());
-    add(p + ".pw2.w", (int64_t)b.cout * b.cexp());
-    add(p + ".pw2.b", b.cout);
-  }
-  int64_t off(const std::string& name) const {
-    for (const auto& it : items)
-      if (it.name == name) return it.offset;
-    return -1;
-  }
-};
-
-Layout make_layout(int mode) {
+PackedLayout make_layout(int mode) {
     const bool wenet = mode == CASYNC_AUDIO_WENET;
-    Layout l;
+    PackedLayout l;
     l.add("inc.inconv.0.fused", 620);  // [w1T 6x12][b1 12][wd 9x12][bd 12][w2T 12x32][b2 32]
     for (auto& st : kDown)
-      for (auto& b : st) l.add_ir(b);
-    l.add_ir(wenet ? kAudioW[0] : kAudio[0]);
-    l.add_ir(wenet ? kAudioW[1] : kAudio[1]);
+      for (auto& b : st) add_ir(l, b);
+    add_ir(l, wenet ? kAudioW[0] : kAudio[0]);
+    add_ir(l, wenet ? kAudioW[1] : kAudio[1]);
     l.add("audio_model.conv3.w", 256ll * 9 * (wenet ? 256 : 128));  // [N][(ky,kx,cin)]
     l.add("audio_model.conv3.b", 256);
-    l.add_ir(kAudio[2]);
+    add_ir(l, kAudio[2]);
     l.add("audio_model.conv5.w", 512ll * 9 * 256);
     l.add("audio_model.conv5.b", 512);
-    l.add_ir(kAudio[3]);
-    l.add_ir(kAudio[4]);
+    add_ir(l, kAudio[3]);
+    add_ir(l, kAudio[4]);
     if (!wenet) {   // AudioConvWenet ends at conv7: no bn7 / relu7 (module/unet.py:135-144)
       l.add("audio_model.bn7.s", 512);
       l.add("audio_model.bn7.t", 512);
@@ -142,9 +125,9 @@ Layout make_layout(int mode) {
     }
     l.add("bn_kx.s", 1024);
     l.add("bn_kx.t", 1024);
-    for (auto& b : kFuse) l.add_ir(b);
+    for (auto& b : kFuse) add_ir(l, b);
     for (auto& st : kUp)
-      for (auto& b : st) l.add_ir(b);
+      for (auto& b : st) add_ir(l, b);
     // Up blocks: the two K-halves of the first block's expand matrix as matrices of their own -- [cexp][cin/2] for the
     // upsampled input (applied at the low resolution: upsample and 1x1 conv commute) and for the skip
     for (auto& st : kUp) {
@@ -157,8 +140,8 @@ Layout make_layout(int mode) {
 }
 
 // the packed layout of an audio mode (anything but CASYNC_AUDIO_WENET: the HuBERT one)
-const Layout& layout(int mode = CASYNC_AUDIO_HUBERT) {
-  static const Layout L[2] = {make_layout(CASYNC_AUDIO_HUBERT), make_layout(CASYNC_AUDIO_WENET)};
+const PackedLayout& layout(int mode = CASYNC_AUDIO_HUBERT) {
+  static const PackedLayout L[2] = {make_layout(CASYNC_AUDIO_HUBERT), make_layout(CASYNC_AUDIO_WENET)};
   return L[mode == CASYNC_AUDIO_WENET ? 1 : 0];
 }
 
@@ -289,29 +272,13 @@ struct Arena {
   }
 };
 
-// hipSetDevice for the life of a scope (the caller's device is restored on exit)
-struct DeviceGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DeviceGuard(int dev) {
-    err = hipGetDevice(&prev);
-    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
-    else if (err == hipSuccess) prev = -1;   // nothing to restore
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 }  // namespace
 
 struct casync_engine {
   int device = 0;
   int dtype = DT_F32;        // activation storage type (DT_BF16: bf16 activations + bf16 GEMM weights)
   int mode = CASYNC_AUDIO_HUBERT;   // audio encoder (fixed at creation): selects the packed layout, the arena and encode()'s branch
-  const float* w = nullptr;  // packed weights on the device (fp32: biases, scales, DW / fused-IR weights)
-  float* owned = nullptr;
-  bf16_t* w16 = nullptr;     // bf16 image of the whole packed buffer (same element offsets), DT_BF16 only
+  PackedWeights pw;          // fp32: biases, scales, DW / fused-IR weights; the bf16 image (DT_BF16 only): the GEMM matrices
   // stream-K scratch of the GEMMs (gemm.hip): one private region per stream that can run a GEMM
   // (lane x {main, audio}), counters zeroed once here and left zeroed by every launch
   char* sk = nullptr;
@@ -331,10 +298,10 @@ struct casync_engine {
   bool streams_ready = false;
   CasyncOptions opt;         // this handle's switches: process defaults at create, casync_set_option afterwards
   CasyncOptions eff;         // what the forward in progress runs under (run_forward: `opt` + the bf16 large-batch plan)
-  const float* W(const std::string& name) const { return w + layout(mode).off(name); }
+  const float* W(const std::string& name) const { return pw.w + layout(mode).off(name); }
   // GEMM weight matrix in the engine's storage type
   const void* WG(const std::string& name) const {
-    return dtype == DT_BF16 ? (const void*)(w16 + layout(mode).off(name)) : (const void*)(w + layout(mode).off(name));
+    return dtype == DT_BF16 ? (const void*)(pw.w16 + layout(mode).off(name)) : (const void*)(pw.w + layout(mode).off(name));
   }
 };
 
@@ -904,7 +871,7 @@ int check_forward_args(casync_handle h, const float* x, const float* a, float* o
   CASYNC_REQUIRE(h, "null handle");
   CASYNC_REQUIRE(x && a && out && ws, "forward: null pointer");
   CASYNC_REQUIRE(batch > 0 && batch <= 8192, "forward: batch %d out of range [1, 8192]", batch);
-  if (!h->w) {
+  if (!h->pw.w) {
     casync_set_error("forward: weights not loaded");
     return CASYNC_ERR_STATE;
   }
@@ -983,19 +950,15 @@ void casync_gate_forget(int device, const void* owner, hipEvent_t* ev) {
 extern "C" {
 
 int casync_abi_version(void) { return CASYNC_ABI_VERSION; }
-int casync_packed_count(void) { return (int)layout().items.size(); }
-const char* casync_packed_name(int i) {
-  return (i >= 0 && i < casync_packed_count()) ? layout().items[i].name.c_str() : nullptr;
-}
-int64_t casync_packed_offset(int i) { return (i >= 0 && i < casync_packed_count()) ? layout().items[i].offset : -1; }
-int64_t casync_packed_size(int i) { return (i >= 0 && i < casync_packed_count()) ? layout().items[i].size : -1; }
+int casync_packed_count(void) { return layout().count(); }
+const char* casync_packed_name(int i) { return layout().name(i); }
+int64_t casync_packed_offset(int i) { return layout().offset(i); }
+int64_t casync_packed_size(int i) { return layout().size(i); }
 int64_t casync_packed_total(void) { return layout().total; }
-int casync_packed_count_m(int mode) { return audio_mode_ok(mode) ? (int)layout(mode).items.size() : 0; }
-const char* casync_packed_name_m(int mode, int i) {
-  return (i >= 0 && i < casync_packed_count_m(mode)) ? layout(mode).items[i].name.c_str() : nullptr;
-}
-int64_t casync_packed_offset_m(int mode, int i) { return (i >= 0 && i < casync_packed_count_m(mode)) ? layout(mode).items[i].offset : -1; }
-int64_t casync_packed_size_m(int mode, int i) { return (i >= 0 && i < casync_packed_count_m(mode)) ? layout(mode).items[i].size : -1; }
+int casync_packed_count_m(int mode) { return audio_mode_ok(mode) ? layout(mode).count() : 0; }
+const char* casync_packed_name_m(int mode, int i) { return audio_mode_ok(mode) ? layout(mode).name(i) : nullptr; }
+int64_t casync_packed_offset_m(int mode, int i) { return audio_mode_ok(mode) ? layout(mode).offset(i) : -1; }
+int64_t casync_packed_size_m(int mode, int i) { return audio_mode_ok(mode) ? layout(mode).size(i) : -1; }
 int64_t casync_packed_total_m(int mode) { return audio_mode_ok(mode) ? layout(mode).total : -1; }
 int64_t casync_workspace_bytes(int batch) {
   return batch > 0 ? Arena::bytes(casync_default_options(), batch, 4) : -1;
@@ -1037,18 +1000,7 @@ int casync_create_mode(int device_id, int dtype, int audio_mode, casync_handle* 
   CASYNC_REQUIRE(out, "create: null out");
   CASYNC_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "create: dtype %d (0 = fp32, 1 = bf16)", dtype);
   CASYNC_REQUIRE(audio_mode_ok(audio_mode), "create: audio mode %d (0 = hubert, 1 = wenet)", audio_mode);
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    casync_set_error("create: no HIP device visible");
-    return CASYNC_ERR_NO_DEVICE;
-  }
-  CASYNC_REQUIRE(device_id >= 0 && device_id < n, "create: device %d of %d", device_id, n);
-  hipDeviceProp_t prop;
-  CASYNC_CHECK_HIP(hipGetDeviceProperties(&prop, device_id));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-    casync_set_error("create: device %d is %s; this library is built for gfx950 only", device_id, prop.gcnArchName);
-    return CASYNC_ERR_NO_DEVICE;
-  }
+  if (int st = casync_require_gfx950("create", device_id)) return st;
   casync_engine* e = new casync_engine();
   e->device = device_id;
   e->dtype = dtype;
@@ -1097,51 +1049,19 @@ void casync_destroy(casync_handle h) {
     if (h->ev_start) (void)hipEventDestroy(h->ev_start);
     if (h->ev_start2) (void)hipEventDestroy(h->ev_start2);
   }
-  if (h->owned) (void)hipFree(h->owned);
-  if (h->w16) (void)hipFree(h->w16);
+  h->pw.release();
   if (h->sk) (void)hipFree(h->sk);
   delete h;
 }
 
-// bf16 image of the packed buffer; runs on the engine's device whatever the caller's current device is
-static int refresh_bf16_weights(casync_handle h, int64_t n) {
-  if (h->dtype != DT_BF16) return CASYNC_OK;
-  DeviceGuard guard(h->device);
-  CASYNC_CHECK_HIP(guard.err);
-  if (!h->w16) CASYNC_CHECK_HIP(hipMalloc((void**)&h->w16, n * sizeof(bf16_t)));
-  const long long blocks = (n / 4 + 255) / 256;   // packed total is a multiple of 64 floats
-  if (int st = casync_launch(f32_to_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, h->w, h->w16, (long long)n)) return st;
-  CASYNC_CHECK_HIP(hipDeviceSynchronize());   // one-time, at weight load (not on the forward path)
-  return CASYNC_OK;
-}
-
 int casync_load_weights_host(casync_handle h, const float* packed, int64_t n_floats) {
-  CASYNC_REQUIRE(h && packed, "load_weights: null");
-  CASYNC_REQUIRE(n_floats == layout(h->mode).total, "load_weights: %lld floats, layout needs %lld",
-                 (long long)n_floats, (long long)layout(h->mode).total);
-  {
-    DeviceGuard guard(h->device);
-    CASYNC_CHECK_HIP(guard.err);
-    if (!h->owned) CASYNC_CHECK_HIP(hipMalloc((void**)&h->owned, n_floats * sizeof(float)));
-    CASYNC_CHECK_HIP(hipMemcpy(h->owned, packed, n_floats * sizeof(float), hipMemcpyHostToDevice));
-  }
-  h->w = h->owned;
-  return refresh_bf16_weights(h, n_floats);
+  CASYNC_REQUIRE(h, "load_weights: null");
+  return h->pw.load_host("load_weights", h->device, packed, n_floats, layout(h->mode).total, h->dtype == DT_BF16);
 }
 
 int casync_load_weights_device(casync_handle h, const float* packed_dev, int64_t n_floats) {
-  CASYNC_REQUIRE(h && packed_dev, "load_weights_device: null");
-  CASYNC_REQUIRE(n_floats == layout(h->mode).total, "load_weights_device: %lld floats, layout needs %lld",
-                 (long long)n_floats, (long long)layout(h->mode).total);
-  CASYNC_REQUIRE(((uintptr_t)packed_dev % 256) == 0, "load_weights_device: buffer must be 256-B aligned");
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, packed_dev) == hipSuccess && attr.type == hipMemoryTypeDevice)
-    CASYNC_REQUIRE(attr.device == h->device, "load_weights_device: buffer lives on device %d, the engine on %d",
-                   attr.device, h->device);
-  else
-    (void)hipGetLastError();
-  h->w = packed_dev;
-  return refresh_bf16_weights(h, n_floats);
+  CASYNC_REQUIRE(h, "load_weights_device: null");
+  return h->pw.adopt_device("load_weights_device", h->device, packed_dev, n_floats, layout(h->mode).total, h->dtype == DT_BF16);
 }
 
 // The engine's own streams are PROCESS-WIDE, one set per device, created as they are first needed (lane streams before

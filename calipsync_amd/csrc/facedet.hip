@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "common.h"
+#include "handle.h"
 
 namespace {
 
@@ -388,21 +389,12 @@ constexpr int kNVgg = 12;
 const int kSrcC[6] = {256, 512, 512, 1024, 512, 256};
 enum { ST_FC6 = 5, ST_FC7, ST_CONV6_2, ST_CONV7_2, ST_LOC, ST_CONF, ST_DET, kStages };
 
+// the packed layout with every tensor's offset resolved once: a forward searches nothing
 struct DetLayout {
-  struct E {
-    std::string name;
-    int64_t off, size;
-  };
-  std::vector<E> e;
-  int64_t total = 0;
+  PackedLayout packed;
   int64_t stem_w, stem_b, vgg_w[kNVgg], vgg_b[kNVgg], fc6_w, fc6_b, fc7_w, fc7_b, ex_w[4], ex_b[4], head_w[6], head_b[6];
-  int64_t add(const std::string& n, int64_t size) {
-    const int64_t at = total;
-    e.push_back({n, at, size});
-    total += (size + 63) / 64 * 64;
-    return at;
-  }
   DetLayout() {
+    auto add = [this](const std::string& n, int64_t size) { return packed.add(n, size); };
     stem_w = add("conv1_1.w", 27 * SC), stem_b = add("conv1_1.b", SC);
     for (int i = 0; i < kNVgg; ++i) {
       const DetConv& c = kVgg[i].c;
@@ -424,8 +416,6 @@ const DetLayout& det_layout() {
   static const DetLayout L;
   return L;
 }
-
-int64_t round64(int64_t n) { return (n + 63) / 64 * 64; }
 
 // frames of one pass through the network: the whole batch unless its largest activation (conv1's, H W 64 floats a frame)
 // would reach 2 GiB
@@ -485,26 +475,11 @@ struct DetWs16 {
 struct casync_s3fd {
   int device = 0;
   int precision = 0;             // 0 fp32, 1 bf16 (det_pass16)
-  const float* w = nullptr;
-  float* owned = nullptr;
-  bf16_t* w16 = nullptr;         // precision 1: bf16 image of the packed buffer (owned; the conv / GEMM matrices are read from it)
+  PackedWeights pw;              // precision 1: the conv / GEMM matrices are read from the bf16 image
   hipEvent_t ev_fwd = nullptr;   // forward gate slot
 };
 
 namespace {
-struct DetDeviceGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DetDeviceGuard(int dev) {
-    err = hipGetDevice(&prev);
-    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
-    else if (err == hipSuccess) prev = -1;
-  }
-  ~DetDeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 #define DT(call)                        \
   do {                                  \
     if (int st__ = (call)) return st__; \
@@ -658,7 +633,7 @@ int det_run(casync_s3fd* D, const void* x, bool u8, int batch, int H, int W, flo
             int stage) {
   CASYNC_REQUIRE(D, "s3fd forward: null handle");
   const bool h16 = D->precision == 1;
-  CASYNC_REQUIRE(D->w && (!h16 || D->w16), "s3fd forward: weights not loaded");
+  CASYNC_REQUIRE(D->pw.w && (!h16 || D->pw.w16), "s3fd forward: weights not loaded");
   CASYNC_REQUIRE(batch >= 0 && batch <= 65536, "s3fd forward: batch %d (0..65536)", batch);
   CASYNC_REQUIRE(stage >= 0 && stage < kStages, "s3fd forward: stage %d (0..%d)", stage, kStages - 1);
   DetGeom G;
@@ -676,7 +651,7 @@ int det_run(casync_s3fd* D, const void* x, bool u8, int batch, int H, int W, flo
     casync_set_error("s3fd forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)need);
     return CASYNC_ERR_STATE;
   }
-  DetDeviceGuard guard(D->device);
+  DeviceGuard guard(D->device);
   CASYNC_CHECK_HIP(guard.err);
   std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
   if (int st = casync_gate_enter(D->device, D, &D->ev_fwd, s, &gate_lock)) return st;
@@ -685,31 +660,22 @@ int det_run(casync_s3fd* D, const void* x, bool u8, int batch, int H, int W, flo
   for (int b0 = 0; b0 < batch; b0 += nb) {
     const int n = batch - b0 < nb ? batch - b0 : nb;
     const void* xb = static_cast<const char*>(x) + (size_t)b0 * in_frame;
-    if (h16) DT(det_pass16(D->w, D->w16, xb, u8, n, G, ws16, out + (size_t)b0 * out_frame, stage, s));
-    else DT(det_pass(D->w, xb, u8, n, G, ws, out + (size_t)b0 * out_frame, stage, s));
+    if (h16) DT(det_pass16(D->pw.w, D->pw.w16, xb, u8, n, G, ws16, out + (size_t)b0 * out_frame, stage, s));
+    else DT(det_pass(D->pw.w, xb, u8, n, G, ws, out + (size_t)b0 * out_frame, stage, s));
   }
   return CASYNC_OK;
 }
 #undef DT
-
-// bf16 image of the packed buffer, made once at weight load (not on the forward path)
-int det_refresh_w16(casync_s3fd* h, int64_t n) {
-  if (h->precision != 1) return CASYNC_OK;
-  if (!h->w16) CASYNC_CHECK_HIP(hipMalloc((void**)&h->w16, n * sizeof(bf16_t)));
-  if (int st = launch_f32_to_bf16(h->w, h->w16, (long long)n, 0)) return st;
-  CASYNC_CHECK_HIP(hipDeviceSynchronize());
-  return CASYNC_OK;
-}
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
 extern "C" {
 
-int casync_s3fd_packed_count(void) { return (int)det_layout().e.size(); }
-const char* casync_s3fd_packed_name(int i) { return i >= 0 && i < casync_s3fd_packed_count() ? det_layout().e[i].name.c_str() : nullptr; }
-int64_t casync_s3fd_packed_offset(int i) { return i >= 0 && i < casync_s3fd_packed_count() ? det_layout().e[i].off : -1; }
-int64_t casync_s3fd_packed_size(int i) { return i >= 0 && i < casync_s3fd_packed_count() ? det_layout().e[i].size : -1; }
-int64_t casync_s3fd_packed_total(void) { return det_layout().total; }
+int casync_s3fd_packed_count(void) { return det_layout().packed.count(); }
+const char* casync_s3fd_packed_name(int i) { return det_layout().packed.name(i); }
+int64_t casync_s3fd_packed_offset(int i) { return det_layout().packed.offset(i); }
+int64_t casync_s3fd_packed_size(int i) { return det_layout().packed.size(i); }
+int64_t casync_s3fd_packed_total(void) { return det_layout().packed.total; }
 int64_t casync_s3fd_priors(int h, int w) {
   DetGeom G;
   return det_geometry(h, w, &G) ? G.off[6] : 0;
@@ -739,18 +705,7 @@ int casync_s3fd_create_ex(int device_id, int precision, casync_s3fd_handle* out)
   CASYNC_REQUIRE(out, "s3fd_create: null out");
   *out = nullptr;
   CASYNC_REQUIRE(precision == 0 || precision == 1, "s3fd_create: precision %d (0 fp32, 1 bf16)", precision);
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    casync_set_error("s3fd_create: no HIP device visible");
-    return CASYNC_ERR_NO_DEVICE;
-  }
-  CASYNC_REQUIRE(device_id >= 0 && device_id < n, "s3fd_create: device %d of %d", device_id, n);
-  hipDeviceProp_t prop;
-  CASYNC_CHECK_HIP(hipGetDeviceProperties(&prop, device_id));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-    casync_set_error("s3fd_create: device %d is %s; this library is built for gfx950 only", device_id, prop.gcnArchName);
-    return CASYNC_ERR_NO_DEVICE;
-  }
+  if (int st = casync_require_gfx950("s3fd_create", device_id)) return st;
   casync_s3fd* h = new casync_s3fd();
   h->device = device_id;
   h->precision = precision;
@@ -760,35 +715,21 @@ int casync_s3fd_create_ex(int device_id, int precision, casync_s3fd_handle* out)
 
 void casync_s3fd_destroy(casync_s3fd_handle h) {
   if (!h) return;
-  DetDeviceGuard guard(h->device);
+  DeviceGuard guard(h->device);
   casync_gate_forget(h->device, h, &h->ev_fwd);
-  if (h->owned) (void)hipFree(h->owned);
-  if (h->w16) (void)hipFree(h->w16);
+  h->pw.release();
   delete h;
 }
 
 int casync_s3fd_load_weights_host(casync_s3fd_handle h, const float* packed, int64_t n_floats) {
-  CASYNC_REQUIRE(h && packed, "s3fd_load_weights: null");
-  CASYNC_REQUIRE(n_floats == det_layout().total, "s3fd_load_weights: %lld floats, layout needs %lld", (long long)n_floats,
-                 (long long)det_layout().total);
-  DetDeviceGuard guard(h->device);
-  CASYNC_CHECK_HIP(guard.err);
-  if (!h->owned) CASYNC_CHECK_HIP(hipMalloc((void**)&h->owned, n_floats * sizeof(float)));
-  CASYNC_CHECK_HIP(hipMemcpy(h->owned, packed, n_floats * sizeof(float), hipMemcpyHostToDevice));
-  h->w = h->owned;
-  return det_refresh_w16(h, n_floats);
+  CASYNC_REQUIRE(h, "s3fd_load_weights: null");
+  return h->pw.load_host("s3fd_load_weights", h->device, packed, n_floats, det_layout().packed.total, h->precision == 1);
 }
 
 int casync_s3fd_load_weights_device(casync_s3fd_handle h, const float* packed_dev, int64_t n_floats) {
-  CASYNC_REQUIRE(h && packed_dev, "s3fd_load_weights_device: null");
-  CASYNC_REQUIRE(n_floats == det_layout().total, "s3fd_load_weights_device: %lld floats, layout needs %lld", (long long)n_floats,
-                 (long long)det_layout().total);
-  CASYNC_REQUIRE(((uintptr_t)packed_dev % 256) == 0, "s3fd_load_weights_device: buffer must be 256-B aligned");
-  h->w = packed_dev;
-  if (h->precision != 1) return CASYNC_OK;
-  DetDeviceGuard guard(h->device);
-  CASYNC_CHECK_HIP(guard.err);
-  return det_refresh_w16(h, n_floats);
+  CASYNC_REQUIRE(h, "s3fd_load_weights_device: null");
+  return h->pw.adopt_device("s3fd_load_weights_device", h->device, packed_dev, n_floats, det_layout().packed.total,
+                            h->precision == 1);
 }
 
 int casync_s3fd_forward(casync_s3fd_handle h, const float* x_dev, int batch, int H, int W, float* det_dev, void* workspace_dev,

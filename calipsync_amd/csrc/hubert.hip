@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.h"
+#include "handle.h"
 
 namespace {
 
@@ -301,28 +302,14 @@ int launch_attention(const float* qkv, float* out, int batch, int T, hipStream_t
 }
 
 // ---- packed layout ---------------------------------------------------------------------------------------------------
-struct HbEntry { std::string name; int64_t off, size; };
-struct HbLayout {
-  std::vector<HbEntry> e;
-  int64_t total = 0;
-  void add(const std::string& n, int64_t sz) {
-    e.push_back({n, total, sz});
-    total += (sz + 63) / 64 * 64;   // 256-B aligned tensors
-  }
-  int64_t off(const std::string& n) const {
-    for (const HbEntry& x : e)
-      if (x.name == n) return x.off;
-    return -1;
-  }
-};
 constexpr int kMaxLayers = 48;
 
-const HbLayout* hb_layout(int layers) {
-  static HbLayout cache[kMaxLayers + 1];
+const PackedLayout* hb_layout(int layers) {   // null outside 1..kMaxLayers
+  static PackedLayout cache[kMaxLayers + 1];
   static std::once_flag once[kMaxLayers + 1];
   if (layers < 1 || layers > kMaxLayers) return nullptr;
   std::call_once(once[layers], [layers] {
-    HbLayout& L = cache[layers];
+    PackedLayout& L = cache[layers];
     for (int i = 0; i < 7; ++i) {
       const std::string p = "fe.conv" + std::to_string(i);
       L.add(p + ".w", (int64_t)kConvC * (i ? kConvC : 1) * kConvK[i]);   // [cout][tap][cin]
@@ -366,8 +353,6 @@ struct HbGeom {
   }
   int64_t tokens() const { return t[7]; }
 };
-
-int64_t round64(int64_t n) { return (n + 63) / 64 * 64; }
 
 struct HbWs {
   float *a, *b, *h, *x, *big;
@@ -413,29 +398,14 @@ struct casync_hubert {
   int device = 0;
   int layers = 0;
   int dtype = DT_F32;         // DT_BF16: the bf16 precision (hb_run16)
-  const float* w = nullptr;   // packed weights (owned or adopted)
-  float* owned = nullptr;
-  bf16_t* w16 = nullptr;      // DT_BF16: bf16 image of the packed buffer (owned; the GEMM weight matrices are read from it)
-  const bf16_t* W16(const std::string& n) const { return w16 + hb_layout(layers)->off(n); }
+  PackedWeights pw;           // DT_BF16: the GEMM weight matrices are read from the bf16 image
+  const bf16_t* W16(const std::string& n) const { return pw.w16 + hb_layout(layers)->off(n); }
   hipEvent_t ev_fwd = nullptr;   // FwdGate slot
-  const float* W(const char* n) const { return w + hb_layout(layers)->off(n); }
-  const float* W(const std::string& n) const { return w + hb_layout(layers)->off(n); }
+  const float* W(const char* n) const { return pw.w + hb_layout(layers)->off(n); }
+  const float* W(const std::string& n) const { return pw.w + hb_layout(layers)->off(n); }
 };
 
 namespace {
-struct HbDeviceGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit HbDeviceGuard(int dev) {
-    err = hipGetDevice(&prev);
-    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
-    else if (err == hipSuccess) prev = -1;
-  }
-  ~HbDeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 int gemm(const float* a, int lda, const float* w, const float* bias, float* c, int ldc, int m, int n, int k, int act,
          const float* post, hipStream_t s) {
   GemmEpilogue e;
@@ -451,7 +421,7 @@ int gemm(const float* a, int lda, const float* w, const float* bias, float* c, i
 int hb_run(casync_hubert* H, const float* wave, int batch, int64_t S, float* out, void* ws_dev, int64_t ws_bytes, hipStream_t s,
            int stage, int n_layers) {
   CASYNC_REQUIRE(H && wave && out && ws_dev, "hubert forward: null pointer");
-  CASYNC_REQUIRE(H->w, "hubert forward: weights not loaded");
+  CASYNC_REQUIRE(H->pw.w, "hubert forward: weights not loaded");
   CASYNC_REQUIRE(batch > 0 && batch <= 65535, "hubert forward: batch %d", batch);
   CASYNC_REQUIRE(S < (1ll << 31), "hubert forward: %lld samples", (long long)S);
   const HbGeom G(S);
@@ -465,7 +435,7 @@ int hb_run(casync_hubert* H, const float* wave, int batch, int64_t S, float* out
     return CASYNC_ERR_STATE;
   }
   const int T = (int)G.tokens(), M = batch * T;
-  HbDeviceGuard guard(H->device);
+  DeviceGuard guard(H->device);
   CASYNC_CHECK_HIP(guard.err);
   std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
   if (int st = casync_gate_enter(H->device, H, &H->ev_fwd, s, &gate_lock)) return st;
@@ -524,7 +494,7 @@ int hb_run(casync_hubert* H, const float* wave, int batch, int64_t S, float* out
 int hb_run16(casync_hubert* H, const float* wave, int batch, int64_t S, float* out, void* ws_dev, int64_t ws_bytes, hipStream_t s,
              int stage, int n_layers) {
   CASYNC_REQUIRE(H && wave && out && ws_dev, "hubert forward: null pointer");
-  CASYNC_REQUIRE(H->w && H->w16, "hubert forward: weights not loaded");
+  CASYNC_REQUIRE(H->pw.w && H->pw.w16, "hubert forward: weights not loaded");
   CASYNC_REQUIRE(batch > 0 && batch <= 65535, "hubert forward: batch %d", batch);
   CASYNC_REQUIRE(S < (1ll << 31), "hubert forward: %lld samples", (long long)S);
   const HbGeom G(S);
@@ -538,7 +508,7 @@ int hb_run16(casync_hubert* H, const float* wave, int batch, int64_t S, float* o
     return CASYNC_ERR_STATE;
   }
   const int T = (int)G.tokens(), M = batch * T;
-  HbDeviceGuard guard(H->device);
+  DeviceGuard guard(H->device);
   CASYNC_CHECK_HIP(guard.err);
   std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
   if (int st = casync_gate_enter(H->device, H, &H->ev_fwd, s, &gate_lock)) return st;
@@ -597,40 +567,16 @@ int hb_run16(casync_hubert* H, const float* wave, int batch, int64_t S, float* o
 #undef HB
   return CASYNC_OK;
 }
-
-// bf16 image of the packed buffer, made once at weight load (not on the forward path)
-int hb_refresh_w16(casync_hubert* h, int64_t n) {
-  if (h->dtype != DT_BF16) return CASYNC_OK;
-  if (!h->w16) CASYNC_CHECK_HIP(hipMalloc((void**)&h->w16, n * sizeof(bf16_t)));
-  if (int st = launch_f32_to_bf16(h->w, h->w16, (long long)n, 0)) return st;
-  CASYNC_CHECK_HIP(hipDeviceSynchronize());
-  return CASYNC_OK;
-}
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
 extern "C" {
 
-int casync_hubert_packed_count(int layers) {
-  const HbLayout* L = hb_layout(layers);
-  return L ? (int)L->e.size() : 0;
-}
-const char* casync_hubert_packed_name(int layers, int i) {
-  const HbLayout* L = hb_layout(layers);
-  return L && i >= 0 && i < (int)L->e.size() ? L->e[i].name.c_str() : nullptr;
-}
-int64_t casync_hubert_packed_offset(int layers, int i) {
-  const HbLayout* L = hb_layout(layers);
-  return L && i >= 0 && i < (int)L->e.size() ? L->e[i].off : -1;
-}
-int64_t casync_hubert_packed_size(int layers, int i) {
-  const HbLayout* L = hb_layout(layers);
-  return L && i >= 0 && i < (int)L->e.size() ? L->e[i].size : -1;
-}
-int64_t casync_hubert_packed_total(int layers) {
-  const HbLayout* L = hb_layout(layers);
-  return L ? L->total : 0;
-}
+int casync_hubert_packed_count(int layers) { return hb_layout(layers) ? hb_layout(layers)->count() : 0; }
+const char* casync_hubert_packed_name(int layers, int i) { return hb_layout(layers) ? hb_layout(layers)->name(i) : nullptr; }
+int64_t casync_hubert_packed_offset(int layers, int i) { return hb_layout(layers) ? hb_layout(layers)->offset(i) : -1; }
+int64_t casync_hubert_packed_size(int layers, int i) { return hb_layout(layers) ? hb_layout(layers)->size(i) : -1; }
+int64_t casync_hubert_packed_total(int layers) { return hb_layout(layers) ? hb_layout(layers)->total : 0; }
 int64_t casync_hubert_tokens(int64_t samples) { return samples > 0 ? HbGeom(samples).tokens() : 0; }
 int64_t casync_hubert_workspace_bytes(int batch, int64_t samples) {
   if (batch <= 0 || samples <= 0) return 0;
@@ -654,18 +600,7 @@ int casync_hubert_create_ex(int device_id, int layers, int dtype, casync_hubert_
   *out = nullptr;
   CASYNC_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "hubert_create: dtype %d (0 fp32, 1 bf16)", dtype);
   CASYNC_REQUIRE(layers >= 1 && layers <= kMaxLayers, "hubert_create: %d layers (1..%d)", layers, kMaxLayers);
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    casync_set_error("hubert_create: no HIP device visible");
-    return CASYNC_ERR_NO_DEVICE;
-  }
-  CASYNC_REQUIRE(device_id >= 0 && device_id < n, "hubert_create: device %d of %d", device_id, n);
-  hipDeviceProp_t prop;
-  CASYNC_CHECK_HIP(hipGetDeviceProperties(&prop, device_id));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-    casync_set_error("hubert_create: device %d is %s; this library is built for gfx950 only", device_id, prop.gcnArchName);
-    return CASYNC_ERR_NO_DEVICE;
-  }
+  if (int st = casync_require_gfx950("hubert_create", device_id)) return st;
   casync_hubert* h = new casync_hubert();
   h->device = device_id;
   h->layers = layers;
@@ -676,35 +611,21 @@ int casync_hubert_create_ex(int device_id, int layers, int dtype, casync_hubert_
 
 void casync_hubert_destroy(casync_hubert_handle h) {
   if (!h) return;
-  HbDeviceGuard guard(h->device);
+  DeviceGuard guard(h->device);
   casync_gate_forget(h->device, h, &h->ev_fwd);
-  if (h->owned) (void)hipFree(h->owned);
-  if (h->w16) (void)hipFree(h->w16);
+  h->pw.release();
   delete h;
 }
 
 int casync_hubert_load_weights_host(casync_hubert_handle h, const float* packed, int64_t n_floats) {
-  CASYNC_REQUIRE(h && packed, "hubert_load_weights: null");
-  const int64_t total = hb_layout(h->layers)->total;
-  CASYNC_REQUIRE(n_floats == total, "hubert_load_weights: %lld floats, layout needs %lld", (long long)n_floats, (long long)total);
-  HbDeviceGuard guard(h->device);
-  CASYNC_CHECK_HIP(guard.err);
-  if (!h->owned) CASYNC_CHECK_HIP(hipMalloc((void**)&h->owned, n_floats * sizeof(float)));
-  CASYNC_CHECK_HIP(hipMemcpy(h->owned, packed, n_floats * sizeof(float), hipMemcpyHostToDevice));
-  h->w = h->owned;
-  return hb_refresh_w16(h, n_floats);
+  CASYNC_REQUIRE(h, "hubert_load_weights: null");
+  return h->pw.load_host("hubert_load_weights", h->device, packed, n_floats, hb_layout(h->layers)->total, h->dtype == DT_BF16);
 }
 
 int casync_hubert_load_weights_device(casync_hubert_handle h, const float* packed_dev, int64_t n_floats) {
-  CASYNC_REQUIRE(h && packed_dev, "hubert_load_weights_device: null");
-  const int64_t total = hb_layout(h->layers)->total;
-  CASYNC_REQUIRE(n_floats == total, "hubert_load_weights_device: %lld floats, layout needs %lld", (long long)n_floats,
-                 (long long)total);
-  CASYNC_REQUIRE(((uintptr_t)packed_dev % 256) == 0, "hubert_load_weights_device: buffer must be 256-B aligned");
-  h->w = packed_dev;
-  HbDeviceGuard guard(h->device);
-  CASYNC_CHECK_HIP(guard.err);
-  return hb_refresh_w16(h, n_floats);
+  CASYNC_REQUIRE(h, "hubert_load_weights_device: null");
+  return h->pw.adopt_device("hubert_load_weights_device", h->device, packed_dev, n_floats, hb_layout(h->layers)->total,
+                            h->dtype == DT_BF16);
 }
 
 int casync_hubert_forward(casync_hubert_handle h, const float* wave_dev, int batch, int64_t samples, float* out_dev,

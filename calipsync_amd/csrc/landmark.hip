@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "handle.h"
 
 namespace {
 
@@ -390,45 +391,29 @@ constexpr int kNB = 11;
 constexpr int kIn = 192;
 constexpr int kStages = 16;   // conv1, conv2, conv3_1..3, conv4_1..3, conv5_1..4, conv6, conv7, conv8, conv_out
 
-struct LmkLayout {
-  struct E {
-    std::string name;
-    int64_t off, size;
-  };
-  std::vector<E> e;
-  int64_t total = 0;
-  void add(const std::string& n, int64_t size) {
-    e.push_back({n, total, size});
-    total += (size + 63) / 64 * 64;
+PackedLayout make_lmk_layout() {
+  PackedLayout L;
+  L.add("conv1.w", 27 * SC), L.add("conv1.b", SC), L.add("conv2.w", 9 * SC), L.add("conv2.b", SC);
+  for (const Bneck& k : kBnecks) {
+    const std::string p = k.name;
+    auto ghost = [&](const std::string& g, int cin, int cout) {
+      const int np = ceil_to(cout / 2, 16);
+      L.add(p + g + ".pw.w", (int64_t)ceil_to(cin, 16) * np), L.add(p + g + ".pw.b", np);
+      L.add(p + g + ".dw.w", 9 * np), L.add(p + g + ".dw.b", np);
+    };
+    ghost(".g1", k.cin, k.hid);
+    if (k.stride == 2) L.add(p + ".dw.w", 9 * k.hid), L.add(p + ".dw.b", k.hid);
+    ghost(".g2", k.hid, k.cout);
   }
-  int64_t off(const std::string& n) const {
-    for (const E& x : e)
-      if (x.name == n) return x.off;
-    return -1;
-  }
-  LmkLayout() {
-    add("conv1.w", 27 * SC), add("conv1.b", SC), add("conv2.w", 9 * SC), add("conv2.b", SC);
-    for (const Bneck& k : kBnecks) {
-      const std::string p = k.name;
-      auto ghost = [&](const std::string& g, int cin, int cout) {
-        const int np = ceil_to(cout / 2, 16);
-        add(p + g + ".pw.w", (int64_t)ceil_to(cin, 16) * np), add(p + g + ".pw.b", np);
-        add(p + g + ".dw.w", 9 * np), add(p + g + ".dw.b", np);
-      };
-      ghost(".g1", k.cin, k.hid);
-      if (k.stride == 2) add(p + ".dw.w", 9 * k.hid), add(p + ".dw.b", k.hid);
-      ghost(".g2", k.hid, k.cout);
-    }
-    add("conv7.w", 9 * C6 * C7), add("conv7.b", C7), add("conv8.w", (int64_t)HP * C7 * C8);
-    add("conv_out.w", NF * NOUT), add("conv_out.b", NOUT);
-  }
-};
-const LmkLayout& lmk_layout() {
-  static const LmkLayout L;
+  L.add("conv7.w", 9 * C6 * C7), L.add("conv7.b", C7), L.add("conv8.w", (int64_t)HP * C7 * C8);
+  L.add("conv_out.w", NF * NOUT), L.add("conv_out.b", NOUT);
+  return L;
+}
+const PackedLayout& lmk_layout() {
+  static const PackedLayout L = make_lmk_layout();
   return L;
 }
 
-int64_t round64(int64_t n) { return (n + 63) / 64 * 64; }
 constexpr int64_t kActFloats = 96 * 96 * 48;   // the largest activation of a frame: conv3_1's first ghost module
 struct LmkWs {
   float *a, *b, *sum[4];
@@ -469,7 +454,7 @@ struct LmkOffsets {
   std::string missing;   // the first name the layout does not hold; empty when all were found
 
   LmkOffsets() {
-    const LmkLayout& L = lmk_layout();
+    const PackedLayout& L = lmk_layout();
     auto get = [&](const std::string& n) {
       const int64_t o = L.off(n);
       if (o < 0 && missing.empty()) missing = n;
@@ -489,26 +474,12 @@ struct LmkOffsets {
 
 struct casync_pfld {
   int device = 0;
-  const float* w = nullptr;
-  float* owned = nullptr;
+  PackedWeights pw;
   hipEvent_t ev_fwd = nullptr;   // forward gate slot
   LmkOffsets at;
 };
 
 namespace {
-struct LmkDeviceGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit LmkDeviceGuard(int dev) {
-    err = hipGetDevice(&prev);
-    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
-    else if (err == hipSuccess) prev = -1;
-  }
-  ~LmkDeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 int64_t stage_floats(int stage) {   // per frame, NHWC
   static const int64_t n[kStages] = {96 * 96 * 32, 96 * 96 * 32, 48 * 48 * 40, 48 * 48 * 40, 48 * 48 * 40, 24 * 24 * 48,
                                      24 * 24 * 48, 24 * 24 * 48, 12 * 12 * 72, 12 * 12 * 72, 12 * 12 * 72, 12 * 12 * 72,
@@ -519,7 +490,7 @@ int64_t stage_floats(int stage) {   // per frame, NHWC
 // stage kStages - 1 = the landmarks [B,220]; a lower stage stops there and writes that NHWC intermediate to `out`
 int lmk_run(casync_pfld* P, const void* x, bool u8, int batch, float* out, void* ws_dev, int64_t ws_bytes, hipStream_t s, int stage) {
   CASYNC_REQUIRE(P && x && out && ws_dev, "pfld forward: null pointer");
-  CASYNC_REQUIRE(P->w, "pfld forward: weights not loaded");
+  CASYNC_REQUIRE(P->pw.w, "pfld forward: weights not loaded");
   CASYNC_REQUIRE(batch > 0 && batch <= 4096, "pfld forward: batch %d (1..4096)", batch);
   CASYNC_REQUIRE(stage >= 0 && stage < kStages, "pfld forward: stage %d (0..%d)", stage, kStages - 1);
   CASYNC_REQUIRE((uintptr_t)x % (u8 ? 1 : 4) == 0 && (uintptr_t)out % 4 == 0 && (uintptr_t)ws_dev % 256 == 0, "pfld forward: alignment");
@@ -528,7 +499,7 @@ int lmk_run(casync_pfld* P, const void* x, bool u8, int batch, float* out, void*
     casync_set_error("pfld forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)ws.floats * 4);
     return CASYNC_ERR_STATE;
   }
-  LmkDeviceGuard guard(P->device);
+  DeviceGuard guard(P->device);
   CASYNC_CHECK_HIP(guard.err);
   std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
   if (int st = casync_gate_enter(P->device, P, &P->ev_fwd, s, &gate_lock)) return st;
@@ -542,7 +513,7 @@ int lmk_run(casync_pfld* P, const void* x, bool u8, int batch, float* out, void*
   };
   float *cur = ws.a, *nxt = ws.b;
   const LmkOffsets& at = P->at;
-  const float* const w = P->w;
+  const float* const w = P->pw.w;
   LM(launch_stem(x, u8, w + at.conv1_w, w + at.conv1_b, w + at.conv2_w, w + at.conv2_b, cur, ws.sum[0], stage == 0 ? out : nullptr,
                  batch, kIn, kIn, s));
   if (stage == 0) return CASYNC_OK;
@@ -580,28 +551,17 @@ int lmk_run(casync_pfld* P, const void* x, bool u8, int batch, float* out, void*
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
 extern "C" {
 
-int casync_pfld_packed_count(void) { return (int)lmk_layout().e.size(); }
-const char* casync_pfld_packed_name(int i) { return i >= 0 && i < casync_pfld_packed_count() ? lmk_layout().e[i].name.c_str() : nullptr; }
-int64_t casync_pfld_packed_offset(int i) { return i >= 0 && i < casync_pfld_packed_count() ? lmk_layout().e[i].off : -1; }
-int64_t casync_pfld_packed_size(int i) { return i >= 0 && i < casync_pfld_packed_count() ? lmk_layout().e[i].size : -1; }
+int casync_pfld_packed_count(void) { return lmk_layout().count(); }
+const char* casync_pfld_packed_name(int i) { return lmk_layout().name(i); }
+int64_t casync_pfld_packed_offset(int i) { return lmk_layout().offset(i); }
+int64_t casync_pfld_packed_size(int i) { return lmk_layout().size(i); }
 int64_t casync_pfld_packed_total(void) { return lmk_layout().total; }
 int64_t casync_pfld_workspace_bytes(int batch) { return batch > 0 && batch <= 4096 ? LmkWs(nullptr, batch).floats * 4 : 0; }
 
 int casync_pfld_create(int device_id, casync_pfld_handle* out) {
   CASYNC_REQUIRE(out, "pfld_create: null out");
   *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    casync_set_error("pfld_create: no HIP device visible");
-    return CASYNC_ERR_NO_DEVICE;
-  }
-  CASYNC_REQUIRE(device_id >= 0 && device_id < n, "pfld_create: device %d of %d", device_id, n);
-  hipDeviceProp_t prop;
-  CASYNC_CHECK_HIP(hipGetDeviceProperties(&prop, device_id));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-    casync_set_error("pfld_create: device %d is %s; this library is built for gfx950 only", device_id, prop.gcnArchName);
-    return CASYNC_ERR_NO_DEVICE;
-  }
+  if (int st = casync_require_gfx950("pfld_create", device_id)) return st;
   casync_pfld* h = new casync_pfld();
   if (!h->at.missing.empty()) {
     casync_set_error("pfld_create: the packed layout has no tensor %s", h->at.missing.c_str());
@@ -615,31 +575,20 @@ int casync_pfld_create(int device_id, casync_pfld_handle* out) {
 
 void casync_pfld_destroy(casync_pfld_handle h) {
   if (!h) return;
-  LmkDeviceGuard guard(h->device);
+  DeviceGuard guard(h->device);
   casync_gate_forget(h->device, h, &h->ev_fwd);
-  if (h->owned) (void)hipFree(h->owned);
+  h->pw.release();
   delete h;
 }
 
 int casync_pfld_load_weights_host(casync_pfld_handle h, const float* packed, int64_t n_floats) {
-  CASYNC_REQUIRE(h && packed, "pfld_load_weights: null");
-  CASYNC_REQUIRE(n_floats == lmk_layout().total, "pfld_load_weights: %lld floats, layout needs %lld", (long long)n_floats,
-                 (long long)lmk_layout().total);
-  LmkDeviceGuard guard(h->device);
-  CASYNC_CHECK_HIP(guard.err);
-  if (!h->owned) CASYNC_CHECK_HIP(hipMalloc((void**)&h->owned, n_floats * sizeof(float)));
-  CASYNC_CHECK_HIP(hipMemcpy(h->owned, packed, n_floats * sizeof(float), hipMemcpyHostToDevice));
-  h->w = h->owned;
-  return CASYNC_OK;
+  CASYNC_REQUIRE(h, "pfld_load_weights: null");
+  return h->pw.load_host("pfld_load_weights", h->device, packed, n_floats, lmk_layout().total, false);
 }
 
 int casync_pfld_load_weights_device(casync_pfld_handle h, const float* packed_dev, int64_t n_floats) {
-  CASYNC_REQUIRE(h && packed_dev, "pfld_load_weights_device: null");
-  CASYNC_REQUIRE(n_floats == lmk_layout().total, "pfld_load_weights_device: %lld floats, layout needs %lld", (long long)n_floats,
-                 (long long)lmk_layout().total);
-  CASYNC_REQUIRE(((uintptr_t)packed_dev % 256) == 0, "pfld_load_weights_device: buffer must be 256-B aligned");
-  h->w = packed_dev;
-  return CASYNC_OK;
+  CASYNC_REQUIRE(h, "pfld_load_weights_device: null");
+  return h->pw.adopt_device("pfld_load_weights_device", h->device, packed_dev, n_floats, lmk_layout().total, false);
 }
 
 int casync_pfld_forward(casync_pfld_handle h, const float* x_dev, int batch, float* out_dev, void* workspace_dev,

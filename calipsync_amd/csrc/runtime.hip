@@ -1,5 +1,6 @@
 // Process-wide runtime state of the engine library: the option table (environment read once), the
-// per-thread "options of the call in progress", and the per-(kernel, device) launch attributes.
+// per-thread "options of the call in progress", the per-(kernel, device) launch attributes, and the handles' shared
+// create check and weight ownership (handle.h).
 #include <stdlib.h>
 #include <string.h>
 
@@ -7,6 +8,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "handle.h"
 
 namespace {
 
@@ -99,4 +101,64 @@ int casync_ensure_dyn_lds(unsigned long long* once_mask, const void* fn, int byt
   CASYNC_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   if (bit) mask->fetch_or(bit, std::memory_order_release);
   return CASYNC_OK;
+}
+
+// ---- handle.h --------------------------------------------------------------------------------------------------------
+int casync_require_gfx950(const char* what, int device_id) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+    casync_set_error("%s: no HIP device visible", what);
+    return CASYNC_ERR_NO_DEVICE;
+  }
+  CASYNC_REQUIRE(device_id >= 0 && device_id < n, "%s: device %d of %d", what, device_id, n);
+  hipDeviceProp_t prop;
+  CASYNC_CHECK_HIP(hipGetDeviceProperties(&prop, device_id));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+    casync_set_error("%s: device %d is %s; this library is built for gfx950 only", what, device_id, prop.gcnArchName);
+    return CASYNC_ERR_NO_DEVICE;
+  }
+  return CASYNC_OK;
+}
+
+// bf16 image of the packed buffer, made at weight load (not on the forward path); the packed total is a multiple of 64
+static int refresh_w16(PackedWeights& p, int device, int64_t n) {
+  DeviceGuard guard(device);
+  CASYNC_CHECK_HIP(guard.err);
+  if (!p.w16) CASYNC_CHECK_HIP(hipMalloc((void**)&p.w16, n * sizeof(bf16_t)));
+  if (int st = launch_f32_to_bf16(p.w, p.w16, (long long)n, 0)) return st;
+  CASYNC_CHECK_HIP(hipDeviceSynchronize());
+  return CASYNC_OK;
+}
+
+int PackedWeights::load_host(const char* what, int device, const float* packed, int64_t n, int64_t total, bool want_bf16) {
+  CASYNC_REQUIRE(packed, "%s: null", what);
+  CASYNC_REQUIRE(n == total, "%s: %lld floats, layout needs %lld", what, (long long)n, (long long)total);
+  {
+    DeviceGuard guard(device);
+    CASYNC_CHECK_HIP(guard.err);
+    if (!owned) CASYNC_CHECK_HIP(hipMalloc((void**)&owned, n * sizeof(float)));
+    CASYNC_CHECK_HIP(hipMemcpy(owned, packed, n * sizeof(float), hipMemcpyHostToDevice));
+  }
+  w = owned;
+  return want_bf16 ? refresh_w16(*this, device, n) : CASYNC_OK;
+}
+
+int PackedWeights::adopt_device(const char* what, int device, const float* packed_dev, int64_t n, int64_t total, bool want_bf16) {
+  CASYNC_REQUIRE(packed_dev, "%s: null", what);
+  CASYNC_REQUIRE(n == total, "%s: %lld floats, layout needs %lld", what, (long long)n, (long long)total);
+  CASYNC_REQUIRE(((uintptr_t)packed_dev % 256) == 0, "%s: buffer must be 256-B aligned", what);
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, packed_dev) == hipSuccess && attr.type == hipMemoryTypeDevice)
+    CASYNC_REQUIRE(attr.device == device, "%s: buffer lives on device %d, the engine on %d", what, attr.device, device);
+  else
+    (void)hipGetLastError();
+  w = packed_dev;
+  return want_bf16 ? refresh_w16(*this, device, n) : CASYNC_OK;
+}
+
+void PackedWeights::release() {
+  if (owned) (void)hipFree(owned);
+  if (w16) (void)hipFree(w16);
+  w = owned = nullptr;
+  w16 = nullptr;
 }

@@ -27,6 +27,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .engine_base import _PackedEngine
+
 # nn.Conv2d(cin, cout, k) of S3FDNet.vgg by ModuleList index (nets.py:34-75), with the engine's name
 VGG = ((0, "conv1_1", 3, 64, 3), (2, "conv1_2", 64, 64, 3), (5, "conv2_1", 64, 128, 3), (7, "conv2_2", 128, 128, 3),
        (10, "conv3_1", 128, 256, 3), (12, "conv3_2", 256, 256, 3), (14, "conv3_3", 256, 256, 3),
@@ -109,24 +111,13 @@ def packed_tensors(sd) -> Dict[str, np.ndarray]:
 def pack(sd) -> np.ndarray:
     """The flat float32 buffer casync_s3fd_load_weights_* takes."""
     from . import _lib
-    named = packed_tensors(sd)
-    items, total = _lib.s3fd_layout()
-    buf = np.zeros(total, dtype=np.float32)
-    for name, off, size in items:
-        a = named.pop(name).reshape(-1)
-        if a.size != size:
-            raise ValueError(f"packed tensor {name}: {a.size} floats, the engine expects {size}")
-        buf[off:off + size] = a
-    if named:
-        raise ValueError(f"tensors the engine layout does not name: {sorted(named)}")
-    return buf
+    return _lib.pack_named(packed_tensors(sd), _lib.s3fd_layout())
 
 
 def unpack(buf: np.ndarray) -> Dict[str, np.ndarray]:
     """Inverse of pack (flat shapes)."""
     from . import _lib
-    items, _ = _lib.s3fd_layout()
-    return {name: buf[off:off + size] for name, off, size in items}
+    return _lib.unpack_named(buf, _lib.s3fd_layout())
 
 
 def map_sizes(h: int, w: int) -> Optional[List[Tuple[int, int]]]:
@@ -152,34 +143,26 @@ def n_priors(h: int, w: int) -> int:
     return sum(a * b for a, b in m) if m else 0
 
 
-class S3FDEngine:
+class S3FDEngine(_PackedEngine):
     """S3FDNet().eval() up to Detect.forward, on the HIP engine: forward(x [B,3,H,W] float, mean subtracted) or
     forward_u8(frames [B,H,W,3] uint8) -> the dense det [B,P,5] on the device.  There is no CPU path.  precision "bf16"
     runs the network on bf16 activations; inputs, outputs and taps stay float32."""
 
+    _destroy = "casync_s3fd_destroy"
+
     def __init__(self, sd, device: str = "cuda:0", precision: str = "fp32"):
-        import ctypes as C
-        from . import _lib
         if precision not in PRECISIONS:
             raise ValueError(f"S3FD engine: precision {precision!r}, expected one of {sorted(PRECISIONS)}")
         self.precision = precision
         buf = pack(sd)                 # (checks the checkpoint before any device call)
-        self._lib = _lib.load()
-        self.device = torch.device(device)
-        h = C.c_void_p()
-        _lib.check(self._lib.casync_s3fd_create_ex(self.device.index or 0, PRECISIONS[precision], C.byref(h)), "casync_s3fd_create_ex")
-        self._h = h
-        _lib.check(self._lib.casync_s3fd_load_weights_host(self._h, buf.ctypes.data, buf.size), "casync_s3fd_load_weights_host")
-        self._ws: Optional[torch.Tensor] = None
+        self._open(device, "casync_s3fd_create_ex", (PRECISIONS[precision],), "casync_s3fd_load_weights_host", buf)
 
     def workspace_bytes(self, batch: int, h: int, w: int) -> int:
         return self._lib.casync_s3fd_workspace_bytes_ex(PRECISIONS[self.precision], batch, h, w)
 
     def _workspace(self, batch: int, h: int, w: int) -> torch.Tensor:
         need = max(self.workspace_bytes(batch, h, w), 256)     # (0: the forward itself says why it refuses the shape)
-        if self._ws is None or self._ws.numel() * 4 < need:
-            self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
-        return self._ws
+        return self._grow_workspace(need)
 
     def stage_shape(self, stage: int, batch: int, h: int, w: int) -> Tuple[int, ...]:
         m = map_sizes(h, w) or [(0, 0)] * 6
@@ -221,17 +204,6 @@ class S3FDEngine:
         return self.forward_u8(x, stage) if u8 else self.forward(x, stage)
 
     __call__ = forward
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.casync_s3fd_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- post-processing on the host: the reference's arithmetic in its own dtypes ------------------------------------------

@@ -17,10 +17,12 @@ import shutil
 import subprocess
 import tempfile
 import wave as _wave
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Tuple
 
 import numpy as np
 import torch
+
+from .engine_base import _PackedEngine
 
 # the configuration the engine computes (transformers HubertConfig of hubert-large-ls960-ft); num_hidden_layers is free
 REQUIRED_CONFIG = {
@@ -153,24 +155,13 @@ def packed_tensors(sd: Dict[str, torch.Tensor], layers: int) -> Dict[str, np.nda
 def pack(sd: Dict[str, torch.Tensor], layers: int) -> np.ndarray:
     """The flat float32 buffer casync_hubert_load_weights_* takes."""
     from . import _lib
-    named = packed_tensors(sd, layers)
-    items, total = _lib.hubert_layout(layers)
-    buf = np.zeros(total, dtype=np.float32)
-    for name, off, size in items:
-        a = named.pop(name).reshape(-1)
-        if a.size != size:
-            raise ValueError(f"packed tensor {name}: {a.size} floats, the engine expects {size}")
-        buf[off:off + size] = a
-    if named:
-        raise ValueError(f"tensors the engine layout does not name: {sorted(named)}")
-    return buf
+    return _lib.pack_named(packed_tensors(sd, layers), _lib.hubert_layout(layers))
 
 
 def unpack(buf: np.ndarray, layers: int) -> Dict[str, np.ndarray]:
     """Inverse of pack (flat shapes)."""
     from . import _lib
-    items, _ = _lib.hubert_layout(layers)
-    return {name: buf[off:off + size] for name, off, size in items}
+    return _lib.unpack_named(buf, _lib.hubert_layout(layers))
 
 
 def tokens(samples: int) -> int:
@@ -191,33 +182,25 @@ def check_precision(precision: str) -> int:
     return PRECISIONS[precision]
 
 
-class HubertEngine:
+class HubertEngine(_PackedEngine):
     """HubertModel(...).last_hidden_state on the HIP engine: forward(wave [B,S] on the device) -> [B,T,1024], fp32 in and
     out.  precision "bf16" runs the GEMMs, the attention and the activations between them in bf16 (fp32 sums, fp32 residual
     stream: DESIGN section 8b); "fp32" is the default."""
 
+    _destroy = "casync_hubert_destroy"
+
     def __init__(self, sd: Dict[str, torch.Tensor], layers: int, device: str = "cuda:0", precision: str = "fp32"):
-        import ctypes as C
-        from . import _lib
         dtype = check_precision(precision)
-        self._lib = _lib.load()
-        self.device = torch.device(device)
         self.layers = layers
         self.precision = precision
-        h = C.c_void_p()
-        _lib.check(self._lib.casync_hubert_create_ex(self.device.index or 0, layers, dtype, C.byref(h)), "casync_hubert_create_ex")
-        self._h = h
-        buf = pack(sd, layers)
-        _lib.check(self._lib.casync_hubert_load_weights_host(self._h, buf.ctypes.data, buf.size), "casync_hubert_load_weights_host")
-        self._ws: Optional[torch.Tensor] = None
+        self._create(device, "casync_hubert_create_ex", layers, dtype)
+        self._load_host("casync_hubert_load_weights_host", pack(sd, layers))
 
     def _workspace(self, batch: int, samples: int) -> torch.Tensor:
         need = self._lib.casync_hubert_workspace_bytes_h(self._h, batch, samples)
         if need <= 0:
             raise ValueError(f"HuBERT engine: {samples} samples give no token (at least {KERNEL} are needed)")
-        if self._ws is None or self._ws.numel() * 4 < need:
-            self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
-        return self._ws
+        return self._grow_workspace(need)
 
     def forward(self, wave: torch.Tensor, stage: int = 0, n_layers: int = 0) -> torch.Tensor:
         """wave [B,S] fp32 (normalised) -> last_hidden_state [B,T,1024]; stage 1/2/3 = debug taps (casync_hubert_forward_tap)."""
@@ -239,17 +222,6 @@ class HubertEngine:
         return out
 
     __call__ = forward
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.casync_hubert_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def normalize(speech: np.ndarray, do_normalize: bool = True) -> np.ndarray:

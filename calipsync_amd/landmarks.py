@@ -20,6 +20,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .engine_base import _PackedEngine
+
 INPUT_SIZE = 192
 N_LANDMARKS = 110
 BN_EPS = 1e-5                      # nn.BatchNorm2d's default, what every block of the reference is built with
@@ -198,41 +200,24 @@ def packed_tensors(sd) -> Dict[str, np.ndarray]:
 def pack(sd) -> np.ndarray:
     """The flat float32 buffer casync_pfld_load_weights_* takes, from either checkpoint form."""
     from . import _lib
-    named = packed_tensors(sd)
-    items, total = _lib.pfld_layout()
-    buf = np.zeros(total, dtype=np.float32)
-    for name, off, size in items:
-        a = named.pop(name).reshape(-1)
-        if a.size != size:
-            raise ValueError(f"packed tensor {name}: {a.size} floats, the engine expects {size}")
-        buf[off:off + size] = a
-    if named:
-        raise ValueError(f"tensors the engine layout does not name: {sorted(named)}")
-    return buf
+    return _lib.pack_named(packed_tensors(sd), _lib.pfld_layout())
 
 
 def unpack(buf: np.ndarray) -> Dict[str, np.ndarray]:
     """Inverse of pack (flat shapes)."""
     from . import _lib
-    items, _ = _lib.pfld_layout()
-    return {name: buf[off:off + size] for name, off, size in items}
+    return _lib.unpack_named(buf, _lib.pfld_layout())
 
 
-class PFLDEngine:
+class PFLDEngine(_PackedEngine):
     """PFLD_GhostOne().eval() on the HIP engine: forward(x [B,3,192,192] float in [0,1]) or forward_u8(crops [B,192,192,3]
     uint8 BGR) -> [B,220] on the device.  There is no CPU path."""
 
+    _destroy = "casync_pfld_destroy"
+
     def __init__(self, sd, device: str = "cuda:0"):
-        import ctypes as C
-        from . import _lib
         buf = pack(sd)                 # (checks the checkpoint before any device call)
-        self._lib = _lib.load()
-        self.device = torch.device(device)
-        h = C.c_void_p()
-        _lib.check(self._lib.casync_pfld_create(self.device.index or 0, C.byref(h)), "casync_pfld_create")
-        self._h = h
-        _lib.check(self._lib.casync_pfld_load_weights_host(self._h, buf.ctypes.data, buf.size), "casync_pfld_load_weights_host")
-        self._ws: Optional[torch.Tensor] = None
+        self._open(device, "casync_pfld_create", (), "casync_pfld_load_weights_host", buf)
 
     def workspace_bytes(self, batch: int) -> int:
         need = self._lib.casync_pfld_workspace_bytes(batch)
@@ -241,10 +226,7 @@ class PFLDEngine:
         return need
 
     def _workspace(self, batch: int) -> torch.Tensor:
-        need = self.workspace_bytes(batch)
-        if self._ws is None or self._ws.numel() * 4 < need:
-            self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
-        return self._ws
+        return self._grow_workspace(self.workspace_bytes(batch))
 
     def _run(self, x: torch.Tensor, u8: bool, stage: Optional[int], out: Optional[torch.Tensor], ws: Optional[torch.Tensor]):
         from . import _lib
@@ -275,17 +257,6 @@ class PFLDEngine:
         return self._run(crops.to(self.device).contiguous(), True, stage, out, workspace)
 
     __call__ = forward
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.casync_pfld_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _read_state_dict(weight_base_dir: str):
