@@ -217,6 +217,11 @@ _PROTOS = {
     "casync_op_jpeg_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int, c_i64]),
     "casync_op_jpeg_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the same trio for 4:2:0 (additive to ABI 13): rows are rows of 16 x 16 MCUs
+    "casync_op_jpeg420_header": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "casync_op_jpeg420_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int, c_i64]),
+    "casync_op_jpeg420_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -61,7 +61,7 @@ class FrameSynthesizer:
     def __init__(self, unet_checkpoint: Optional[str], data_dir: Optional[str], device: str = "cuda:0", batch_size: int = 8, *,
                  seed: Optional[int] = None, precision: str = "fp32", net: Optional[Model] = None,
                  batches_in_flight: Optional[int] = None, resident: Optional[bool] = None, clip=None, output: str = "frames",
-                 jpeg_quality: int = 95):
+                 jpeg_quality: int = 95, jpeg_subsampling="4:4:4"):
         """Same positional arguments as the reference (infer_api.py:13-14).  Keyword-only extensions:
         ``seed`` (reproducible frame walk), ``precision`` (engine storage type), ``net`` (an already
         loaded ``Model`` instead of a checkpoint path), ``batches_in_flight`` (default 1, or the
@@ -79,7 +79,9 @@ class FrameSynthesizer:
 
         ``output`` ("frames", the default, or "jpeg"; "jpeg" needs the resident path): the items of
         ``iterate_synthesized_frames`` carry ``'jpeg'``, the frame as a complete baseline JPEG file of ``jpeg_quality``
-        encoded on the device (``jpeg.encode_jpeg_device``), in place of ``'frame'``; no raw frame crosses to the host."""
+        encoded on the device (``jpeg.encode_jpeg_device``), in place of ``'frame'``; no raw frame crosses to the host.
+        ``jpeg_subsampling`` ("4:4:4", the default, or "4:2:0", libjpeg's own default: about half the bytes) is that file's chroma
+        sampling; the black frame of a failed load is encoded the same way."""
         if resident is None:
             resident = clip is not None or os.environ.get("CASYNC_RESIDENT_CLIP", "0").lower() not in ("", "0", "false")
         if clip is not None and not resident:
@@ -93,7 +95,8 @@ class FrameSynthesizer:
                 raise ValueError("output='jpeg' encodes the frames where they lie on the device: it needs resident=True or clip=")
             from . import jpeg
             jpeg.quant_tables(jpeg_quality)         # ValueError for a quality outside 1..100
-        self.output, self.jpeg_quality = output, int(jpeg_quality)
+            jpeg._subsampling(jpeg_subsampling)     # ValueError for anything but 4:4:4 / 0 and 4:2:0 / 2
+        self.output, self.jpeg_quality, self.jpeg_subsampling = output, int(jpeg_quality), jpeg_subsampling
         self.resident, self._clip = bool(resident), clip
         if batches_in_flight is None:
             batches_in_flight = int(os.environ.get("CASYNC_BATCHES_IN_FLIGHT", "1"))
@@ -204,7 +207,7 @@ class FrameSynthesizer:
 
     def _result(self, pending) -> list:
         """What a batch of the resident clip hands out: its frames, or (output="jpeg") their JPEG files."""
-        return pending.result_jpeg(self.jpeg_quality) if self.output == "jpeg" else pending.result()
+        return pending.result_jpeg(self.jpeg_quality, self.jpeg_subsampling) if self.output == "jpeg" else pending.result()
 
     def _collect(self, pending, originals) -> list:
         if pending is not None:
@@ -278,7 +281,7 @@ class FrameSynthesizer:
             black = np.zeros((480, 640, 3), dtype=np.uint8)
             if self.output == "jpeg":
                 from . import jpeg
-                black = jpeg.encode_jpeg_host(black, self.jpeg_quality)
+                black = jpeg.encode_jpeg_host(black, self.jpeg_quality, self.jpeg_subsampling)
             yield from self._emit([black], [0])
         finally:
             total_time = sum(time_stats.values())
@@ -314,7 +317,8 @@ class VideoStreamManager:
     ``audio_path`` is itself a ``.npy`` of features.  The mp4 writer / ffmpeg mux (inference.py:88-110) is used when cv2 / ffmpeg exist; otherwise
     the frames are written as a Motion-JPEG ``.avi`` with Pillow (``mjpeg_avi.py``; no audio track).  With ``output="jpeg",
     resident=True`` (passed on to ``FrameSynthesizer``) the frames are JPEG-encoded on the device and ``<stem>.avi`` is written
-    from those bytes, wherever cv2 exists or not: no raw frame is held on the host."""
+    from those bytes, wherever cv2 exists or not: no raw frame is held on the host.  ``jpeg_quality`` and ``jpeg_subsampling``
+    travel the same way."""
 
     def __init__(self, data_dir: str, unet_checkpoint: Optional[str], hubert_path=None, device: str = "cuda:0",
                  batch_size: int = 8, output_sample_rate: int = 24000, hubert_precision: str = "fp32", **synth_kwargs):

@@ -8,6 +8,10 @@ integer DCT, round-half-away quantisation), so the bytes are those of Pillow's
     files = encode_jpeg_device(frames_dev, quality=95)     # [B,H,W,3] uint8 on the device -> B complete files
     data = encode_jpeg_host(frame_bgr, quality=95)         # the same bytes from numpy
 
+``subsampling="4:2:0"`` (or 2, Pillow's number) on either entry writes libjpeg's default chroma sampling instead (csrc/jpeg_enc420.hip,
+DESIGN.md section 8i): Y sampled 2 x 2, Cb and Cr averaged 2 x 2, one restart interval per row of 16 x 16 MCUs, the bytes of
+Pillow's ``subsampling=2``.  4:4:4 stays the default.
+
 The restart markers make the block rows independent: the device encodes one row per wave.  The host twin is the fallback for
 a frame whose row outgrew its scratch slot, the subject of the CPU tests and the yardstick for inputs without a fixture."""
 from __future__ import annotations
@@ -87,19 +91,30 @@ def _huff_tables():
     return _HUFF
 
 
-def jpeg_header(H: int, W: int, quality: int = 95) -> bytes:
+def _subsampling(subsampling) -> int:
+    """"4:4:4" / 0 -> 0, "4:2:0" / 2 -> 2 (Pillow's numbers); anything else is a ValueError"""
+    if isinstance(subsampling, str):
+        if subsampling in ("4:4:4", "4:2:0"):
+            return 0 if subsampling == "4:4:4" else 2
+    elif not isinstance(subsampling, bool) and isinstance(subsampling, (int, np.integer)) and int(subsampling) in (0, 2):
+        return int(subsampling)
+    raise ValueError(f"jpeg: subsampling {subsampling!r} is neither '4:4:4' / 0 nor '4:2:0' / 2")
+
+
+def jpeg_header(H: int, W: int, quality: int = 95, subsampling="4:4:4") -> bytes:
     """Everything ahead of the scan, 629 bytes for any size and quality: SOI, APP0 (JFIF 1.1), the two DQT, SOF0, the four
-    DHT, DRI (one restart interval per block row) and SOS."""
+    DHT, DRI (one restart interval per block row; per row of 16 x 16 MCUs at 4:2:0, where Y samples 2 x 2) and SOS."""
     _check_size(H, W, quality)
     H, W = int(H), int(W)
+    sub = _subsampling(subsampling)
     seg = lambda marker, body: bytes((0xFF, marker)) + struct.pack(">H", len(body) + 2) + body
     luma, chroma = quant_tables(quality)
     out = b"\xff\xd8" + seg(0xE0, b"JFIF\0" + bytes((1, 1, 0, 0, 1, 0, 1, 0, 0)))
     out += seg(0xDB, bytes([0]) + bytes(int(v) for v in luma)) + seg(0xDB, bytes([1]) + bytes(int(v) for v in chroma))
-    out += seg(0xC0, bytes([8]) + struct.pack(">HH", H, W) + bytes((3, 1, 0x11, 0, 2, 0x11, 1, 3, 0x11, 1)))
+    out += seg(0xC0, bytes([8]) + struct.pack(">HH", H, W) + bytes((3, 1, 0x22 if sub else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1)))
     for ident, (bits, vals) in ((0x00, DC_LUMA), (0x10, AC_LUMA), (0x01, DC_CHROMA), (0x11, AC_CHROMA)):
         out += seg(0xC4, bytes([ident]) + bytes(bits) + bytes(vals))
-    out += seg(0xDD, struct.pack(">H", (W + 7) // 8)) + seg(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0)))
+    out += seg(0xDD, struct.pack(">H", (W + 15) // 16 if sub else (W + 7) // 8)) + seg(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0)))
     assert len(out) == HEADER_BYTES
     return out
 
@@ -136,17 +151,66 @@ def _fdct_pass(d, first: bool):
     return out
 
 
+def _ycc(f: np.ndarray) -> np.ndarray:
+    """[3, H, W] int64: libjpeg's 16-bit fixed-point Y, Cb, Cr of the unshifted 0..255 samples of a BGR frame"""
+    b, g, r = (f[:, :, i].astype(np.int64) for i in range(3))
+    half = 128 << 16
+    return np.stack([(19595 * r + 38470 * g + 7471 * b + 32768) >> 16,
+                     (-11059 * r - 21709 * g + 32768 * b + half + 32767) >> 16,
+                     (32768 * r - 27439 * g - 5329 * b + half + 32767) >> 16])
+
+
+def _transform(planes: np.ndarray, div: np.ndarray) -> np.ndarray:
+    """Level-shifted planes [..., 8 r, 8 c] -> [..., r, c, 64 (zigzag order)]: the two DCT passes and the round-half-away
+    quantisation by div (8 Q, zigzag order, broadcast against the result)."""
+    rows, cols = planes.shape[-2] // 8, planes.shape[-1] // 8
+    lead = planes.shape[:-2]
+    n = len(lead)
+    blocks = planes.reshape(lead + (rows, 8, cols, 8)).transpose(tuple(range(n)) + (n, n + 2, n + 1, n + 3))
+    coef = _fdct_pass(np.ascontiguousarray(blocks), True)                             # along x
+    coef = _fdct_pass(np.ascontiguousarray(coef.swapaxes(-1, -2)), False).swapaxes(-1, -2)    # along y
+    coef = coef.reshape(lead + (rows, cols, 64))[..., list(ZIGZAG)]
+    mag = (np.abs(coef) + (div >> 1)) // div
+    return np.where(coef < 0, -mag, mag)
+
+
+def quantized_blocks_420(frame_bgr: np.ndarray, quality: int = 95):
+    """The 4:2:0 scan of a frame, (q [MCU rows, MCUs per row, 6 (Y00, Y01, Y10, Y11, Cb, Cr), 64 (zigzag order)] int64,
+    dummy [MCU rows, MCUs per row, 6] bool).  Y is padded by edge replication to whole 8 x 8 blocks only: a Y block of an MCU
+    past those is a dummy, all zero but for the DC of the Y block before it in its MCU, so it codes as difference 0 and EOB.
+    Chroma: the full-resolution planes are padded on the right to whole MCUs (and by one row under an odd H), averaged 2 x 2
+    with libjpeg's alternating bias 1, 2, and the last *downsampled* row is repeated to whole blocks."""
+    f = np.asarray(frame_bgr)
+    H, W = f.shape[:2]
+    luma, chroma = (8 * t.astype(np.int64) for t in quant_tables(quality))
+    ycc = _ycc(f)
+    mrows, mcols = (H + 15) // 16, (W + 15) // 16
+    y = np.pad(ycc[0], ((0, -H % 8), (0, -W % 8)), mode="edge") - 128
+    yq = _transform(y, luma)                                                          # [ceil(H/8), ceil(W/8), 64]
+    q = np.zeros((2 * mrows, 2 * mcols, 64), dtype=np.int64)
+    q[:yq.shape[0], :yq.shape[1]] = yq
+    dummy = np.ones((2 * mrows, 2 * mcols), dtype=bool)
+    dummy[:yq.shape[0], :yq.shape[1]] = False
+    mcu = lambda a: a.reshape((mrows, 2, mcols, 2) + a.shape[2:]).swapaxes(1, 2).reshape((mrows, mcols, 4) + a.shape[2:])
+    q, dummy = mcu(q), mcu(dummy)
+    for k in range(1, 4):                                                             # block 0 of an MCU is never a dummy
+        q[..., k, 0] = np.where(dummy[..., k], q[..., k - 1, 0], q[..., k, 0])
+    c = np.pad(ycc[1:], ((0, 0), (0, H % 2), (0, 16 * mcols - W)), mode="edge")
+    bias = np.where(np.arange(8 * mcols) % 2, 2, 1)
+    c = (c[:, 0::2, 0::2] + c[:, 0::2, 1::2] + c[:, 1::2, 0::2] + c[:, 1::2, 1::2] + bias) >> 2
+    c = np.pad(c, ((0, 0), (0, 8 * mrows - c.shape[1]), (0, 0)), mode="edge") - 128
+    cq = _transform(c, chroma)                                                        # [2, mrows, mcols, 64]
+    q = np.concatenate([q, cq.transpose(1, 2, 0, 3)], axis=2)
+    return q, np.concatenate([dummy, np.zeros((mrows, mcols, 2), dtype=bool)], axis=2)
+
+
 def quantized_blocks(frame_bgr: np.ndarray, quality: int = 95) -> np.ndarray:
     """The quantised coefficients [block rows, MCUs per row, 3 (Y, Cb, Cr), 64 (zigzag order)] int64 of a frame: colour
     conversion, edge replication, DCT and quantisation, vectorised over every block."""
     f = np.asarray(frame_bgr)
     H, W = f.shape[:2]
     luma, chroma = quant_tables(quality)
-    b, g, r = (f[:, :, i].astype(np.int64) for i in range(3))
-    half = 128 << 16
-    ycc = np.stack([(19595 * r + 38470 * g + 7471 * b + 32768) >> 16,
-                    (-11059 * r - 21709 * g + 32768 * b + half + 32767) >> 16,
-                    (32768 * r - 27439 * g - 5329 * b + half + 32767) >> 16]) - 128
+    ycc = _ycc(f) - 128
     ycc = np.pad(ycc, ((0, 0), (0, -H % 8), (0, -W % 8)), mode="edge")
     rows, cols = ycc.shape[1] // 8, ycc.shape[2] // 8
     blocks = ycc.reshape(3, rows, 8, cols, 8).transpose(1, 3, 0, 2, 4)               # [rows, cols, 3, y, x]
@@ -166,28 +230,34 @@ def _bit_length(v: np.ndarray) -> np.ndarray:
     return n
 
 
-def scan_symbols(q: np.ndarray):
-    """The code words of a scan, vectorised over every block: q [rows, cols, 3, 64] quantised coefficients -> (row [n], code [n],
-    length [n], kind [n]) in stream order, where kind is 0 for a DC code (its category is length's companion in the symbol
-    statistics), 1 for an AC code, 2 for ZRL and 3 for EOB, and (dc categories [n_dc], ac categories [n_ac]) for the statistics."""
-    rows, cols = q.shape[:2]
+def scan_symbols(q: np.ndarray, components=(0, 1, 2)):
+    """The code words of a scan, vectorised over every block: q [rows, cols, blocks of an MCU, 64] quantised coefficients, of
+    which block k belongs to components[k] (0 Y, 1 Cb, 2 Cr) -> (row [n], code [n], length [n], kind [n]) in stream order, where
+    kind is 0 for a DC code (its category is length's companion in the symbol statistics), 1 for an AC code, 2 for ZRL and 3 for
+    EOB, and (dc categories [n_dc], ac categories [n_ac]) for the statistics."""
+    rows, cols, nb = q.shape[:3]
+    components = np.asarray(components, dtype=np.int64)
     (dcl_c, dcl_s), (acl_c, acl_s), (dcc_c, dcc_s), (acc_c, acc_s) = _huff_tables()
     dc_code = np.stack([dcl_c, dcc_c, dcc_c])
     dc_size = np.stack([dcl_s, dcc_s, dcc_s])
     ac_code = np.stack([acl_c, acc_c, acc_c])
     ac_size = np.stack([acl_s, acc_s, acc_s])
-    comp = np.broadcast_to(np.arange(3)[None, None, :], (rows, cols, 3))
-    # order key of a code word: ((row, col, comp), k, sub) with sub = position among the words one coefficient emits
-    block_id = (np.arange(rows)[:, None, None] * cols + np.arange(cols)[None, :, None]) * 3 + np.arange(3)[None, None, :]
+    comp = np.broadcast_to(components[None, None, :], (rows, cols, nb))
+    # order key of a code word: ((row, col, block), k, sub) with sub = position among the words one coefficient emits
+    block_id = (np.arange(rows)[:, None, None] * cols + np.arange(cols)[None, :, None]) * nb + np.arange(nb)[None, None, :]
 
     def words(v, huff_code, huff_size):
         cat = _bit_length(np.abs(v))
         low = np.where(v < 0, v - 1, v) & ((1 << cat) - 1)
         return cat, (huff_code << cat) | low, huff_size + cat
 
-    # DC: difference against the same component of the previous MCU of the row
+    # DC: difference against the previous block of the same component in the row
     dc = q[..., 0]
-    diff = dc - np.concatenate([np.zeros((rows, 1, 3), dtype=np.int64), dc[:, :-1]], axis=1)
+    diff = np.empty_like(dc)
+    for c in range(3):
+        mine = np.nonzero(components == c)[0]
+        seq = dc[:, :, mine].reshape(rows, -1)
+        diff[:, :, mine] = (seq - np.concatenate([np.zeros((rows, 1), dtype=np.int64), seq[:, :-1]], axis=1)).reshape(rows, cols, -1)
     dc_cat = _bit_length(np.abs(diff))
     _, code, size = words(diff, dc_code[comp, dc_cat], dc_size[comp, dc_cat])
     keys = [block_id.reshape(-1) * 64 * 4]
@@ -226,7 +296,7 @@ def scan_symbols(q: np.ndarray):
     key = np.concatenate(keys)
     order = np.argsort(key, kind="stable")
     key = key[order]
-    return (key // (cols * 3 * 64 * 4), np.concatenate(codes)[order], np.concatenate(sizes)[order], np.concatenate(kinds)[order],
+    return (key // (cols * nb * 64 * 4), np.concatenate(codes)[order], np.concatenate(sizes)[order], np.concatenate(kinds)[order],
             (dc_cat.reshape(-1), cat))
 
 
@@ -258,63 +328,92 @@ def _check_frame(frame_bgr) -> np.ndarray:
     return f
 
 
-def encode_jpeg_host(frame_bgr: np.ndarray, quality: int = 95) -> bytes:
-    """One BGR uint8 [H,W,3] frame as a complete baseline JPEG file: the numpy twin of the device encoder."""
+Y420 = (0, 0, 0, 0, 1, 2)         # the component of each block of a 4:2:0 MCU
+
+
+def _scan_blocks(f: np.ndarray, quality: int, sub: int):
+    """(q [restart rows, MCUs per row, blocks of an MCU, 64], the component of each block of an MCU)"""
+    if sub:
+        return quantized_blocks_420(f, quality)[0], Y420
+    return quantized_blocks(f, quality), (0, 1, 2)
+
+
+def encode_jpeg_host(frame_bgr: np.ndarray, quality: int = 95, subsampling="4:4:4") -> bytes:
+    """One BGR uint8 [H,W,3] frame as a complete baseline JPEG file: the numpy twin of the device encoder, 4:4:4 or 4:2:0."""
     f = _check_frame(frame_bgr)
+    sub = _subsampling(subsampling)
     H, W = f.shape[:2]
-    out = [jpeg_header(H, W, quality)]
-    q = quantized_blocks(f, quality)
+    out = [jpeg_header(H, W, quality, sub)]
+    q, components = _scan_blocks(f, quality, sub)
     rows = q.shape[0]
-    row, code, size, _, _ = scan_symbols(q)
+    row, code, size, _, _ = scan_symbols(q, components)
     for r, data in enumerate(_pack_rows(row, code, size, rows)):
         out.append(data.replace(b"\xff", b"\xff\x00"))
         out.append(bytes((0xFF, 0xD0 + (r & 7))) if r + 1 < rows else b"\xff\xd9")
     return b"".join(out)
 
 
-def symbol_statistics(frame_bgr: np.ndarray, quality: int = 95) -> dict:
-    """What the scan of a frame exercises (tests/golden/make_jpeg_golden.py asserts coverage over its cases): the DC and AC
-    categories seen, the number of ZRL codes, of blocks without an EOB, of stuffed bytes, and the block rows."""
+def symbol_statistics(frame_bgr: np.ndarray, quality: int = 95, subsampling="4:4:4") -> dict:
+    """What the scan of a frame exercises (tests/golden/make_jpeg_golden.py and make_jpeg420_golden.py assert coverage over their
+    cases): the DC and AC categories seen, the number of ZRL codes, of blocks without an EOB, of stuffed bytes, and the restart
+    rows (block rows at 4:4:4, MCU rows at 4:2:0)."""
     f = _check_frame(frame_bgr)
-    q = quantized_blocks(f, quality)
+    q, components = _scan_blocks(f, quality, _subsampling(subsampling))
     rows = q.shape[0]
-    row, code, size, kind, (dc_cat, ac_cat) = scan_symbols(q)
+    row, code, size, kind, (dc_cat, ac_cat) = scan_symbols(q, components)
     stuffed = sum(d.count(b"\xff") for d in _pack_rows(row, code, size, rows))
     return {"dc": set(int(v) for v in np.unique(dc_cat)), "ac": set(int(v) for v in np.unique(ac_cat)),
-            "zrl": int((kind == 2).sum()), "no_eob": int(q.shape[0] * q.shape[1] * 3 - (kind == 3).sum()), "stuffed": int(stuffed),
-            "rows": int(rows)}
+            "zrl": int((kind == 2).sum()), "no_eob": int(q.shape[0] * q.shape[1] * q.shape[2] - (kind == 3).sum()),
+            "stuffed": int(stuffed), "rows": int(rows)}
 
 
 # ---------------------------------------------------------------------------------------------------------------- device
-def default_slot_bytes(W: int) -> int:
-    """The scratch slot of one block row when slot_bytes = 0: twice its raw bytes."""
+def default_slot_bytes(W: int, subsampling="4:4:4") -> int:
+    """The scratch slot of one restart row when slot_bytes = 0: twice the raw bytes of the samples it codes (a block row of
+    three planes at 4:4:4; at 4:2:0 an MCU row, 384 samples per 16 x 16 MCU)."""
+    if _subsampling(subsampling):
+        return 2 * 384 * ((int(W) + 15) // 16)
     return 2 * 8 * 3 * 8 * ((int(W) + 7) // 8)
 
 
-def _header_from_lib(H: int, W: int, quality: int) -> bytes:
+def restart_rows(H: int, subsampling="4:4:4") -> int:
+    """Restart intervals of a frame: rows of 8 x 8 blocks at 4:4:4, of 16 x 16 MCUs at 4:2:0"""
+    return (int(H) + 15) // 16 if _subsampling(subsampling) else (int(H) + 7) // 8
+
+
+def _entry(name: str, sub: int) -> str:
+    """casync_op_jpeg_<name> or its 4:2:0 sibling casync_op_jpeg420_<name>"""
+    return f"casync_op_jpeg420_{name}" if sub else f"casync_op_jpeg_{name}"
+
+
+def _header_from_lib(H: int, W: int, quality: int, subsampling="4:4:4") -> bytes:
     from . import _lib
+    entry = _entry("header", _subsampling(subsampling))
     buf = (C.c_uint8 * HEADER_BYTES)()
-    n = _lib.check(_lib.load().casync_op_jpeg_header(H, W, quality, buf, HEADER_BYTES), "casync_op_jpeg_header")
+    n = _lib.check(getattr(_lib.load(), entry)(H, W, quality, buf, HEADER_BYTES), entry)
     return bytes(buf[:n])
 
 
-def encode_jpeg_op(frames, quality: int, slot_bytes: int, scratch, out, offsets, status) -> None:
-    """casync_op_jpeg_encode on torch's current stream, every buffer the caller's (uint8 scratch and out, int64 offsets [B+1],
-    int32 status [B]); nothing is waited for."""
+def encode_jpeg_op(frames, quality: int, slot_bytes: int, scratch, out, offsets, status, subsampling="4:4:4") -> None:
+    """casync_op_jpeg_encode (casync_op_jpeg420_encode for 4:2:0) on torch's current stream, every buffer the caller's (uint8
+    scratch and out, int64 offsets [B+1], int32 status [B]); nothing is waited for."""
     import torch
     from . import _lib
+    entry = _entry("encode", _subsampling(subsampling))
     B, H, W = (int(v) for v in frames.shape[:3])
-    _lib.check(_lib.load().casync_op_jpeg_encode(frames.data_ptr(), B, H, W, int(quality), int(slot_bytes), scratch.data_ptr(),
-                                                 scratch.numel(), out.data_ptr(), out.numel(), offsets.data_ptr(), status.data_ptr(),
-                                                 torch.cuda.current_stream(frames.device).cuda_stream), "casync_op_jpeg_encode")
+    _lib.check(getattr(_lib.load(), entry)(frames.data_ptr(), B, H, W, int(quality), int(slot_bytes), scratch.data_ptr(),
+                                           scratch.numel(), out.data_ptr(), out.numel(), offsets.data_ptr(), status.data_ptr(),
+                                           torch.cuda.current_stream(frames.device).cuda_stream), entry)
 
 
-def encode_jpeg_device(frames, quality: int = 95, *, slot_bytes: int = 0) -> List[bytes]:
+def encode_jpeg_device(frames, quality: int = 95, *, subsampling="4:4:4", slot_bytes: int = 0) -> List[bytes]:
     """uint8 [B,H,W,3] BGR frames on the device -> B complete JPEG files, encoded where they lie (torch's current stream).
     Two copies cross to the host: offsets and status, then exactly the bytes produced (through ``frame_loop``'s pinned pool).
     A frame whose row outgrew its ``slot_bytes`` scratch slot (0: twice the row's raw bytes) is downloaded alone and encoded
-    by ``encode_jpeg_host``, so the caller always gets B valid files."""
+    by ``encode_jpeg_host``, so the caller always gets B valid files.  ``subsampling`` "4:2:0" writes what libjpeg writes by
+    default: chroma at half resolution both ways, six blocks per 16 x 16 pixels in place of twelve."""
     import torch
+    sub = _subsampling(subsampling)
     if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
         what = f"{tuple(frames.shape)} {frames.dtype}" if isinstance(frames, torch.Tensor) else type(frames).__name__
         raise ValueError(f"encode_jpeg_device: needs a uint8 [B,H,W,3] tensor, got {what}")
@@ -333,18 +432,18 @@ def encode_jpeg_device(frames, quality: int = 95, *, slot_bytes: int = 0) -> Lis
     lib = _lib.load()
     frames = frames.contiguous()
     dev = frames.device
-    slot = int(slot_bytes) or default_slot_bytes(W)
-    rows = (H + 7) // 8
-    need = lib.casync_op_jpeg_workspace_bytes(B, H, W, slot)
+    slot = int(slot_bytes) or default_slot_bytes(W, sub)
+    rows = restart_rows(H, sub)
+    need = getattr(lib, _entry("workspace_bytes", sub))(B, H, W, slot)
     if need < 0:
-        _lib.check(int(need), "casync_op_jpeg_workspace_bytes")
+        _lib.check(int(need), _entry("workspace_bytes", sub))
     cap = B * (HEADER_BYTES + rows * slot)                     # a frame that passed its slots fits here
     with torch.cuda.device(dev):
         scratch = torch.empty(need, dtype=torch.uint8, device=dev)
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
         meta = torch.empty(B + 1 + (B + 1) // 2, dtype=torch.int64, device=dev)        # offsets [B+1] | status [B] int32
         offsets, status = meta[:B + 1], meta[B + 1:].view(torch.int32)[:B]
-        encode_jpeg_op(frames, quality, slot, scratch, out, offsets, status)
+        encode_jpeg_op(frames, quality, slot, scratch, out, offsets, status, sub)
         meta_host = frame_loop._acquire_pinned(meta.numel() * 8)
         data_host = None
         try:
@@ -364,7 +463,7 @@ def encode_jpeg_device(frames, quality: int = 95, *, slot_bytes: int = 0) -> Lis
                 if st[i] == 0:
                     files.append(data[off[i]:off[i + 1]].tobytes())
                 else:                                          # a row outgrew its slot: this frame alone, on the host
-                    files.append(encode_jpeg_host(frames[i].cpu().numpy(), quality))
+                    files.append(encode_jpeg_host(frames[i].cpu().numpy(), quality, sub))
             return files
         finally:
             frame_loop._release_pinned(meta_host)

@@ -129,13 +129,13 @@ class PendingClipBatch:
             self._frames = _hand_out(host, b, h, w)
         return self._frames
 
-    def result_jpeg(self, quality: int = 95) -> List[bytes]:
-        """The finished frames as B complete baseline JPEG files (4:4:4, one restart interval per block row), encoded on the
-        device where ``result_device()`` lies (``jpeg.encode_jpeg_device``, on torch's current stream): what crosses to the
-        host is the compressed bytes.  The raw download is not run; when this is the only result wanted, submit with
-        ``download=False``."""
+    def result_jpeg(self, quality: int = 95, subsampling="4:4:4") -> List[bytes]:
+        """The finished frames as B complete baseline JPEG files (4:4:4 and one restart interval per block row, or with
+        ``subsampling="4:2:0"`` libjpeg's default chroma subsampling and one per MCU row), encoded on the device where
+        ``result_device()`` lies (``jpeg.encode_jpeg_device``, on torch's current stream): what crosses to the host is the
+        compressed bytes.  The raw download is not run; when this is the only result wanted, submit with ``download=False``."""
         from . import jpeg
-        return jpeg.encode_jpeg_device(self._out, quality)
+        return jpeg.encode_jpeg_device(self._out, quality, subsampling=subsampling)
 
 
 class _Chunks:

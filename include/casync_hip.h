@@ -46,7 +46,7 @@ enum {
 #define CASYNC_ABI_VERSION 13  /* 12: S3FD face detector handle (casync_s3fd_*, casync_op_s3fd_*); 13: its bf16 precision
                                 * (casync_s3fd_create_ex, _precision, _workspace_bytes_ex, casync_op_s3fd16_*).  The face-pipeline
                                 * operators at the end of this file (casync_op_resize_linear_u8, _face_crops192, _s3fd_candidates,
-                                * _landmarks_finalize), casync_op_s3fd_nms, casync_op_clip_gather / _compose and casync_op_jpeg_* were added under 13: new symbols only, no prototype or layout changed */
+                                * _landmarks_finalize), casync_op_s3fd_nms, casync_op_clip_gather / _compose, casync_op_jpeg_* and casync_op_jpeg420_* were added under 13: new symbols only, no prototype or layout changed */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -659,6 +659,37 @@ int64_t casync_op_jpeg_workspace_bytes(int batch, int H, int W, int64_t slot_byt
 int     casync_op_jpeg_encode(const uint8_t* frames_bgr, int batch, int H, int W, int quality, int64_t slot_bytes, uint8_t* scratch,
                               int64_t scratch_bytes, uint8_t* out, int64_t out_cap, int64_t* offsets, int32_t* status,
                               casync_stream stream);
+
+/* ---- 4:2:0 baseline JPEG of finished frames (additive to ABI 13: three new symbols, nothing else changed) ---------- */
+/* The casync_op_jpeg_* trio with chroma at half resolution both ways, what libjpeg writes by default: the same argument lists,
+ * status codes, buffer contracts and refusals, where a "row" is a row of 16 x 16 MCUs, ceil(H / 16) of them.  The stream: the
+ * same 629 header bytes but for SOF0 (Y samples 2 x 2: component 1 is 0x22, components 2 and 3 stay 0x11) and DRI (ceil(W / 16),
+ * one restart interval per MCU row); then the scan, every MCU row padded with 1-bits and closed by RSTn (n counts MCU rows from
+ * 0, modulo 8), the last one by EOI.  One MCU is Y(2r,2c), Y(2r,2c+1), Y(2r+1,2c), Y(2r+1,2c+1), Cb(r,c), Cr(r,c); the three DC
+ * predictors restart at 0 at the head of every MCU row.
+ *   Y:      the last column and row repeated up to 8 ceil(W / 8) x 8 ceil(H / 8), then level-shifted.  A Y block of an MCU past
+ *           those (block column >= ceil(W / 8) or block row >= ceil(H / 8)) is a dummy: its AC coefficients are zero and its DC
+ *           is that of the Y block before it in the same MCU, so it codes as DC difference 0 and EOB.
+ *   Cb, Cr: the full-resolution plane of the 16-bit fixed-point colour conversion is padded on the right to 16 ceil(W / 16)
+ *           columns by repeating the last column, and at the bottom by one repeated row when H is odd; every output sample is
+ *           (a + b + c + d + bias) >> 2 over its 2 x 2 inputs, bias 1 in even output columns and 2 in odd ones; the last
+ *           downsampled row is then repeated up to 8 ceil(H / 16) rows; then the level shift.
+ * DCT, quantisation (luma table for Y, chroma table for Cb and Cr), Huffman tables, padding and byte stuffing are those of the
+ * 4:4:4 stream, so the bytes are those of libjpeg-turbo for quality q, 2 x 2 chroma subsampling and one restart interval per
+ * MCU row (calipsync_amd/jpeg.py encode_jpeg_host(..., subsampling="4:2:0") is the numpy twin; tests/golden/jpeg420_cases.npz
+ * holds the recorded bytes).
+ *   jpeg420_header:          HOST ONLY.  Writes the 629 header bytes to out (host memory, cap >= 629) and returns their number.
+ *   jpeg420_workspace_bytes: the row lengths, then one slot of slot_bytes per MCU row of every frame.  slot_bytes 0 = the default,
+ *     twice the raw bytes of the samples an MCU row codes: 2 * 384 * ceil(W / 16).
+ *   jpeg420_encode:          as jpeg_encode.  status 1: an MCU row outgrew its slot; status 2: the frame would pass out_cap.
+ * One wave per MCU row (two lanes per MCU, 32 MCUs at a time: colour, downsampling, DCT and quantisation in registers, 24 KB of
+ * coefficients and 8 KB of code bits in LDS; a dummy block runs no DCT), then the same plan and pack stages.  The output is a
+ * pure function of the input: no global atomics, one writer per byte.  No allocation, no synchronisation.                   */
+int     casync_op_jpeg420_header(int H, int W, int quality, uint8_t* out, int cap);
+int64_t casync_op_jpeg420_workspace_bytes(int batch, int H, int W, int64_t slot_bytes);
+int     casync_op_jpeg420_encode(const uint8_t* frames_bgr, int batch, int H, int W, int quality, int64_t slot_bytes, uint8_t* scratch,
+                                 int64_t scratch_bytes, uint8_t* out, int64_t out_cap, int64_t* offsets, int32_t* status,
+                                 casync_stream stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Finished frames off the device as JPEG files against today's raw download and Pillow encode, on one MI355X, in one process.
 
     python tools/jpeg_bench.py [--frames 64] [--batches 16,64] [--quality 95] [--contents smooth,noise] [--rounds 3] [--threads 16]
-                               [--json profiles/jpeg_bench.json]
+                               [--json profiles/jpeg_bench.json] [--subsampling 4:4:4,4:2:0]
 
 Frames are synthetic 1080 x 1920, resident on the device (ResidentClip; no network runs: a batch is ``clip.fetch``, the compose
 of stored frames, so the figures are those of getting finished frames off the device and nothing else).  Two contents: `smooth`,
@@ -17,6 +17,10 @@ Every leg is warmed up once, then the legs alternate for --rounds rounds; a line
 round.  A difference between two legs counts only where it exceeds that spread.  Beside them the mean JPEG size of a frame.
 Legs b, c and d produce the same files for the same frames up to Pillow's missing restart markers (b's bytes are checked against
 the numpy twin in tests/test_jpeg_gpu.py, not here).
+
+With ``--subsampling 4:4:4,4:2:0`` the tool compares the chroma samplings of the encoder instead (the
+default --json becomes profiles/jpeg420_bench.json): per content and B only legs a and b, once per setting, the settings
+alternating within each round on the same frames, and per setting the mean file size.
 
 It needs a GPU and does not fall back.
 """
@@ -52,14 +56,14 @@ def make_content(kind, n):
     return frames
 
 
-def kernel_ms(frames_dev, quality, repeats=10):
-    """device ms of one casync_op_jpeg_encode on the batch, by events: the median"""
+def kernel_ms(frames_dev, quality, repeats=10, subsampling="4:4:4"):
+    """device ms of one casync_op_jpeg_encode (casync_op_jpeg420_encode) on the batch, by events: the median"""
     import torch
     from calipsync_amd import _lib, jpeg
     B = int(frames_dev.shape[0])
-    rows = (H + 7) // 8
-    slot = jpeg.default_slot_bytes(W)
-    need = _lib.load().casync_op_jpeg_workspace_bytes(B, H, W, 0)
+    rows = jpeg.restart_rows(H, subsampling)
+    slot = jpeg.default_slot_bytes(W, subsampling)
+    need = getattr(_lib.load(), jpeg._entry("workspace_bytes", jpeg._subsampling(subsampling)))(B, H, W, 0)
     dev = frames_dev.device
     scratch = torch.empty(need, dtype=torch.uint8, device=dev)
     out = torch.empty(B * (jpeg.HEADER_BYTES + rows * slot), dtype=torch.uint8, device=dev)
@@ -69,7 +73,7 @@ def kernel_ms(frames_dev, quality, repeats=10):
     for r in range(repeats + 2):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         ev[0].record()
-        jpeg.encode_jpeg_op(frames_dev, quality, 0, scratch, out, offsets, status)
+        jpeg.encode_jpeg_op(frames_dev, quality, 0, scratch, out, offsets, status, subsampling)
         ev[1].record()
         torch.cuda.synchronize()
         if r >= 2:
@@ -83,6 +87,33 @@ def spread(values):
     return {"ms": round(statistics.median(v), 3), "ms_min_max": [round(v[0], 3), round(v[-1], 3)]}
 
 
+def compare_settings(clip, idx, kind, settings, a):
+    """legs a and b of every chroma sampling in `settings` on one batch: round 0 warms up, then the settings alternate"""
+    import torch
+    B = len(idx)
+    frames_dev = clip.fetch(idx, download=False).result_device()
+    k_ms, j_ms, size = ({s: [] for s in settings} for _ in range(3))
+    for r in range(a.rounds + 1):
+        for s in settings:
+            k, mean_bytes = kernel_ms(frames_dev, a.quality, subsampling=s)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            files = clip.fetch(idx, download=False).result_jpeg(a.quality, s)
+            t = (time.perf_counter() - t0) * 1e3
+            assert len(files) == B and sum(len(f) for f in files) == round(mean_bytes * B)
+            if r:
+                k_ms[s].append(k)
+                j_ms[s].append(t)
+                size[s] = int(mean_bytes)
+    res = {"what": "subsampling", "content": kind, "batch": B, "quality": a.quality, "frame": [H, W], "rounds": a.rounds,
+           "raw_bytes": H * W * 3, "settings": {}}
+    for s in settings:
+        res["settings"][s] = {"mean_jpeg_bytes": size[s],
+                              "a_kernels": dict(spread(k_ms[s]), frames_per_s=round(B / statistics.median(k_ms[s]) * 1e3, 1)),
+                              "b_jpeg": dict(spread(j_ms[s]), frames_per_s=round(B / statistics.median(j_ms[s]) * 1e3, 1))}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
@@ -91,8 +122,12 @@ def main():
     ap.add_argument("--contents", default="smooth,noise")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16)
-    ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "jpeg_bench.json"))
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--subsampling", default=None, help="e.g. 4:4:4,4:2:0: compare the encoder's chroma samplings (legs a and b only)")
     a = ap.parse_args()
+    if a.json is None:
+        a.json = os.path.join(ROOT, "profiles", "jpeg420_bench.json" if a.subsampling else "jpeg_bench.json")
+    settings = a.subsampling.split(",") if a.subsampling else None
     if a.rounds < 3:
         raise SystemExit("at least three rounds per leg")
     import torch
@@ -113,6 +148,10 @@ def main():
             if B > a.frames:
                 continue
             idx = list(range(B))
+            if settings:
+                lines.append(compare_settings(clip, idx, kind, settings, a))
+                print(json.dumps(lines[-1]), flush=True)
+                continue
             k_ms, mean_bytes = kernel_ms(clip.fetch(idx, download=False).result_device(), a.quality)
 
             def leg(name):
@@ -142,7 +181,7 @@ def main():
         clip.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
     with open(a.json, "w") as f:
-        args = " ".join(f"--{k.replace('_', '-')} {v}" for k, v in sorted(vars(a).items()) if k != "json")
+        args = " ".join(f"--{k.replace('_', '-')} {v}" for k, v in sorted(vars(a).items()) if k != "json" and v is not None)
         json.dump({"what": f"tools/jpeg_bench.py {args} on one MI355X, profiler off", "source_hash": build.source_hash(), "lines": lines}, f,
                   indent=1)
         f.write("\n")
