@@ -14,40 +14,76 @@ from calipsync_amd import facedet
 
 STAGE_AFTER = {2: "conv1_2", 7: "conv2_2", 14: "conv3_3", 21: "conv4_3", 28: "conv5_3", 31: "fc6", 33: "fc7"}
 POOLS = {2: False, 7: False, 14: True, 21: False, 28: False}       # vgg index of the conv in front of a pool -> ceil_mode
+SOURCES = ("conv3_3", "conv4_3", "conv5_3", "fc7", "conv6_2", "conv7_2")   # the taps the heads read, in prior order
+# every conv of the trunk in forward order: (state-dict prefix, engine name, conv2d arguments, ceil_mode of the pool behind it
+# or None, the tap it ends or None)
+_CONVS = tuple((f"vgg.{idx}", name, dict(padding=6, dilation=6) if name == "fc6" else dict(padding=k // 2), POOLS.get(idx),
+                STAGE_AFTER.get(idx)) for idx, name, _cin, _cout, k in facedet.VGG) + \
+    tuple((f"extras.{idx}", name, dict(stride=2 if k == 3 else 1, padding=k // 2), None, name if k == 3 else None)
+          for idx, name, _cin, _cout, k in facedet.EXTRAS)
+_TAPS = tuple(c[4] for c in _CONVS if c[4])
+assert _TAPS == facedet.STAGES[:9]
 
 
-def network(sd, x, dtype=torch.float64):
-    """x [B,3,H,W] (mean subtracted) -> {stage: NCHW tensor, "loc": [B,P,4], "conf": [B,P,2] logits after the max-out}"""
-    p = {k: (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))).to(dtype) for k, v in sd.items()}   # (tensors: any device)
+def _param(sd, key, dtype):
+    v = sd[key]
+    return (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))).to(dtype)   # (tensors: any device)
+
+
+def segment(sd, x, start, dtype=torch.float64, post=None):
+    """One stretch of the trunk: from the tensor at tap `start` (a name or an index of facedet.STAGES[:9]; None = the
+    mean-subtracted input [B,3,H,W]) to the next tap -> (name, NCHW tensor).  A tap is taken after its ReLU and before its pool,
+    so the pool behind tap `start` opens this segment.  post, where given, is applied to the output of every conv (after the
+    ReLU): a model of an engine that rounds there."""
+    start = _TAPS[start] if isinstance(start, int) else start
+    first = 0 if start is None else 1 + [c[4] for c in _CONVS].index(start)
+    if first >= len(_CONVS):
+        raise ValueError(f"s3fd_ref.segment: no tap behind {start}")
     x = torch.as_tensor(x).to(dtype)
-    taps, sources = {}, []
-    for idx, name, _cin, _cout, k in facedet.VGG:
-        kw = dict(padding=6, dilation=6) if name == "fc6" else dict(padding=k // 2)
-        x = F.relu(F.conv2d(x, p[f"vgg.{idx}.weight"], p[f"vgg.{idx}.bias"], **kw))
-        if idx in STAGE_AFTER:
-            taps[STAGE_AFTER[idx]] = x
-        if idx in (14, 21, 28):
-            norm = x.pow(2).sum(dim=1, keepdim=True).sqrt() + 1e-10
-            sources.append(p[f"{facedet.L2NORMS[len(sources)][0]}.weight"].view(1, -1, 1, 1) * torch.div(x, norm))
-        if idx in POOLS:
-            x = F.max_pool2d(x, 2, 2, ceil_mode=POOLS[idx])
-    sources.append(x)
-    for idx, name, _cin, _cout, k in facedet.EXTRAS:
-        x = F.relu(F.conv2d(x, p[f"extras.{idx}.weight"], p[f"extras.{idx}.bias"], stride=2 if k == 3 else 1, padding=k // 2))
-        if k == 3:
-            taps[name] = x
-            sources.append(x)
-    loc, conf = [], []
-    for k, s in enumerate(sources):
-        lo = F.conv2d(s, p[f"loc.{k}.weight"], p[f"loc.{k}.bias"], padding=1)
-        co = F.conv2d(s, p[f"conf.{k}.weight"], p[f"conf.{k}.bias"], padding=1)
+    if first and _CONVS[first - 1][3] is not None:
+        x = F.max_pool2d(x, 2, 2, ceil_mode=_CONVS[first - 1][3])
+    for prefix, _name, kw, _pool, tap in _CONVS[first:]:
+        x = F.relu(F.conv2d(x, _param(sd, f"{prefix}.weight", dtype).to(x.device), _param(sd, f"{prefix}.bias", dtype).to(x.device), **kw))
+        if post is not None:
+            x = post(x)
+        if tap:
+            return tap, x
+        if _pool is not None:
+            x = F.max_pool2d(x, 2, 2, ceil_mode=_pool)
+    raise AssertionError("unreachable: the last conv ends a tap")
+
+
+def heads(sd, taps, dtype=torch.float64, post=None):
+    """the six source taps (SOURCES order; a list, or a dict that holds them) -> (loc [B,P,4], conf [B,P,2] logits after conf[0]'s
+    max-out, maps): L2Norm on the first three, then loc[k] / conf[k].  post, where given, is applied to x / norm."""
+    if isinstance(taps, dict):
+        taps = [taps[n] for n in SOURCES]
+    loc, conf, maps = [], [], []
+    for k, s in enumerate(taps):
+        s = torch.as_tensor(s).to(dtype)
+        if k < 3:
+            norm = s.pow(2).sum(dim=1, keepdim=True).sqrt() + 1e-10
+            s = torch.div(s, norm)
+            s = _param(sd, f"{facedet.L2NORMS[k][0]}.weight", dtype).to(s.device).view(1, -1, 1, 1) * (s if post is None else post(s))
+        lo = F.conv2d(s, _param(sd, f"loc.{k}.weight", dtype).to(s.device), _param(sd, f"loc.{k}.bias", dtype).to(s.device), padding=1)
+        co = F.conv2d(s, _param(sd, f"conf.{k}.weight", dtype).to(s.device), _param(sd, f"conf.{k}.bias", dtype).to(s.device), padding=1)
         if k == 0:
             co = torch.cat((co[:, 0:3].max(dim=1, keepdim=True)[0], co[:, 3:]), dim=1)
         loc.append(lo.permute(0, 2, 3, 1).reshape(lo.shape[0], -1))
         conf.append(co.permute(0, 2, 3, 1).reshape(co.shape[0], -1))
-    taps["loc"] = torch.cat(loc, 1).view(x.shape[0], -1, 4)
-    taps["conf"] = torch.cat(conf, 1).view(x.shape[0], -1, 2)
-    taps["maps"] = [tuple(s.shape[2:]) for s in sources]
+        maps.append(tuple(s.shape[2:]))
+    b = loc[0].shape[0]
+    return torch.cat(loc, 1).view(b, -1, 4), torch.cat(conf, 1).view(b, -1, 2), maps
+
+
+def network(sd, x, dtype=torch.float64):
+    """x [B,3,H,W] (mean subtracted) -> {stage: NCHW tensor, "loc": [B,P,4], "conf": [B,P,2] logits after the max-out}: the nine
+    segments in a row, then the heads"""
+    taps, start = {}, None
+    for _ in _TAPS:
+        start, x = segment(sd, x, start, dtype)
+        taps[start] = x
+    taps["loc"], taps["conf"], taps["maps"] = heads(sd, taps, dtype)
     return taps
 
 

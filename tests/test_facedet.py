@@ -102,6 +102,73 @@ def test_map_sizes_and_workspace_agree_with_the_library():
     assert lib.casync_s3fd_workspace_bytes(0, H, W) == 0 and lib.casync_s3fd_workspace_bytes(1, 9000, 64) == 0
 
 
+# ---- the restatement in segments ---------------------------------------------------------------------------------------------
+def _network_in_one_pass(sd, x, dtype):
+    """S3FDNet.forward written out in one piece (nets.py:109-171), as tests/s3fd_ref.py had it before it was cut into segments:
+    what segment() and heads() must compose to"""
+    F = torch.nn.functional
+    p = {k: torch.as_tensor(np.asarray(v)).to(dtype) for k, v in sd.items()}
+    x = torch.as_tensor(x).to(dtype)
+    taps, sources = {}, []
+    for idx, name, _cin, _cout, k in facedet.VGG:
+        kw = dict(padding=6, dilation=6) if name == "fc6" else dict(padding=k // 2)
+        x = F.relu(F.conv2d(x, p[f"vgg.{idx}.weight"], p[f"vgg.{idx}.bias"], **kw))
+        if idx in s3fd_ref.STAGE_AFTER:
+            taps[s3fd_ref.STAGE_AFTER[idx]] = x
+        if idx in (14, 21, 28):
+            norm = x.pow(2).sum(dim=1, keepdim=True).sqrt() + 1e-10
+            sources.append(p[f"{facedet.L2NORMS[len(sources)][0]}.weight"].view(1, -1, 1, 1) * torch.div(x, norm))
+        if idx in s3fd_ref.POOLS:
+            x = F.max_pool2d(x, 2, 2, ceil_mode=s3fd_ref.POOLS[idx])
+    sources.append(x)
+    for idx, name, _cin, _cout, k in facedet.EXTRAS:
+        x = F.relu(F.conv2d(x, p[f"extras.{idx}.weight"], p[f"extras.{idx}.bias"], stride=2 if k == 3 else 1, padding=k // 2))
+        if k == 3:
+            taps[name] = x
+            sources.append(x)
+    loc, conf = [], []
+    for k, s in enumerate(sources):
+        lo = F.conv2d(s, p[f"loc.{k}.weight"], p[f"loc.{k}.bias"], padding=1)
+        co = F.conv2d(s, p[f"conf.{k}.weight"], p[f"conf.{k}.bias"], padding=1)
+        if k == 0:
+            co = torch.cat((co[:, 0:3].max(dim=1, keepdim=True)[0], co[:, 3:]), dim=1)
+        loc.append(lo.permute(0, 2, 3, 1).reshape(lo.shape[0], -1))
+        conf.append(co.permute(0, 2, 3, 1).reshape(co.shape[0], -1))
+    taps["loc"] = torch.cat(loc, 1).view(x.shape[0], -1, 4)
+    taps["conf"] = torch.cat(conf, 1).view(x.shape[0], -1, 2)
+    taps["maps"] = [tuple(s.shape[2:]) for s in sources]
+    return taps
+
+
+@pytest.mark.parametrize("h,w", [(H, W), (141, 86)])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_the_segments_and_the_heads_compose_to_the_network_bit_for_bit(sd, fx, h, w, dtype):
+    u8 = recipe.make_s3fd_inputs(2, h, w) if (h, w) == (H, W) else recipe.make_s3fd_inputs(1, h, w, seed=recipe.S3FD_INPUT_SEED + 1)
+    x = torch.from_numpy((u8.astype(np.float32) - facedet.IMG_MEAN).transpose(0, 3, 1, 2).copy())
+    want = _network_in_one_pass(sd, x, dtype)
+    assert want["maps"] == facedet.map_sizes(h, w)
+    chained, start, t = {}, None, x
+    for k in range(9):
+        name, t = s3fd_ref.segment(sd, t, start, dtype)
+        assert name == facedet.STAGES[k] and t.dtype == dtype
+        chained[name], start = t, name
+    for k, name in enumerate(facedet.STAGES[:9]):
+        assert torch.equal(chained[name], want[name]), name
+        if k:                                                # ... and each segment alone, started by index from the tap in front
+            again, u = s3fd_ref.segment(sd, want[facedet.STAGES[k - 1]], k - 1, dtype)
+            assert again == name and torch.equal(u, want[name]), name
+    loc, conf, maps = s3fd_ref.heads(sd, [chained[n] for n in s3fd_ref.SOURCES], dtype)
+    assert maps == want["maps"] and torch.equal(loc, want["loc"]) and torch.equal(conf, want["conf"])
+    whole = s3fd_ref.network(sd, x, dtype)
+    assert set(whole) == set(want) and whole["maps"] == want["maps"]
+    assert all(torch.equal(whole[n], want[n]) for n in want if n != "maps")
+    with pytest.raises(ValueError, match="no tap behind"):
+        s3fd_ref.segment(sd, t, "conv7_2", dtype)
+    if (h, w) == (H, W) and dtype == torch.float64:          # the pieces are the reference: its own float64 forward of these frames
+        assert np.abs(loc.numpy() - fx["loc64"]).max() <= 1e-11 and np.abs(conf.numpy() - fx["conf64"]).max() <= 1e-11
+        assert np.abs(s3fd_ref.dense(whole, h, w).numpy() - fx["det64"]).max() <= 1e-12
+
+
 # ---- post-processing on the fixture: bit for bit ----------------------------------------------------------------------------
 class _Dense:
     """stands in for the engine: forward_u8 returns prepared dense outputs in turn"""
