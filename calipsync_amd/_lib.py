@@ -222,6 +222,11 @@ _PROTOS = {
     "casync_op_jpeg420_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int, c_i64]),
     "casync_op_jpeg420_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    # baseline JPEG files -> frames (additive to ABI 13); rec is HOST memory, [batch][16] int32 (include/casync_hip.h), data holds the
+    # files' scans, segment lists and table blocks on the device, status int32 [batch] on the device
+    "casync_op_jpegdec_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int, C.c_int, c_i64]),
+    "casync_op_jpegdec_decode": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -61,7 +61,7 @@ class FrameSynthesizer:
     def __init__(self, unet_checkpoint: Optional[str], data_dir: Optional[str], device: str = "cuda:0", batch_size: int = 8, *,
                  seed: Optional[int] = None, precision: str = "fp32", net: Optional[Model] = None,
                  batches_in_flight: Optional[int] = None, resident: Optional[bool] = None, clip=None, output: str = "frames",
-                 jpeg_quality: int = 95, jpeg_subsampling="4:4:4"):
+                 jpeg_quality: int = 95, jpeg_subsampling="4:4:4", clip_decode: str = "host"):
         """Same positional arguments as the reference (infer_api.py:13-14).  Keyword-only extensions:
         ``seed`` (reproducible frame walk), ``precision`` (engine storage type), ``net`` (an already
         loaded ``Model`` instead of a checkpoint path), ``batches_in_flight`` (default 1, or the
@@ -76,6 +76,8 @@ class FrameSynthesizer:
         (``resident_clip.ResidentClip``): ``data_dir`` is read once, on the first ``iterate_synthesized_frames``, and a batch
         sends only its records up; the frames yielded are those of ``resident=False`` byte for byte.  ``clip``: a
         ``ResidentClip`` made elsewhere (``from_frames``: no directory at all); ``data_dir`` may then be None.
+        ``clip_decode`` ("host", the default, or "device"; the resident path only): who decodes the directory's .jpg frames on
+        that first call, passed to ``ResidentClip.from_data_dir(decode=...)``.
 
         ``output`` ("frames", the default, or "jpeg"; "jpeg" needs the resident path): the items of
         ``iterate_synthesized_frames`` carry ``'jpeg'``, the frame as a complete baseline JPEG file of ``jpeg_quality``
@@ -97,7 +99,11 @@ class FrameSynthesizer:
             jpeg.quant_tables(jpeg_quality)         # ValueError for a quality outside 1..100
             jpeg._subsampling(jpeg_subsampling)     # ValueError for anything but 4:4:4 / 0 and 4:2:0 / 2
         self.output, self.jpeg_quality, self.jpeg_subsampling = output, int(jpeg_quality), jpeg_subsampling
-        self.resident, self._clip = bool(resident), clip
+        if clip_decode not in ("host", "device"):
+            raise ValueError(f"clip_decode {clip_decode!r} is neither 'host' nor 'device'")
+        if clip_decode == "device" and not resident:
+            raise ValueError("clip_decode='device' decodes into the resident clip: it needs resident=True")
+        self.resident, self._clip, self.clip_decode = bool(resident), clip, clip_decode
         if batches_in_flight is None:
             batches_in_flight = int(os.environ.get("CASYNC_BATCHES_IN_FLIGHT", "1"))
         if batches_in_flight < 0:
@@ -233,7 +239,7 @@ class FrameSynthesizer:
             if self.resident and self._clip is None and total_frames:
                 from .resident_clip import ResidentClip
                 t0 = time.time()   # the whole directory, once: kept for the life of this object
-                self._clip = ResidentClip.from_data_dir(self.data_dir, self.device, io_workers=self.batch_size)
+                self._clip = ResidentClip.from_data_dir(self.data_dir, self.device, io_workers=self.batch_size, decode=self.clip_decode)
                 time_stats["load_frame"] += time.time() - t0
             for batch_start in range(0, total_frames, self.batch_size):
                 try:

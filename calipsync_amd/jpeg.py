@@ -13,7 +13,12 @@ DESIGN.md section 8i): Y sampled 2 x 2, Cb and Cr averaged 2 x 2, one restart in
 Pillow's ``subsampling=2``.  4:4:4 stays the default.
 
 The restart markers make the block rows independent: the device encodes one row per wave.  The host twin is the fallback for
-a frame whose row outgrew its scratch slot, the subject of the CPU tests and the yardstick for inputs without a fixture."""
+a frame whose row outgrew its scratch slot, the subject of the CPU tests and the yardstick for inputs without a fixture.
+
+The way back, baseline JPEG files -> frames (csrc/jpeg_dec.hip), is the second half of this file:
+
+    frames_dev = decode_jpeg_device(files)                 # B files of one size -> [B,H,W,3] uint8 BGR on the device
+    frame_bgr = decode_jpeg_host(data)                     # the same bytes from numpy: Pillow's, reversed to BGR"""
 from __future__ import annotations
 
 import ctypes as C
@@ -469,3 +474,714 @@ def encode_jpeg_device(frames, quality: int = 95, *, subsampling="4:4:4", slot_b
             frame_loop._release_pinned(meta_host)
             if data_host is not None:
                 frame_loop._release_pinned(data_host)
+
+
+# ================================================================================================================ decoding
+# Baseline JPEG -> pixels, byte for byte libjpeg's default path (islow IDCT, fancy upsampling, 16-bit fixed-point colour):
+# csrc/jpeg_dec.hip on the device, the numpy twin here.  The entropy stage of the device cuts each restart
+# segment into subsequences of chunk_bits bits and finds every subsequence's entry state by a fixed-point iteration;
+# sync_states() below is the host model of exactly that rule.
+DEFAULT_CHUNK_BITS = 2048           # the fastest of 256 / 512 / 1024 / 2048 on 1080p files (tools/jpeg_decode_bench.py)
+TAB_BYTES = 384 + 8 + 4 * 832     # the per-frame table block of the device (see _device_tables)
+MAX_SUBSEQUENCES = 1 << 17        # per frame: what casync_op_jpegdec_decode admits (the plan's rounds are bounded by this number)
+REC_WORDS = 16
+
+
+class JpegUnsupported(ValueError):
+    """The file is outside the subset the decoder reads (parse_jpeg names the reason)"""
+
+
+class JpegUnreadable(ValueError):
+    """decode_jpeg_device: file .index is outside the subset and the host decoder cannot read it either"""
+
+    def __init__(self, index: int, what: str):
+        super().__init__(what)
+        self.index = int(index)
+
+
+class JpegCorrupt(ValueError):
+    """The scan of a file inside the subset broke a rule; .status is the device's code: 1 invalid code or coefficient overrun,
+    2 the scan ended before the last MCU, 3 more data than MCUs in a segment"""
+
+    def __init__(self, status: int, what: str):
+        super().__init__(what)
+        self.status = int(status)
+
+
+class JpegInfo:
+    """What parse_jpeg reads from the headers.  H, W; subsampling 0 (4:4:4) or 2 (4:2:0); qtables: per component int32 [64] in
+    zigzag order; dc_tables / ac_tables: per component (bits[16], vals) as the scan selects them; dc_sel / ac_sel: the table
+    ids (0 / 1); restart_interval in MCUs (0: none); scan_offset, scan_length: the entropy-coded bytes, markers included;
+    restart_offsets: byte offsets in the file of every RSTn marker."""
+    __slots__ = ("H", "W", "subsampling", "qtables", "dc_tables", "ac_tables", "dc_sel", "ac_sel", "restart_interval", "scan_offset",
+                 "scan_length", "restart_offsets")
+
+    @property
+    def blocks_per_mcu(self) -> int:
+        return 6 if self.subsampling else 3
+
+    @property
+    def mcu_grid(self):
+        """(MCU rows, MCUs per row)"""
+        s = 16 if self.subsampling else 8
+        return (self.H + s - 1) // s, (self.W + s - 1) // s
+
+    def segments(self):
+        """[(start, end)] of the restart segments, byte offsets relative to the scan's first byte, markers excluded"""
+        cuts = [int(o) - self.scan_offset for o in self.restart_offsets]
+        starts = [0] + [c + 2 for c in cuts]
+        return list(zip(starts, cuts + [self.scan_length]))
+
+    def expected_segments(self) -> int:
+        rows, cols = self.mcu_grid
+        n = rows * cols
+        return (n + self.restart_interval - 1) // self.restart_interval if self.restart_interval else 1
+
+
+def _huff_ok(bits, vals) -> bool:
+    code = 0
+    for length in range(1, 17):
+        code += bits[length - 1]
+        if code > (1 << length):
+            return False
+        code <<= 1
+    return sum(bits) == len(vals) and len(vals) <= 256
+
+
+def parse_jpeg(data) -> JpegInfo:
+    """The headers of a baseline file of the supported subset (SOF0, 8 bits, three components sampled 1x1 or 2x2 / 1x1 / 1x1, one
+    interleaved scan, 8-bit quantisation tables, Huffman tables 0 and 1, any restart interval); JpegUnsupported otherwise."""
+    data = bytes(data)
+    n = len(data)
+    if n < 4 or data[:2] != b"\xff\xd8":
+        raise JpegUnsupported("jpeg: not a JPEG file (no SOI)")
+    ended = JpegUnsupported("jpeg: the file ends inside its headers")
+    qt, huff, frame, ri, pos, adobe = {}, {}, None, 0, 2, 1
+    while True:
+        if pos + 4 > n:
+            raise ended
+        if data[pos] != 0xFF:
+            raise JpegUnsupported(f"jpeg: no marker at byte {pos}")
+        m = data[pos + 1]
+        if m == 0xFF:
+            pos += 1
+            continue
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            pos += 2
+            continue
+        if m == 0xD9:
+            raise ended
+        length = struct.unpack(">H", data[pos + 2:pos + 4])[0]
+        if length < 2 or pos + 2 + length > n:
+            raise ended
+        body = data[pos + 4:pos + 2 + length]
+        pos += 2 + length
+        if m == 0xC0:
+            if frame is not None:
+                raise JpegUnsupported("jpeg: several frames")
+            if len(body) < 6 or len(body) < 6 + 3 * body[5]:
+                raise JpegUnsupported("jpeg: a short SOF segment")
+            if body[0] != 8:
+                raise JpegUnsupported(f"jpeg: {body[0]}-bit samples")
+            H, W = struct.unpack(">HH", body[1:5])
+            nf = body[5]
+            if nf == 1:
+                raise JpegUnsupported("jpeg: a grayscale file")
+            if nf == 4:
+                raise JpegUnsupported("jpeg: a four-component (CMYK) file")
+            if nf != 3:
+                raise JpegUnsupported(f"jpeg: {nf} components")
+            if H < 1 or W < 1:
+                raise JpegUnsupported("jpeg: a frame without a size (DNL)")
+            comps = [(body[6 + 3 * i], body[7 + 3 * i], body[8 + 3 * i]) for i in range(3)]
+            samp = tuple(c[1] for c in comps)
+            if samp == (0x11, 0x11, 0x11):
+                sub = 0
+            elif samp == (0x22, 0x11, 0x11):
+                sub = 2
+            else:
+                raise JpegUnsupported("jpeg: chroma sampling other than 4:4:4 and 4:2:0 (" + ", ".join(f"{s >> 4}x{s & 15}" for s in samp) + ")")
+            frame = (H, W, sub, comps)
+        elif m in (0xC1, 0xC2, 0xC3, 0xC5, 0xC6, 0xC7, 0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF, 0xCC):
+            what = {0xC2: "a progressive file", 0xC1: "an extended sequential file", 0xC3: "a lossless file"}.get(
+                m, "arithmetic coding" if m >= 0xC9 else f"frame type SOF{m - 0xC0}")
+            raise JpegUnsupported(f"jpeg: {what}")
+        elif m == 0xC4:
+            at = 0
+            while at < len(body):
+                if at + 17 > len(body):
+                    raise JpegUnsupported("jpeg: a short DHT segment")
+                tc, th = body[at] >> 4, body[at] & 15
+                bits = tuple(body[at + 1:at + 17])
+                vals = bytes(body[at + 17:at + 17 + sum(bits)])
+                if tc > 1 or not _huff_ok(bits, vals):
+                    raise JpegUnsupported("jpeg: a Huffman table that is no prefix code")
+                huff[(tc, th)] = (bits, vals)
+                at += 17 + sum(bits)
+        elif m == 0xDB:
+            at = 0
+            while at < len(body):
+                pq, tq = body[at] >> 4, body[at] & 15
+                if pq:
+                    raise JpegUnsupported("jpeg: a 16-bit quantisation table")
+                if at + 65 > len(body):
+                    raise JpegUnsupported("jpeg: a short DQT segment")
+                qt[tq] = np.frombuffer(body[at + 1:at + 65], dtype=np.uint8).astype(np.int32)
+                at += 65
+        elif m == 0xDD:
+            if len(body) < 2:
+                raise JpegUnsupported("jpeg: a short DRI segment")
+            ri = struct.unpack(">H", body[:2])[0]
+        elif m == 0xEE:
+            if body[:5] == b"Adobe" and len(body) >= 12:
+                adobe = body[11]                                 # judged at the scan: a CMYK file is named as that
+        elif m == 0xDA:
+            if frame is None:
+                raise JpegUnsupported("jpeg: a scan ahead of the frame header")
+            H, W, sub, comps = frame
+            if adobe != 1:
+                raise JpegUnsupported(f"jpeg: Adobe colour transform {adobe}, not YCbCr")
+            if len(body) < 1 or body[0] != 3 or len(body) < 10:
+                raise JpegUnsupported("jpeg: a scan that does not interleave the three components (several scans)")
+            sel = [(body[1 + 2 * i], body[2 + 2 * i]) for i in range(3)]
+            if [s[0] for s in sel] != [c[0] for c in comps]:
+                raise JpegUnsupported("jpeg: scan components out of frame order")
+            if tuple(body[7:10]) != (0, 63, 0):
+                raise JpegUnsupported("jpeg: a scan with spectral selection or successive approximation")
+            break
+        # every other segment (APPn, COM, ...) is skipped
+    info = JpegInfo()
+    info.H, info.W, info.subsampling = H, W, sub
+    info.dc_sel, info.ac_sel = tuple(s[1] >> 4 for s in sel), tuple(s[1] & 15 for s in sel)
+    if max(info.dc_sel + info.ac_sel) > 1:
+        raise JpegUnsupported("jpeg: a Huffman table id above 1")
+    try:
+        info.qtables = [qt[c[2]] for c in comps]
+        info.dc_tables = [huff[(0, t)] for t in info.dc_sel]
+        info.ac_tables = [huff[(1, t)] for t in info.ac_sel]
+    except KeyError as exc:
+        raise JpegUnsupported(f"jpeg: the scan names a table the file does not define ({exc.args[0]})") from None
+    info.restart_interval = int(ri)
+    info.scan_offset = pos
+    scan = np.frombuffer(data, dtype=np.uint8, offset=pos)
+    ff = np.nonzero(scan[:-1] == 0xFF)[0] if scan.size > 1 else np.zeros(0, dtype=np.int64)
+    nxt = scan[ff + 1]
+    rst = (nxt >= 0xD0) & (nxt <= 0xD7)
+    other = ff[(nxt != 0) & ~rst]
+    end = int(other[0]) if other.size else int(scan.size)          # no marker behind the scan: it runs to the end of the file
+    if other.size and b"\xff\xda" in data[pos + end:]:
+        raise JpegUnsupported("jpeg: several scans")
+    info.scan_length = end
+    marks = ff[rst]
+    info.restart_offsets = (marks[marks < end] + pos).astype(np.int64)
+    return info
+
+
+def _lut16(bits, vals) -> np.ndarray:
+    """the next 16 bits -> length << 8 | symbol (0: no code)"""
+    lut = np.zeros(65536, dtype=np.int32)
+    code, k = 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            lo = code << (16 - length)
+            lut[lo:lo + (1 << (16 - length))] = (length << 8) | vals[k]
+            code += 1
+            k += 1
+        code <<= 1
+    return lut
+
+
+class _Segment:
+    """One restart segment, unstuffed, with the maps between bit positions of the stuffed stream (relative to the scan's first
+    byte; byte k of a segment is stuffing iff it is 0x00 behind 0xFF, a position never lies in one; bytes past the segment's end
+    read as zero) and of the unstuffed one."""
+
+    def __init__(self, scan: bytes, start: int, end: int):
+        sb = scan[start:end]
+        a = np.frombuffer(sb, dtype=np.uint8)
+        stuff = np.zeros(a.size, dtype=bool)
+        if a.size > 1:
+            stuff[1:] = (a[1:] == 0) & (a[:-1] == 0xFF)
+        self.start, self.n_s = start, a.size
+        self.stuff = stuff
+        self.didx = np.nonzero(~stuff)[0]
+        self.cum = np.cumsum(~stuff) - 1
+        self.n_u = int(self.didx.size)
+        self.u = a[~stuff].tobytes() + b"\0" * 16
+        self.end_bits = end * 8
+
+    def to_u(self, p: int) -> int:
+        p -= self.start * 8
+        k, o = p >> 3, p & 7
+        if k < self.n_s and self.stuff[k]:
+            k, o = k + 1, 0
+        if k >= self.n_s:
+            return (self.n_u + k - self.n_s) * 8 + o
+        return int(self.cum[k]) * 8 + o
+
+    def to_s(self, q: int) -> int:
+        k, o = q >> 3, q & 7
+        k = self.n_s + k - self.n_u if k >= self.n_u else int(self.didx[k])
+        return (self.start + k) * 8 + o
+
+
+class _Scan:
+    """The tables of a file's scan in the form the symbol loop wants"""
+
+    def __init__(self, info: JpegInfo, data: bytes):
+        self.info = info
+        self.scan = bytes(data[info.scan_offset:info.scan_offset + info.scan_length])
+        self.bpm = info.blocks_per_mcu
+        self.comp = Y420 if info.subsampling else (0, 1, 2)
+        self.dc = [_lut16(*t).tolist() for t in info.dc_tables]
+        self.ac = [_lut16(*t).tolist() for t in info.ac_tables]
+        rows, cols = info.mcu_grid
+        self.n_mcu = rows * cols
+        self.ri = info.restart_interval or self.n_mcu
+        self.segs = info.segments()
+
+    def seg_blocks(self, j: int) -> int:
+        """blocks the geometry gives segment j"""
+        return max(0, min(self.ri, self.n_mcu - j * self.ri)) * self.bpm
+
+    def run(self, seg: _Segment, q: int, s: int, z: int, end_q: int, out=None, block0: int = 0, cap: int = 0, pred=None):
+        """Decode the symbols that start at unstuffed bit positions q <= .. < end_q from state (slot s, zigzag index z).
+        -> (q, s, z, blocks finished, blocks finished ahead of an invalid code or -1, DC difference sums [3]).  out
+        [blocks, 64] (zigzag order) takes the coefficients of blocks block0 + 0 .. below block0 + cap, DC as values from pred."""
+        u, bpm, comp = seg.u, self.bpm, self.comp
+        n, dcs = 0, [0, 0, 0]
+        while q < end_q:
+            k, o = q >> 3, q & 7
+            w = (int.from_bytes(u[k:k + 5], "big") >> (8 - o)) & 0xFFFFFFFF
+            c = comp[s]
+            done = False
+            if z == 0:
+                e = self.dc[c][w >> 16]
+                ln, cat = e >> 8, e & 0xFF
+                if ln == 0 or cat > 11:
+                    return -1, 0, 0, n, n, dcs
+                v = 0
+                if cat:
+                    v = (w >> (32 - ln - cat)) & ((1 << cat) - 1)
+                    if v < (1 << (cat - 1)):
+                        v -= (1 << cat) - 1
+                dcs[c] += v
+                if out is not None and n < cap:
+                    pred[c] += v
+                    out[block0 + n, 0] = pred[c]
+                z = 1
+                q += ln + cat
+            else:
+                e = self.ac[c][w >> 16]
+                ln, sym = e >> 8, e & 0xFF
+                if ln == 0:
+                    return -1, 0, 0, n, n, dcs
+                r, cat = sym >> 4, sym & 15
+                if cat == 0:
+                    if r == 15:
+                        z += 16
+                        if z > 64:
+                            return -1, 0, 0, n, n, dcs
+                        done = z == 64
+                    else:
+                        done = True
+                else:
+                    z += r
+                    if z > 63:
+                        return -1, 0, 0, n, n, dcs
+                    v = (w >> (32 - ln - cat)) & ((1 << cat) - 1)
+                    if v < (1 << (cat - 1)):
+                        v -= (1 << cat) - 1
+                    if out is not None and n < cap:
+                        out[block0 + n, z] = v
+                    z += 1
+                    done = z == 64
+                q += ln + cat
+            if done:
+                z, s, n = 0, (s + 1) % bpm, n + 1
+        return q, s, z, n, -1, dcs
+
+
+def _segment_status(n: int, err_n: int, want: int) -> int:
+    if 0 <= err_n < want:
+        return 1
+    return 2 if n < want else 3 if n > want else 0
+
+
+def _decode_scan(info: JpegInfo, data: bytes):
+    """(coefficients [blocks, 64] int32 in zigzag order, stream order, DC as values; status)"""
+    sc = _Scan(info, data)
+    coef = np.zeros((sc.n_mcu * sc.bpm, 64), dtype=np.int32)
+    if len(sc.segs) != info.expected_segments():
+        return coef, 2 if len(sc.segs) < info.expected_segments() else 3
+    status = 0
+    for j, (a, b) in enumerate(sc.segs):
+        seg = _Segment(sc.scan, a, b)
+        want = sc.seg_blocks(j)
+        _, _, _, n, err_n, _ = sc.run(seg, 0, 0, 0, seg.n_u * 8, coef, j * sc.ri * sc.bpm, want, [0, 0, 0])
+        if status == 0:
+            status = _segment_status(n, err_n, want)
+    return coef, status
+
+
+def scan_status(data) -> int:
+    """The status the device gives a file of the subset: 0, or the code of the first restart segment that breaks a rule"""
+    return _decode_scan(parse_jpeg(data), bytes(data))[1]
+
+
+def _idct_pass(c, shift: int):
+    """One pass of libjpeg's accurate integer inverse DCT (jidctint) along the last axis of c [..., 8] (int64)"""
+    z1 = (c[..., 2] + c[..., 6]) * 4433
+    t2, t3 = z1 - c[..., 6] * 15137, z1 + c[..., 2] * 6270
+    t0, t1 = (c[..., 0] + c[..., 4]) << 13, (c[..., 0] - c[..., 4]) << 13
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    t0, t1, t2, t3 = c[..., 7], c[..., 5], c[..., 3], c[..., 1]
+    z1, z2, z3, z4 = t0 + t3, t1 + t2, t0 + t2, t1 + t3
+    z5 = (z3 + z4) * 9633
+    t0, t1, t2, t3 = t0 * 2446, t1 * 16819, t2 * 25172, t3 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
+    out = np.empty_like(c)
+    for i, v in enumerate((t10 + t3, t11 + t2, t12 + t1, t13 + t0, t13 - t0, t12 - t1, t11 - t2, t10 - t3)):
+        out[..., i] = _descale(v, shift)
+    return out
+
+
+def _idct_blocks(coef_zz: np.ndarray, q_zz: np.ndarray) -> np.ndarray:
+    """[n, 64] coefficients and [64] table, both in zigzag order -> [n, 8, 8] samples 0..255"""
+    nat = np.zeros(coef_zz.shape, dtype=np.int64)
+    nat[:, list(ZIGZAG)] = coef_zz.astype(np.int64) * q_zz.astype(np.int64)
+    b = nat.reshape(-1, 8, 8)
+    b = _idct_pass(np.ascontiguousarray(b.swapaxes(-1, -2)), 11).swapaxes(-1, -2)      # columns first
+    b = _idct_pass(np.ascontiguousarray(b), 18)                                          # then rows
+    return np.clip(b + 128, 0, 255)
+
+
+def _upsample_h2v2(c: np.ndarray, H: int, W: int) -> np.ndarray:
+    """libjpeg's h2v2_fancy_upsample of the real downsampled plane c [ceil(H/2), ceil(W/2)] -> [H, W]"""
+    ch, cw = c.shape
+    near = np.repeat(np.arange(ch), 2)
+    far = np.clip(near + np.where(np.arange(2 * ch) % 2, 1, -1), 0, ch - 1)
+    s = 3 * c[near] + c[far]                                                             # [2 ch, cw]
+    left = np.concatenate([s[:, :1], s[:, :-1]], axis=1)
+    right = np.concatenate([s[:, 1:], s[:, -1:]], axis=1)
+    out = np.empty((2 * ch, 2 * cw), dtype=np.int64)
+    out[:, 0::2] = (3 * s + left + 8) >> 4
+    out[:, 1::2] = (3 * s + right + 7) >> 4
+    return out[:H, :W]
+
+
+def _pixels(info: JpegInfo, coef: np.ndarray) -> np.ndarray:
+    """coefficients [blocks, 64] (zigzag order, stream order) -> BGR uint8 [H, W, 3]"""
+    H, W = info.H, info.W
+    rows, cols = info.mcu_grid
+    bpm = info.blocks_per_mcu
+    coef = coef.reshape(rows, cols, bpm, 64)
+    if info.subsampling:
+        y = _idct_blocks(coef[:, :, :4].reshape(-1, 64), info.qtables[0]).reshape(rows, cols, 2, 2, 8, 8)
+        y = y.transpose(0, 2, 4, 1, 3, 5).reshape(rows * 16, cols * 16)[:H, :W]
+        planes = [y]
+        for c in (1, 2):
+            p = _idct_blocks(coef[:, :, 3 + c].reshape(-1, 64), info.qtables[c]).reshape(rows, cols, 8, 8)
+            p = p.transpose(0, 2, 1, 3).reshape(rows * 8, cols * 8)[:(H + 1) // 2, :(W + 1) // 2]
+            planes.append(_upsample_h2v2(p, H, W))
+    else:
+        planes = []
+        for c in range(3):
+            p = _idct_blocks(coef[:, :, c].reshape(-1, 64), info.qtables[c]).reshape(rows, cols, 8, 8)
+            planes.append(p.transpose(0, 2, 1, 3).reshape(rows * 8, cols * 8)[:H, :W])
+    y, cb, cr = planes[0], planes[1] - 128, planes[2] - 128
+    r = y + ((91881 * cr + 32768) >> 16)
+    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
+    b = y + ((116130 * cb + 32768) >> 16)
+    return np.clip(np.stack([b, g, r], axis=-1), 0, 255).astype(np.uint8)
+
+
+def decode_jpeg_host(data) -> np.ndarray:
+    """A baseline JPEG file of the subset -> BGR uint8 [H, W, 3], the numpy twin of the device decoder: the bytes of Pillow's
+    ``Image.open(...).convert("RGB")``, reversed to BGR.  JpegUnsupported for a file outside the subset, JpegCorrupt (with the
+    device's status code) for a scan that breaks a rule."""
+    data = bytes(data)
+    info = parse_jpeg(data)
+    coef, status = _decode_scan(info, data)
+    if status:
+        raise JpegCorrupt(status, f"jpeg: the scan is damaged (status {status})")
+    return _pixels(info, coef)
+
+
+def _chunk_bits(chunk_bits: int) -> int:
+    c = int(chunk_bits) or DEFAULT_CHUNK_BITS
+    if c < 32 or c % 32 or c > (1 << 30):
+        raise ValueError(f"jpeg: chunk_bits {chunk_bits} is not a multiple of 32 in 32..2^30")
+    return c
+
+
+def _subsequences(segs, chunk: int):
+    """subsequences of each segment [(start, end)] (bytes): max(1, ceil(bits / chunk))"""
+    return [max(1, -(-(b - a) * 8 // chunk)) for a, b in segs]
+
+
+class SyncResult:
+    """states [S, 3] int64: the entry state (bit position in the stuffed scan, block slot of the MCU, zigzag index) of every
+    subsequence, segment after segment; segment [S]; rounds [S]: the round after which the state last changed (0: it was known or
+    guessed right); total_rounds: decoding rounds run"""
+    __slots__ = ("states", "segment", "rounds", "total_rounds")
+
+
+def _boundaries(sc: _Scan, chunk: int):
+    """(segment objects, [(segment index, k, end bit)] per subsequence)"""
+    segs = [_Segment(sc.scan, a, b) for a, b in sc.segs]
+    subs = []
+    for j, (n, seg) in enumerate(zip(_subsequences(sc.segs, chunk), segs)):
+        for k in range(n):
+            end = seg.end_bits if k == n - 1 else min(seg.start * 8 + (k + 1) * chunk, seg.end_bits)
+            subs.append((j, k, end))
+    return segs, subs
+
+
+def sync_states(info: JpegInfo, data, chunk_bits: int = 0) -> SyncResult:
+    """The host model of the device's entropy plan.  Every restart segment is cut into subsequences of chunk_bits bits of the
+    stuffed stream.  The first of a segment starts in the known state, every other from the guess (its first bit, slot 0, zigzag
+    0).  A round decodes every subsequence whose entry state changed; the exit state of one is the entry state of the next.  The
+    rounds end when no entry state changes: subsequence k of a segment is right after at most k rounds.  A subsequence that meets
+    an invalid code hands the guess to the next one, so a wrong guess that runs into one does not spoil what follows it (the
+    frame's status comes from the first invalid code of a segment, which no later state changes)."""
+    chunk = _chunk_bits(chunk_bits)
+    sc = _Scan(info, bytes(data))
+    segs, subs = _boundaries(sc, chunk)
+    S = len(subs)
+    entry = []
+    for j, k, _ in subs:
+        seg = segs[j]
+        entry.append((seg.to_s(seg.to_u(min(seg.start * 8 + k * chunk, seg.end_bits))), 0, 0))     # to_s(to_u()) steps over a stuffed byte
+    exits = [None] * S
+    rounds = [0] * S
+    changed = list(range(S))
+    total = 0
+    while changed:
+        total += 1
+        for g in changed:
+            j, k, end = subs[g]
+            p, s, z = entry[g]
+            seg = segs[j]
+            q, s, z, _, _, _ = sc.run(seg, seg.to_u(p), s, z, seg.to_u(end))
+            exits[g] = (seg.to_s(seg.to_u(end)), 0, 0) if q < 0 else (seg.to_s(q), s, z)
+        nxt = []
+        for g in changed:
+            if g + 1 < S and subs[g + 1][0] == subs[g][0] and entry[g + 1] != exits[g]:
+                entry[g + 1] = exits[g]
+                rounds[g + 1] = total
+                nxt.append(g + 1)
+        changed = nxt
+    res = SyncResult()
+    res.states = np.asarray(entry, dtype=np.int64).reshape(S, 3)
+    res.segment = np.asarray([j for j, _, _ in subs], dtype=np.int64)
+    res.rounds = np.asarray(rounds, dtype=np.int64)
+    res.total_rounds = total
+    return res
+
+
+def serial_states(info: JpegInfo, data, chunk_bits: int = 0) -> np.ndarray:
+    """[S, 3]: the state of a plain serial decoder where it crosses into each subsequence of sync_states' cut (behind an invalid
+    code it goes on from the next boundary's guess)"""
+    chunk = _chunk_bits(chunk_bits)
+    sc = _Scan(info, bytes(data))
+    segs, subs = _boundaries(sc, chunk)
+    out, state = [], None
+    for j, k, end in subs:
+        seg = segs[j]
+        if k == 0:
+            state = (seg.start * 8, 0, 0)
+        out.append(state)
+        q, s, z, _, _, _ = sc.run(seg, seg.to_u(state[0]), state[1], state[2], seg.to_u(end))
+        state = (seg.to_s(seg.to_u(end)), 0, 0) if q < 0 else (seg.to_s(q), s, z)
+    return np.asarray(out, dtype=np.int64).reshape(len(subs), 3)
+
+
+# ---------------------------------------------------------------------------------------------------------------- device
+def _device_huffman(bits, vals) -> bytes:
+    """832 bytes: lut [256] u16 (length << 8 | symbol for codes of up to 8 bits) | maxcode [8] int32 of lengths 9..16 (-1: none) |
+    valoff [8] int32 (index of the length's first symbol minus its first code) | the symbols, padded to 256"""
+    lut = np.zeros(256, dtype=np.uint16)
+    maxcode = np.full(8, -1, dtype=np.int32)
+    valoff = np.zeros(8, dtype=np.int32)
+    code, k = 0, 0
+    for length in range(1, 17):
+        n = bits[length - 1]
+        if n and length <= 8:
+            for i in range(n):
+                lo = (code + i) << (8 - length)
+                lut[lo:lo + (1 << (8 - length))] = (length << 8) | vals[k + i]
+        elif n:
+            maxcode[length - 9] = code + n - 1
+            valoff[length - 9] = k - code
+        code = (code + n) << 1
+        k += n
+    return lut.tobytes() + maxcode.tobytes() + valoff.tobytes() + bytes(vals) + b"\0" * (256 - len(vals))
+
+
+def _device_tables(info: JpegInfo) -> bytes:
+    """The table block of one frame, TAB_BYTES: quantisation [3][64] u16 in natural order | the DC table (0 / 1) of each component,
+    0 | the AC table of each, 0 | the Huffman tables DC 0, DC 1, AC 0, AC 1 (zeros where the file has none)"""
+    q = np.zeros((3, 64), dtype=np.uint16)
+    for c in range(3):
+        q[c, list(ZIGZAG)] = info.qtables[c]
+    out = q.tobytes() + bytes(info.dc_sel) + b"\0" + bytes(info.ac_sel) + b"\0"
+    for cls, sel, tables in ((0, info.dc_sel, info.dc_tables), (1, info.ac_sel, info.ac_tables)):
+        for t in (0, 1):
+            out += _device_huffman(*tables[sel.index(t)]) if t in sel else b"\0" * 832
+    assert len(out) == TAB_BYTES
+    return out
+
+
+class DecodePlan:
+    """What casync_op_jpegdec_decode wants for a batch of files: blob (uint8: each file's scan, segment list and table block,
+    4-byte aligned), rec (int32 [B, 16], see include/casync_hip.h), infos (JpegInfo, or the JpegUnsupported of a file outside the
+    subset, whose record carries status 1 and nothing else), total_sub, subsampling (2: every file is 4:2:0, else 0)"""
+    __slots__ = ("blob", "rec", "infos", "total_sub", "subsampling", "H", "W", "chunk_bits")
+
+
+def plan_decode(files, chunk_bits: int = 0) -> DecodePlan:
+    chunk = _chunk_bits(chunk_bits)
+    plan = DecodePlan()
+    plan.chunk_bits = chunk
+    plan.infos = []
+    parts, at, total = [], 0, 0
+    rec = np.zeros((len(files), REC_WORDS), dtype=np.int32)
+
+    def put(b: bytes) -> int:
+        nonlocal at
+        off = at
+        b += b"\0" * (-len(b) % 4)
+        parts.append(b)
+        at += len(b)
+        return off
+
+    for i, data in enumerate(files):
+        data = bytes(data)
+        rec[i, 8] = total
+        try:
+            info = parse_jpeg(data)
+            if info.scan_length >= 1 << 27:
+                raise JpegUnsupported("jpeg: a scan of 128 MiB or more")
+        except JpegUnsupported as exc:
+            plan.infos.append(exc)
+            rec[i, 9] = 1
+            continue
+        plan.infos.append(info)
+        segs = info.segments()
+        want = info.expected_segments()
+        rec[i, 2], rec[i, 3] = info.subsampling, info.restart_interval
+        if len(segs) != want:                                    # the host's call: the device gets no work for this frame
+            rec[i, 9] = 2 if len(segs) < want else 3
+            continue
+        nsub = _subsequences(segs, chunk)
+        if sum(nsub) > MAX_SUBSEQUENCES:                         # the host path: the device bounds its rounds by this count
+            plan.infos[-1] = JpegUnsupported(f"jpeg: {sum(nsub)} subsequences of {chunk} bits, the device takes {MAX_SUBSEQUENCES} a frame")
+            rec[i, 2], rec[i, 3], rec[i, 9] = 0, 0, 1
+            continue
+        first = np.concatenate([[0], np.cumsum(nsub)]).astype(np.int32)
+        rec[i, 0] = put(data[info.scan_offset:info.scan_offset + info.scan_length])
+        rec[i, 1] = info.scan_length
+        rec[i, 4] = len(segs)
+        rec[i, 5] = put(np.asarray([a for a, _ in segs] + [b for _, b in segs], dtype=np.int32).tobytes() + first.tobytes())
+        rec[i, 6] = put(_device_tables(info))
+        rec[i, 7] = int(first[-1])
+        total += int(first[-1])
+    plan.blob = np.frombuffer(b"".join(parts) or b"\0\0\0\0", dtype=np.uint8)
+    plan.rec, plan.total_sub = rec, total
+    good = [x for x in plan.infos if isinstance(x, JpegInfo)]
+    plan.subsampling = 2 if good and all(x.subsampling == 2 for x in good) else 0
+    sizes = {(x.H, x.W) for x in good}
+    plan.H, plan.W = next(iter(sizes)) if len(sizes) == 1 else (0, 0)
+    return plan
+
+
+def decode_jpeg_op(plan: DecodePlan, data, scratch, out, status, H: int = 0, W: int = 0) -> None:
+    """casync_op_jpegdec_decode on torch's current stream, every buffer the caller's (uint8 data holding plan.blob, uint8 scratch,
+    uint8 out [B,H,W,3], int32 status [B]); nothing is waited for."""
+    import torch
+    from . import _lib
+    _lib.check(_lib.load().casync_op_jpegdec_decode(data.data_ptr(), data.numel(), plan.rec.ctypes.data, plan.rec.shape[0], H or plan.H, W or plan.W,
+                                                    plan.subsampling, plan.chunk_bits, scratch.data_ptr(), scratch.numel(), out.data_ptr(),
+                                                    status.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream), "casync_op_jpegdec_decode")
+
+
+def _decode_pillow(data) -> np.ndarray:
+    """BGR uint8 [H,W,3] of any file Pillow reads: the host path of a file outside the subset, as frame_synth._imread decodes"""
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(bytes(data))) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, ::-1])
+
+
+def decode_jpeg_device(files, *, device="cuda:0", chunk_bits: int = 0, fallback: str = "host", out=None):
+    """A sequence of JPEG files (bytes) of one size -> uint8 [B,H,W,3] BGR on the device, decoded there (csrc/jpeg_dec.hip): the
+    compressed bytes go up in one pinned copy, and what comes back is the B status words.  A file outside the subset
+    (parse_jpeg), or one whose device status is non-zero, is decoded on the host with Pillow and uploaded into its slot; with
+    ``fallback="raise"`` it raises instead, naming the file's index.  ``chunk_bits`` (0: the default, 2048) is the length of the
+    subsequences the entropy stage cuts a scan into.  ``out``: a contiguous uint8 [B,H,W,3] device tensor to decode into."""
+    import torch
+    if fallback not in ("host", "raise"):
+        raise ValueError(f"decode_jpeg_device: fallback {fallback!r} is neither 'host' nor 'raise'")
+    files = [bytes(f) for f in files]
+    dev = torch.device(device) if out is None else out.device
+    if dev.type != "cuda":
+        raise RuntimeError("decode_jpeg_device needs a ROCm device (decode_jpeg_host is the host decoder)")
+    plan = plan_decode(files, chunk_bits)
+    B = len(files)
+    if B == 0:
+        return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=dev) if out is None else out
+    host = {}                                                    # index -> pixels decoded on the host
+    for i, info in enumerate(plan.infos):
+        if not isinstance(info, JpegInfo):
+            if fallback == "raise":
+                raise JpegUnsupported(f"decode_jpeg_device: file {i}: {info}")
+            try:
+                host[i] = _decode_pillow(files[i])
+            except Exception as exc:
+                raise JpegUnreadable(i, f"decode_jpeg_device: cannot read file {i}: {info}; Pillow: {exc}") from exc
+    sizes = {(x.H, x.W) for x in plan.infos if isinstance(x, JpegInfo)} | {v.shape[:2] for v in host.values()}
+    if len(sizes) != 1:
+        raise ValueError(f"decode_jpeg_device: the files must have one size, got {sorted(sizes)} (h x w)")
+    H, W = (int(v) for v in next(iter(sizes)))
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W, 3) or not out.is_contiguous()):
+        raise ValueError(f"decode_jpeg_device: out must be a contiguous uint8 {(B, H, W, 3)} tensor, got {tuple(out.shape)} {out.dtype}")
+    from . import _lib, frame_loop
+    lib = _lib.load()
+    need = lib.casync_op_jpegdec_workspace_bytes(B, H, W, plan.subsampling, plan.total_sub)
+    if need < 0:
+        _lib.check(int(need), "casync_op_jpegdec_workspace_bytes")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        stage = frame_loop._acquire_pinned(plan.blob.size)
+        status_host = frame_loop._acquire_pinned(4 * B)
+        try:
+            stage[:plan.blob.size].numpy()[:] = plan.blob
+            data = torch.empty(plan.blob.size, dtype=torch.uint8, device=dev)
+            data.copy_(stage[:plan.blob.size], non_blocking=True)
+            scratch = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            decode_jpeg_op(plan, data, scratch, out, status, H, W)
+            status_host[:4 * B].copy_(status.view(torch.uint8), non_blocking=True)
+            stream.synchronize()
+            st = status_host[:4 * B].numpy().view(np.int32).copy()
+        finally:
+            frame_loop._release_pinned(stage)
+            frame_loop._release_pinned(status_host)
+        for i in range(B):
+            if st[i] and i not in host:
+                if fallback == "raise":
+                    raise JpegCorrupt(int(st[i]), f"decode_jpeg_device: file {i}: the scan is damaged (status {int(st[i])})")
+                try:
+                    host[i] = _decode_pillow(files[i])
+                except Exception as exc:
+                    raise JpegCorrupt(int(st[i]), f"decode_jpeg_device: file {i}: status {int(st[i])} on the device, and Pillow cannot read it "
+                                      f"either ({exc})") from exc
+                if host[i].shape != (H, W, 3):
+                    raise ValueError(f"decode_jpeg_device: file {i} decodes to {host[i].shape}, the batch is {(H, W, 3)}")
+        for i, px in host.items():
+            out[i].copy_(torch.from_numpy(px))
+    return out

@@ -251,10 +251,16 @@ class ResidentClip:
                 frame_loop._release_pinned(stage)
 
     @classmethod
-    def from_data_dir(cls, data_dir: str, device="cuda:0", io_workers: int = 8) -> "ResidentClip":
+    def from_data_dir(cls, data_dir: str, device="cuda:0", io_workers: int = 8, decode: str = "host") -> "ResidentClip":
         """The clip of an ``infer_data`` directory (frames/, positions/, masks/), every file read once, with the loaders and
-        the .jpg / .npy rule of ``frame_synth.FrameSynthesizer``; masks stay uint8 where the file holds uint8."""
+        the .jpg / .npy rule of ``frame_synth.FrameSynthesizer``; masks stay uint8 where the file holds uint8.
+        ``decode="device"``: the workers read the .jpg frames as bytes and ``jpeg.decode_jpeg_device`` decodes each list of
+        ``UPLOAD_CHUNK`` files straight into the clip's storage, so that the compressed bytes cross to the device, not the
+        pixels; the frames are the same bytes as with ``"host"`` wherever the host decoder is libjpeg's default path (Pillow,
+        cv2).  Masks, .npy frames and files outside the decoder's subset take the host path."""
         from .frame_synth import _imread
+        if decode not in ("host", "device"):
+            raise ValueError(f"ResidentClip.from_data_dir: decode {decode!r} is neither 'host' nor 'device'")
         frames_dir, positions_dir, masks_dir = (os.path.join(data_dir, d) for d in ("frames", "positions", "masks"))
         names = os.listdir(frames_dir)
         ext = ".jpg" if any(f.endswith(".jpg") for f in names) else ".npy"
@@ -263,9 +269,15 @@ class ResidentClip:
             raise ValueError(f"ResidentClip: no frames in {frames_dir}")
         landmarks, masks = [None] * n, [None] * n
 
+        as_bytes = decode == "device" and ext == ".jpg"
+
         def load(i):
             stem = f"{i:06d}"
-            img = _imread(os.path.join(frames_dir, stem + ext))
+            if as_bytes:
+                with open(os.path.join(frames_dir, stem + ext), "rb") as f:
+                    img = f.read()
+            else:
+                img = _imread(os.path.join(frames_dir, stem + ext))
             if img is None:
                 raise ValueError(f"ResidentClip: cannot read {os.path.join(frames_dir, stem + ext)}")
             landmarks[i] = np.loadtxt(os.path.join(positions_dir, stem + ".txt"))
@@ -278,7 +290,35 @@ class ResidentClip:
 
         with ThreadPoolExecutor(max_workers=max(1, int(io_workers))) as pool:
             chunks = (list(pool.map(load, range(i, min(i + UPLOAD_CHUNK, n)))) for i in range(0, n, UPLOAD_CHUNK))
+            if as_bytes:
+                return cls(cls._decode_chunks(n, chunks, torch.device(device), frames_dir), landmarks, masks, device)
             return cls(_Chunks(n, chunks), landmarks, masks, device)      # the two lists fill while the frames go up
+
+    @classmethod
+    def _decode_chunks(cls, n: int, chunks, device, frames_dir: str) -> torch.Tensor:
+        """Lists of JPEG files -> the device tensor [n,H,W,3], each list decoded on the device into its place"""
+        from . import jpeg
+        frames, at = None, 0
+        for files in chunks:
+            try:
+                if frames is None:
+                    try:
+                        info = jpeg.parse_jpeg(files[0])                     # its size is the clip's
+                        shape = (info.H, info.W, 3)
+                    except jpeg.JpegUnsupported:
+                        shape = tuple(jpeg.decode_jpeg_device(files[:1], device=device).shape[1:])
+                    cls._check_size(n, shape)                                # before the clip is allocated
+                    with torch.cuda.device(device):
+                        frames = torch.empty((n,) + shape, dtype=torch.uint8, device=device)
+                jpeg.decode_jpeg_device(files, out=frames[at:at + len(files)])
+            except jpeg.JpegUnreadable as exc:
+                raise ValueError(f"ResidentClip: cannot read {os.path.join(frames_dir, f'{at + exc.index:06d}.jpg')}") from exc
+            except ValueError as exc:
+                if isinstance(exc, (jpeg.JpegUnsupported, jpeg.JpegCorrupt)):
+                    raise
+                raise _mixed([str(exc)]) from exc
+            at += len(files)
+        return frames
 
     @classmethod
     def from_frames(cls, frames_bgr, landmark_detector, boxes=None, chunk: int = 32, masks=None) -> "ResidentClip":

@@ -46,7 +46,7 @@ enum {
 #define CASYNC_ABI_VERSION 13  /* 12: S3FD face detector handle (casync_s3fd_*, casync_op_s3fd_*); 13: its bf16 precision
                                 * (casync_s3fd_create_ex, _precision, _workspace_bytes_ex, casync_op_s3fd16_*).  The face-pipeline
                                 * operators at the end of this file (casync_op_resize_linear_u8, _face_crops192, _s3fd_candidates,
-                                * _landmarks_finalize), casync_op_s3fd_nms, casync_op_clip_gather / _compose, casync_op_jpeg_* and casync_op_jpeg420_* were added under 13: new symbols only, no prototype or layout changed */
+                                * _landmarks_finalize), casync_op_s3fd_nms, casync_op_clip_gather / _compose, casync_op_jpeg_*, casync_op_jpeg420_* and casync_op_jpegdec_* were added under 13: new symbols only, no prototype or layout changed */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -689,6 +689,50 @@ int     casync_op_jpeg420_header(int H, int W, int quality, uint8_t* out, int ca
 int64_t casync_op_jpeg420_workspace_bytes(int batch, int H, int W, int64_t slot_bytes);
 int     casync_op_jpeg420_encode(const uint8_t* frames_bgr, int batch, int H, int W, int quality, int64_t slot_bytes, uint8_t* scratch,
                                  int64_t scratch_bytes, uint8_t* out, int64_t out_cap, int64_t* offsets, int32_t* status,
+                                 casync_stream stream);
+
+/* ---- baseline JPEG files -> frames (additive to ABI 13: two new symbols, nothing else changed) -------------------- */
+/* `batch` baseline JPEG files of one size -> uint8 BGR frames [batch,H,W,3] on the device, byte for byte what libjpeg's default
+ * integer path decodes (islow inverse DCT: 13 constant bits, columns first, descaled by 11 and 18 bits, +128, clamp; 4:2:0 chroma
+ * through h2v2 fancy upsampling of the real ceil(H/2) x ceil(W/2) plane with its edge rows and columns repeated; 16-bit
+ * fixed-point YCbCr -> RGB).  calipsync_amd/jpeg.py decode_jpeg_host is the numpy twin, parse_jpeg reads the headers and
+ * plan_decode builds what this call takes; tests/golden/jpeg_decode_cases.npz holds recorded files and pixels.  The subset: SOF0,
+ * 8 bits, three components sampled 1x1 / 1x1 / 1x1 or 2x2 / 1x1 / 1x1, one interleaved scan, 8-bit quantisation tables, Huffman
+ * tables 0 and 1 of any contents, any restart interval.
+ *   data [data_bytes], DEVICE, 4-byte aligned: per file its scan (the entropy-coded bytes, RSTn markers included), its segment
+ *     list and its table block, each on a 4-byte boundary.
+ *       segment list: int32 start [nseg] | end [nseg] | first subsequence [nseg + 1]; start / end are byte offsets relative to the
+ *         scan of each restart segment, markers excluded; segment j has max(1, ceil(8 (end - start) / chunk_bits)) subsequences.
+ *       table block, 3720 bytes: quantisation uint16 [3][64] per component in natural order | uint8 DC table (0 / 1) of each
+ *         component, 0 | uint8 AC table of each, 0 | Huffman tables DC 0, DC 1, AC 0, AC 1 of 832 bytes: uint16 lut [256] on the
+ *         next 8 bits (length << 8 | symbol, 0: a longer code) | int32 maxcode [8] of lengths 9..16 (-1: none) | int32 valoff [8]
+ *         (index of the length's first symbol - its first code) | uint8 symbols [256].
+ *   rec [batch][16] int32 in HOST memory, read before the call returns:
+ *     { scan byte offset in data, scan bytes, sampling (0: 4:4:4, 2: 4:2:0), restart interval in MCUs (0: none), segments,
+ *       segment list byte offset, table block byte offset, subsequences, index of its first subsequence among the batch's,
+ *       status decided on the host (0; otherwise the frame gets that status, no subsequences and no work), 0 ... }
+ *   subsampling: 2 sizes the scratch for 4:2:0 files only, 0 for either.  chunk_bits: a multiple of 32 in 32..2^30.  A frame has
+ *     at most 2^17 subsequences: the plan runs at most as many rounds as a frame has subsequences and a round sweeps them all, so
+ *     this bounds the time one workgroup can be kept busy by a file that never synchronises (a record above it is refused; the
+ *     caller takes a longer chunk_bits or the host path, as calipsync_amd/jpeg.py plan_decode does).
+ *   jpegdec_workspace_bytes: 64 bytes per subsequence, then per frame its int16 coefficients [blocks][64] and its sample planes.
+ *   status [batch] int32, DEVICE: 0, or the code of the first restart segment that breaks a rule -- 1: an invalid Huffman code, a
+ *     DC category above 11 or a run past coefficient 63 ahead of the segment's last block; 2: the segment's bytes end before its
+ *     last block; 3: they hold more blocks than its MCUs.  A frame with a non-zero status has unspecified pixels inside its own
+ *     slot of `out`; nothing outside its slot and its scratch is written.
+ * Refused with CASYNC_ERR_ARG before anything is launched or touched: a null pointer, a misaligned buffer, H or W outside
+ * 1..65535, a record whose offsets leave data, whose segment count is not the geometry's, which has more than 2^17 subsequences, or whose subsequences do not follow the
+ * previous record's, a scratch smaller than jpegdec_workspace_bytes says.  The contents of data are never trusted: every value
+ * read from a segment list or a table is clamped or masked, bits past a segment's end read as zero, a segment writes at most the
+ * blocks its MCUs have, and every loop is bounded by the bits of its subsequence.
+ * Four kernels per 64 frames: the entropy plan (one workgroup per frame: the entry state of every subsequence by a fixed-point
+ * iteration from guessed states, which ends after at most as many rounds as the longest segment has subsequences with the serial
+ * decoder's states; then block offsets, DC predictors and the status by a segmented prefix sum), the coefficient write (one lane
+ * per subsequence), the inverse DCT (one lane per block) and upsampling + colour (one lane per four pixels).  The output is a pure
+ * function of the input: no global atomics.  One hipMemsetAsync of the coefficients; no allocation, no synchronisation.        */
+int64_t casync_op_jpegdec_workspace_bytes(int batch, int H, int W, int subsampling, int64_t total_subsequences);
+int     casync_op_jpegdec_decode(const uint8_t* data, int64_t data_bytes, const int32_t* rec, int batch, int H, int W, int subsampling,
+                                 int chunk_bits, uint8_t* scratch, int64_t scratch_bytes, uint8_t* out, int32_t* status,
                                  casync_stream stream);
 
 #ifdef __cplusplus
