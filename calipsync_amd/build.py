@@ -44,15 +44,15 @@ SOURCES_CLIP = ["clip_ops.hip"]
 OBJ_DIR_JPEG = os.path.join(LIB_DIR, "obj_jpeg")
 SOURCES_JPEG = ["jpeg_enc.hip"]
 # Its 4:2:0 sibling (tests/kernel_ledger_jpeg420.py is its ledger): a tenth object directory, its source an entry of SOURCES in
-# the same way.  The two encoders share no code, so neither object changes when the other's source does.
+# the same way.  What the two encoders share is csrc/jpeg_enc_common.h (an entry of HEADERS), in each object's own anonymous namespace.
 OBJ_DIR_JPEG420 = os.path.join(LIB_DIR, "obj_jpeg420")
 SOURCES_JPEG420 = ["jpeg_enc420.hip"]
 # The baseline JPEG decoder (tests/kernel_ledger_jpegdec.py is its ledger): an eleventh object directory, its source an entry of
-# SOURCES in the same way.  It shares no code with the encoders.
+# SOURCES in the same way.  It shares no code with the encoders (their jpeg_enc_common.h is not its header).
 OBJ_DIR_JPEGDEC = os.path.join(LIB_DIR, "obj_jpegdec")
 SOURCES_JPEGDEC = ["jpeg_dec.hip"]
 SOURCES = ["runtime.hip", "gemm.hip", "ops.hip", "ir_fused.hip", "pw_dw.hip", "pw_dw_bf16.hip", "attention.hip", "attention_bf16.hip", "frame_ops.hip", "hubert.hip", "engine.hip"] + SOURCES_DET + SOURCES_DET16 + SOURCES_FACE + SOURCES_NMS + SOURCES_CLIP + SOURCES_JPEG + SOURCES_JPEG420 + SOURCES_JPEGDEC
-HEADERS = ["common.h", "handle.h", "ir_common.h", "pw_dw_common.h", os.path.join("..", "..", "include", "casync_hip.h")]
+HEADERS = ["common.h", "handle.h", "ir_common.h", "pw_dw_common.h", "jpeg_enc_common.h", os.path.join("..", "..", "include", "casync_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 
 

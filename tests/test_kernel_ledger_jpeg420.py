@@ -61,6 +61,14 @@ def test_the_jpeg420_object_is_in_its_own_directory(objects):
         assert build.source_hash() != with_420
     finally:
         build.SOURCES = sources
+    # ... and the header the two encoders share
+    headers = build.HEADERS
+    assert "jpeg_enc_common.h" in headers
+    try:
+        build.HEADERS = [h for h in headers if h != "jpeg_enc_common.h"]
+        assert build.source_hash() != with_420
+    finally:
+        build.HEADERS = headers
 
 
 def test_every_jpeg420_kernel_has_a_ledger_case(table):
