@@ -96,14 +96,23 @@ constexpr int kUpsTileBytes = 16384;   // 6 rows x 20 pixels (40x40 strips) or 1
 template <int HL>
 __device__ __forceinline__ void ups_tile_load(float* sG, const float* g, int ld, int gy0, int n_rows, int wave, int lane) {
   // g: this frame's channel slice (32 channels from the workgroup's n0); rows past the frame re-read its last row
+  // piece (j * 4 + wave) * 64 + lane = quad ql of pixel p = (j * 4 + wave) * 8 + (lane >> 3): p & 7 is the lane's, and
+  // (row, column) = (p / HL, p % HL) is carried from one j to the next (p grows by 32)
+  const int ql = lane & 7, p7 = lane >> 3;
+  int row = 0, gx = wave * 8 + p7;
+#pragma unroll
+  for (int k = 0; k < 32 / HL; ++k)
+    if (gx >= HL) gx -= HL, ++row;
 #pragma unroll
   for (int j = 0; j < kUpsTileBytes / 4096; ++j) {
-    const int piece = (j * 4 + wave) * 64 + lane, p = piece >> 3, ql = piece & 7;
-    int gr = p / HL;
-    const int gx = p - gr * HL;
-    gr = gr < n_rows ? gr : n_rows - 1;
+    if (j > 0) {
+      row += 32 / HL;
+      gx += 32 % HL;
+      if (32 % HL != 0 && gx >= HL) gx -= HL, ++row;
+    }
+    const int gr = row < n_rows ? row : n_rows - 1;
     const int gy = gy0 + gr < HL ? gy0 + gr : HL - 1;
-    const float* src = g + (size_t)(gy * HL + gx) * ld + 4 * (ql ^ (p & 7));
+    const float* src = g + (size_t)(gy * HL + gx) * ld + 4 * (ql ^ p7);
     __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)src,
                                      (void __attribute__((address_space(3)))*)(reinterpret_cast<char*>(sG) + (j * 4 + wave) * 1024), 16, 0, 0);
   }
@@ -259,16 +268,15 @@ __device__ __forceinline__ void e_zero_columns(float* sE, int tid) {
   }
 }
 
-// One work item of the depthwise epilogue: channel quad cq, output column ox, `nrows` output rows downwards from output
-// row oy0.  R0 = image row of tap row ky = 0 of the first output (may be -1 for a whole frame's first row: skipped);
-// d = the first output's place in D.  EDGE: the image holds whole frames of HW rows without zero rows -- the tap row above
-// the first and below the last image row of the frame is left out; strips carry their zero rows in the image.
+// One work item of the depthwise epilogue, row by row (the long runs of dw_walk below): `nrows` output rows downwards from
+// output row oy0 of one channel quad and output column.  p0[kx] = float offset of tap (ky = 0, kx) of the first output in the
+// image (its row may be -1 for a whole frame's first row: skipped); d = the first output's place in D.  EDGE: the image holds
+// whole frames of HW rows without zero rows -- the tap row above the first and below the last image row of the frame is left
+// out; strips carry their zero rows in the image.
 template <class E, int S, int HW, bool EDGE>
-__device__ __forceinline__ void dw_run(const float* sE, int R0, int ox, int cq, int oy0, const f32x4 (&wt)[9], f32x4 bv, float* d,
+__device__ __forceinline__ void dw_run(const float* sE, const int (&p0)[3], int oy0, const f32x4 (&wt)[9], f32x4 bv, float* d,
                                        size_t d_row, int nrows) {
-  int p[3];   // float offsets into the image (integers, so that the loads stay LDS instructions with immediate row offsets)
-#pragma unroll
-  for (int kx = 0; kx < 3; ++kx) p[kx] = E::at(R0, ox * S + kx - 1, cq);
+  int p[3] = {p0[0], p0[1], p0[2]};
   for (int r = 0; r < nrows; ++r) {
     f32x4 a = bv;
     const int y0 = (oy0 + r) * S - 1;                       // frame row of tap row 0
@@ -282,6 +290,103 @@ __device__ __forceinline__ void dw_run(const float* sE, int R0, int ox, int cq, 
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) p[kx] += S * E::ROWF;
     d += d_row;
+  }
+}
+
+// (image row, column) of pixel px of a stack of WD-wide image rows -- whole frames lie on top of each other, so frame f, row y
+// is image row f HW + y = px / WD -- carried from one pixel tile of a wave to its next: px grows by STEP, no division per tile.
+template <int WD, int STEP>
+struct PxWalk {
+  int R, x;
+  __device__ __forceinline__ explicit PxWalk(int px) : R(px / WD), x(px - (px / WD) * WD) {}
+  __device__ __forceinline__ void next() {
+    R += STEP / WD;
+    x += STEP % WD;
+    if (STEP % WD != 0 && x >= WD) x -= WD, ++R;
+  }
+};
+// ETile::at(R, x, cq) of pixel px = R WD + x: the pixel's place in the image is px + 2 R + 1 (two zero columns per row above it,
+// one in front).  Where the width and the tile step are multiples of 8 the key (x + 1) & 7 is that of the lane, `key4` (float
+// offset of the keyed quad, computed once); elsewhere it is taken from x.
+template <int WD, int STEP, int BN>
+__device__ __forceinline__ int e_at_px(int px, int R, int x, int cq, int key4) {
+  if constexpr (WD % 8 == 0 && STEP % 8 == 0) return (px + 2 * R + 1) * BN + key4;
+  else return (px + 2 * R + 1) * BN + (((cq ^ (x + 1)) & 7) << 2);
+}
+
+// Epilogue 2: the depthwise 3x3 over the E image, + bd, LeakyReLU -> D.  A work item is a channel quad, an output column and a
+// run of RPS output rows; item id = (run WO + ox) NQ + cq belongs to thread id % 256.  The thread splits its id ONCE into
+// (cq, ox, run): from one item to its next the quad stays (256 % NQ == 0), the column grows by 256 / NQ modulo WO and the run
+// by the carry -- adds, one compare, one conditional subtract.  Only the runs that hold rows are numbered (NRR of them per
+// frame, frame-major: run = f NRR + rr), so no item is set up for nothing and a half-empty frame pair ends the walk early.
+//   ROWS   output rows of a frame (whole frames) or of a strip
+//   EDGE   whole frames: the image has no zero rows, the tap row above a frame's first / below its last row is left out --
+//          tested once per run (only a frame's first run can lack the row above, only ky = 2 of a row whose taps reach row HW
+//          the one below); strips carry their zero rows in the image (image row 0 = tap row 0 of the strip's first output)
+//   Dwg    the workgroup's first output pixel, at this channel tile's first channel; nf frames are there
+// Runs of up to eight rows are unrolled: their 9 RPS tap reads sit at immediate offsets from three column pointers.  Longer
+// runs (16x32 frames: one item of 16 rows per thread, past the immediates' reach) walk down row by row (dw_run).
+template <class E, int BN, int S, int HW, int ROWS, int WO, int RPS, int F, bool EDGE>
+__device__ __forceinline__ void dw_walk(const float* sE, int tid, int nf, const float* __restrict__ wd, const float* __restrict__ bd,
+                                        int N, float* Dwg, int ldd) {
+  constexpr int NQ = BN / 4, CPW = 256 / NQ;               // channel quads; columns the 256 threads cover at once
+  constexpr int NRR = (ROWS + RPS - 1) / RPS;              // runs of a frame that hold rows
+  constexpr int QW = CPW / WO, RW = CPW % WO;              // a thread's next item: QW runs and RW columns on
+  constexpr bool KEYFIX = (S * WO) % 8 == 0 && (S * CPW) % 8 == 0;   // ... leaves (x + 1) & 7 of its taps alone
+  constexpr bool BOTTOM = EDGE && (ROWS - 1) * S + 1 >= HW;          // a frame's last output row reaches below the frame
+  constexpr bool FULL = ROWS % RPS == 0;                             // every run has RPS rows: only a run's last row can be that row
+  static_assert(256 % NQ == 0 && F <= 2, "a thread keeps its channel quad; at most a frame pair");
+  const int cq = tid % NQ;
+  int ox = tid / NQ, run = 0;
+#pragma unroll
+  for (int k = 0; k < QW; ++k)
+    if (ox >= WO) ox -= WO, ++run;
+  const int nruns = NRR * nf;
+  if (run >= nruns) return;
+  f32x4 wt[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) wt[t] = *reinterpret_cast<const f32x4*>(wd + 4 * cq + (size_t)t * N);
+  const f32x4 bv = *reinterpret_cast<const f32x4*>(bd + 4 * cq);
+  char* const dq = reinterpret_cast<char*>(Dwg + 4 * cq);
+  const size_t d_row = (size_t)WO * ldd * sizeof(float);
+  auto key4 = [&](int c) { return ((cq ^ c) & 7) << 2; };   // float offset of quad cq in a pixel of image column c = x + 1
+  int kfix[3];
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx) kfix[kx] = kx * BN + key4(ox * S + kx);
+  for (; run < nruns;) {
+    int f = 0, rr = run;
+    if (F == 2 && rr >= NRR) rr -= NRR, f = 1;
+    const int r0 = rr * RPS, rem = ROWS - r0;              // first output row of the run; rows from there to the frame's end
+    const int c = ox * S;                                  // image column of tap kx = 0
+    const int pb = ((f * HW + r0 * S - (EDGE ? 1 : 0)) * E::WP + c) * BN;
+    int p[3];   // float offsets into the image (integers, so that the loads stay LDS instructions with immediate row offsets)
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) p[kx] = pb + (KEYFIX ? kfix[kx] : kx * BN + key4(c + kx));
+    // (the launchers bound A and W1, not D: the pixel's byte offset is a full 32 x 32 -> 64-bit product behind the 64-bit base)
+    char* d = dq + (unsigned long long)(unsigned)(((f * ROWS + r0) * WO + ox) * 4) * (unsigned)ldd;
+    if constexpr (RPS <= 8) {
+      static_assert(((RPS - 1) * S + 2) * E::ROWF * 4 + 16 <= 65536, "tap row offsets of an unrolled run are DS immediates");
+      const bool top = EDGE && r0 == 0;
+#pragma unroll
+      for (int r = 0; r < RPS; ++r) {
+        if (!FULL && r > 0 && r >= rem) break;
+        f32x4 a = bv;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+          if (EDGE && r == 0 && ky == 0 && top) continue;
+          if (BOTTOM && ky == 2 && (!FULL || r == RPS - 1) && (r0 + r) * S + 1 >= HW) continue;
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) a += *reinterpret_cast<const f32x4*>(sE + p[kx] + (r * S + ky) * E::ROWF) * wt[ky * 3 + kx];
+        }
+        *reinterpret_cast<f32x4*>(d) = lrelu4(a);
+        d += d_row;
+      }
+    } else {
+      dw_run<E, S, HW, EDGE>(sE, p, r0, wt, bv, reinterpret_cast<float*>(d), (size_t)WO * ldd, rem < RPS ? rem : RPS);
+    }
+    run += QW;
+    ox += RW;
+    if (RW != 0 && ox >= WO) ox -= WO, ++run;
   }
 }
 
@@ -338,44 +443,26 @@ __device__ __forceinline__ void pw_dw_body(
   e_zero_columns<E, F * HW, G::NQ, WD>(sE, tid);
   {
     const f32x4 bias = *reinterpret_cast<const f32x4*>(b1 + n0 + 16 * wn + 4 * q);
+    constexpr int STEP = 16 * G::WPN;                     // a wave's next pixel tile
+    const int cq = 4 * wn + q, key4 = ((cq ^ (l15 + 1)) & 7) << 2;
+    PxWalk<WD, STEP> w(16 * wm + l15);
 #pragma unroll
-    for (int i = 0; i < G::MTW; ++i) {
+    for (int i = 0; i < G::MTW; ++i, w.next()) {
       const int t = wm + G::WPN * i;
       const int px = 16 * t + l15;
       if (pw_dw_ksplit<G> && i == G::MTW - 1) continue;   // the shared tile: below
-      if (t < G::MT && px < m_valid) {
-        const int f = px / G::P, rem = px - f * G::P, y = rem / WD, x = rem - y * WD;
-        *reinterpret_cast<f32x4*>(sE + E::at(f * HW + y, x, 4 * wn + q)) = lrelu4(acc[i] + bias);
-      }
+      if (t < G::MT && px < m_valid) *reinterpret_cast<f32x4*>(sE + e_at_px<WD, STEP, BN>(px, w.R, w.x, cq, key4)) = lrelu4(acc[i] + bias);
     }
     if constexpr (pw_dw_ksplit<G>) {
-      const int px = 16 * (G::MT - 1) + l15, f = px / G::P, rem = px - f * G::P, y = rem / WD, x = rem - y * WD;
-      float* slot = sE + E::at(f * HW + y, x, 4 * wn + q);
+      const int px = 16 * (G::MT - 1) + l15, R = px / WD, x = px - R * WD;
+      float* slot = sE + E::at(R, x, cq);
       shared_tile_sum(slot, px < m_valid, wm, ks, acc[G::MTW - 1], [&](f32x4 sum) { *reinterpret_cast<f32x4*>(slot) = lrelu4(sum + bias); });
     }
   }
   __syncthreads();
 
   // ---- epilogue 2: depthwise 3x3 (zero columns = the horizontal padding; the vertical one by skipping tap rows), + bd, LeakyReLU -> D ----
-  {
-    constexpr int HO = G::HO, WO = G::WO, NITEM = G::NQ * WO * G::RS * F;
-    f32x4 wt[9];
-    int cq_of = -1;
-    for (int id = tid; id < NITEM; id += 256) {
-      const int cq = id % G::NQ, rest = id / G::NQ, ox = rest % WO, run = rest / WO, f = run / G::RS, r0 = (run - f * G::RS) * G::RPS;
-      if (f >= nf) continue;
-      if (cq != cq_of) {   // (256 % NQ == 0: a thread keeps its channel quad; loaded once)
-        const float* wq = wd + n0 + 4 * cq;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) wt[t] = *reinterpret_cast<const f32x4*>(wq + (size_t)t * N);
-        cq_of = cq;
-      }
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(bd + n0 + 4 * cq);
-      const int nrows = HO - r0 < G::RPS ? HO - r0 : G::RPS;
-      dw_run<E, S, HW, true>(sE, f * HW + r0 * S - 1, ox, cq, r0, wt, bv,
-                             D + ((size_t)(f0 + f) * HO * WO + (size_t)r0 * WO + ox) * ldd + n0 + 4 * cq, (size_t)WO * ldd, nrows);
-    }
-  }
+  dw_walk<E, BN, S, HW, G::HO, G::WO, G::RPS, F, true>(sE, tid, nf, wd + n0, bd + n0, N, D + (size_t)f0 * G::HO * G::WO * ldd + n0, ldd);
 }
 
 template <int HW, int F, int BN, int KF, int S, int NST = 2>
@@ -432,28 +519,31 @@ __global__ __launch_bounds__(256, (FTGeom<HW, F, BN, KF, S, NST>::occ)) void pw_
   e_zero_columns<E, F * HW, G::NQ, HW>(sE, tid);
   {
     const f32x4 bias = *reinterpret_cast<const f32x4*>(b1 + n0 + 16 * wn + 4 * q);
+    constexpr int STEP = 16 * G::WPN;                     // a wave's next pixel tile
+    const int cq = 4 * wn + q, key4 = ((cq ^ (l15 + 1)) & 7) << 2;
+    PxWalk<HW, STEP> w(16 * wm + l15);
 #pragma unroll
-    for (int i = 0; i < G::MTW; ++i) {
+    for (int i = 0; i < G::MTW; ++i, w.next()) {
       const int t = wm + G::WPN * i;
       const int px = 16 * t + l15;
       if (pw_dw_ksplit<G> && i == G::MTW - 1) continue;   // the shared tile: below
       if (t < G::MT && px < m_valid) {
-        const int f = px / G::P, rem = px - f * G::P, y = rem / HW, x = rem - y * HW;
         f32x4 v = acc[i] + bias;
         if (ups) {
           // + the bilinear x2 upsample of the low-resolution half of an Up block's expand conv (it commutes with the
-          // 1x1 conv: common.h GemmEpilogue::ups_src), HW/2 x HW/2 frames of ld_ups channels
-          v += ups_at_lds<HW>(sG, 0, y, x, 4 * wn + q);
+          // 1x1 conv: common.h GemmEpilogue::ups_src), HW/2 x HW/2 frames of ld_ups channels (one frame per tile: the
+          // image row is the frame's row)
+          v += ups_at_lds<HW>(sG, 0, w.R, w.x, cq);
         }
-        *reinterpret_cast<f32x4*>(sE + E::at(f * HW + y, x, 4 * wn + q)) = lrelu4(v);
+        *reinterpret_cast<f32x4*>(sE + e_at_px<HW, STEP, BN>(px, w.R, w.x, cq, key4)) = lrelu4(v);
       }
     }
     if constexpr (pw_dw_ksplit<G>) {
-      const int px = 16 * (G::MT - 1) + l15, f = px / G::P, rem = px - f * G::P, y = rem / HW, x = rem - y * HW;
-      float* slot = sE + E::at(f * HW + y, x, 4 * wn + q);
+      const int px = 16 * (G::MT - 1) + l15, R = px / HW, x = px - R * HW;
+      float* slot = sE + E::at(R, x, cq);
       shared_tile_sum(slot, px < m_valid, wm, ks, acc[G::MTW - 1], [&](f32x4 sum) {
         f32x4 v = sum + bias;
-        if (ups) v += ups_at_lds<HW>(sG, 0, y, x, 4 * wn + q);
+        if (ups) v += ups_at_lds<HW>(sG, 0, R, x, cq);
         *reinterpret_cast<f32x4*>(slot) = lrelu4(v);
       });
     }
@@ -461,25 +551,7 @@ __global__ __launch_bounds__(256, (FTGeom<HW, F, BN, KF, S, NST>::occ)) void pw_
   __syncthreads();
 
   // ---- epilogue 2: depthwise 3x3 (zero columns = the horizontal padding; the vertical one by skipping tap rows), + bd, LeakyReLU -> D ----
-  {
-    constexpr int HO = G::HO, NITEM = G::NQ * HO * G::RS * F;
-    f32x4 wt[9];
-    int cq_of = -1;
-    for (int id = tid; id < NITEM; id += 256) {
-      const int cq = id % G::NQ, rest = id / G::NQ, ox = rest % HO, run = rest / HO, f = run / G::RS, r0 = (run - f * G::RS) * G::RPS;
-      if (f >= nf) continue;
-      if (cq != cq_of) {   // (256 % NQ == 0: a thread keeps its channel quad; loaded once)
-        const float* wq = wd + n0 + 4 * cq;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) wt[t] = *reinterpret_cast<const f32x4*>(wq + (size_t)t * N);
-        cq_of = cq;
-      }
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(bd + n0 + 4 * cq);
-      const int nrows = HO - r0 < G::RPS ? HO - r0 : G::RPS;
-      dw_run<E, S, HW, true>(sE, f * HW + r0 * S - 1, ox, cq, r0, wt, bv,
-                             D + ((size_t)(f0 + f) * HO * HO + (size_t)r0 * HO + ox) * ldd + n0 + 4 * cq, (size_t)HO * ldd, nrows);
-    }
-  }
+  dw_walk<E, BN, S, HW, G::HO, G::HO, G::RPS, F, true>(sE, tid, nf, wd + n0, bd + n0, N, D + (size_t)f0 * G::HO * G::HO * ldd + n0, ldd);
 }
 
 // Rectangular frames (AudioConvWenet's 16x32 blocks, module/unet.py:114-117): one whole H x W frame per tile, stride 1.  16x32 x
@@ -572,28 +644,31 @@ __global__ __launch_bounds__(256, (FSGeom<HW, SR, STRIDE, BN, KF>::occ)) void pw
   e_zero_columns<E, G::RIN, G::NQ, HW>(sE, tid);
   {
     const f32x4 bias = *reinterpret_cast<const f32x4*>(b1 + n0 + 16 * wn + 4 * q);
+    constexpr int STEP = 16 * G::WPN;                     // a wave's next pixel tile
+    const int cq = 4 * wn + q, key4 = ((cq ^ (l15 + 1)) & 7) << 2;
+    PxWalk<HW, STEP> w(16 * wm + l15);                    // (image row = strip-local input row)
 #pragma unroll
-    for (int i = 0; i < G::MTW; ++i) {
+    for (int i = 0; i < G::MTW; ++i, w.next()) {
       const int t = wm + G::WPN * i;
       const int px = 16 * t + l15;
       if (pw_dw_ksplit<G> && i == G::MTW - 1) continue;   // the shared tile: below
       if (t < G::MT && px < G::M) {
-        const int yl = px / HW, x = px - yl * HW, y = y0 + yl;
-        const bool inside = y >= 0 && y < HW;
+        const int y = y0 + w.R;
+        const bool inside = (unsigned)y < (unsigned)HW;
         f32x4 v = acc[i] + bias;
         if (ups && inside) {
-          v += ups_at_lds<HW>(sG, gy0, y, x, 4 * wn + q);
+          v += ups_at_lds<HW>(sG, gy0, y, w.x, cq);
         }
-        *reinterpret_cast<f32x4*>(sE + E::at(yl, x, 4 * wn + q)) = inside ? lrelu4(v) : f32x4{0.f, 0.f, 0.f, 0.f};
+        *reinterpret_cast<f32x4*>(sE + e_at_px<HW, STEP, BN>(px, w.R, w.x, cq, key4)) = inside ? lrelu4(v) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
     if constexpr (pw_dw_ksplit<G>) {
       const int px = 16 * (G::MT - 1) + l15, yl = px / HW, x = px - yl * HW, y = y0 + yl;
       const bool inside = y >= 0 && y < HW;
-      float* slot = sE + E::at(yl, x, 4 * wn + q);
+      float* slot = sE + E::at(yl, x, cq);
       shared_tile_sum(slot, px < G::M, wm, ks, acc[G::MTW - 1], [&](f32x4 sum) {
         f32x4 v = sum + bias;
-        if (ups && inside) v += ups_at_lds<HW>(sG, gy0, y, x, 4 * wn + q);
+        if (ups && inside) v += ups_at_lds<HW>(sG, gy0, y, x, cq);
         *reinterpret_cast<f32x4*>(slot) = inside ? lrelu4(v) : f32x4{0.f, 0.f, 0.f, 0.f};
       });
     }
@@ -601,26 +676,10 @@ __global__ __launch_bounds__(256, (FSGeom<HW, SR, STRIDE, BN, KF>::occ)) void pw
   __syncthreads();
 
   // ---- epilogue 2: depthwise 3x3 over the strip, + bd, LeakyReLU -> D ----
-  {
-    constexpr int HO = G::HO, NITEM = G::NQ * HO * G::RS;
-    const int oy_first = st * SR, rows_out = HO - oy_first < SR ? HO - oy_first : SR;
-    f32x4 wt[9];
-    int cq_of = -1;
-    for (int id = tid; id < NITEM; id += 256) {
-      const int cq = id % G::NQ, rest = id / G::NQ, ox = rest % HO, r0 = (rest / HO) * G::RPS;
-      if (r0 >= rows_out) continue;
-      if (cq != cq_of) {
-        const float* wq = wd + n0 + 4 * cq;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) wt[t] = *reinterpret_cast<const f32x4*>(wq + (size_t)t * N);
-        cq_of = cq;
-      }
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(bd + n0 + 4 * cq);
-      const int nrows = rows_out - r0 < G::RPS ? rows_out - r0 : G::RPS;
-      dw_run<E, STRIDE, HW, false>(sE, r0 * STRIDE, ox, cq, 0, wt, bv,
-                                   D + (((size_t)fr * HO + oy_first + r0) * HO + ox) * ldd + n0 + 4 * cq, (size_t)HO * ldd, nrows);
-    }
-  }
+  // (the strips divide the frame: every strip holds SR output rows; its first output is row st * SR of frame fr)
+  static_assert(G::HO % SR == 0, "whole strips");
+  dw_walk<E, BN, STRIDE, HW, SR, G::HO, G::RPS, 1, false>(sE, tid, 1, wd + n0, bd + n0, N,
+                                                           D + ((size_t)fr * G::HO + st * SR) * G::HO * ldd + n0, ldd);
 }
 
 // The K split of the frame-pair tile's shared pixel tile: with gemm_streamk = 0 (bits that do not depend on the batch: a frame
