@@ -405,8 +405,9 @@ int launch_cross_attention(const void* q, int ldq, const void* k, int ldk, const
 // the bf16 engine's attention core (attention_bf16.hip): q, k, v, res, out bf16; one workgroup per frame
 int launch_cross_attention_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* res, int ld_res,
                                 const float* gamma_dev, void* out, int ld_out, int batch, hipStream_t stream);
+// lo (bf16 only): write R(x - R(x)), the half of x the lo = 0 launch's bf16 image lost
 int launch_nchw_to_nhwc(const float* in, void* out, int batch, int c, int hw, hipStream_t stream,
-                        int dtype = DT_F32);
+                        int dtype = DT_F32, int lo = 0);
 int launch_crop_to_input(const unsigned char* crops, float* x, int batch, hipStream_t stream);
 int launch_pred_to_u8(const float* pred, unsigned char* out, int batch, hipStream_t stream);
 int launch_audio_window_gather(const float* features, int n_steps, const int* idx_dev, void* out, int batch,

@@ -217,7 +217,7 @@ struct Arena {
   enum Id {
     CAT4, CAT3, CAT2, CAT1, CATA, E1, E2, T0, U4, F, FM, U1, U2, U3, UG,
     A0, AC1, AC2, AC3, AC4, AC5, AC6, AE1, AE2,
-    H, TX, OX0, OX1, OX2, OX3, KX, KXF, P1Q, AO, Q, KV, EP1, EP2, COUNT
+    H, TX, OX0, OX1, OX2, OX3, KX, KXF, P1Q, AO, Q, KV, EP1, EP2, A0L, COUNT
   };
   Buf b[COUNT] = {
       {"cat4", 160 * 160 * 64, 0},  {"cat3", 80 * 80 * 128, 0},  {"cat2", 40 * 40 * 256, 0},
@@ -234,19 +234,23 @@ struct Arena {
       {"KX", 100 * 1024, 0},        {"KXF", 100 * 1024, 0},      {"P1Q", 100 * 576, 0},
       {"AO", 100 * 512, 0},         {"Q", 100 * 64, 0},          {"KV", 100 * kBlocks * kKV, 0},
       // skip_early: W1b . skip + b of up1.0 (20x20 x 1024) and up2.0 (40x40 x 512), small batches only
-      {"EP1", 400 * 1024, 0},       {"EP2", 1600 * 512, 0}};
+      {"EP1", 400 * 1024, 0},       {"EP2", 1600 * 512, 0},
+      // wenet, bf16 storage: the low half of the audio window, R(x - R(x)) (encode(): conv1's residual add); last, so that no other
+      // buffer moves
+      {"A0L", 0, 0}};
   // (the two skip_early buffers exist only for the batches that use them: 4.9 MB per frame)
   // wenet: the audio window is 256 x 16 x 32, conv1 / conv2 write 16x32 x 256 and expand to 16x32 x 512
-  Arena(const CasyncOptions& o, int batch, int mode = CASYNC_AUDIO_HUBERT) {
+  Arena(const CasyncOptions& o, int batch, int mode = CASYNC_AUDIO_HUBERT, int esz_ = 4) {
     b[E1].per_frame = b[E2].per_frame = max_unfused_expand(o);
     if (!skip_early_batch(o, batch)) b[EP1].per_frame = b[EP2].per_frame = 0;
     if (mode == CASYNC_AUDIO_WENET) {
       b[A0].per_frame = b[AC1].per_frame = 512 * 256;
       b[AE1].per_frame = b[AE2].per_frame = 512 * 512;
+      if (esz_ == 2) b[A0L].per_frame = 512 * 256;
     }
   }
   static int64_t bytes(const CasyncOptions& o, int batch, int esz = 4, int mode = CASYNC_AUDIO_HUBERT) {
-    Arena a(o, batch, mode);
+    Arena a(o, batch, mode, esz);
     int64_t tot = 0;
     for (auto& x : a.b) tot += (x.per_frame * batch + 63) / 64 * 64;
     return tot * (int64_t)esz;
@@ -629,7 +633,21 @@ struct Plan {
       // + ReLU to 10x10; conv6; conv7 straight into the audio half of cat([x5, a]) (no bn7 / relu7)
       r.run("audio.nchw_to_nhwc", 0, (4.0 + dtype_size(dt())) * B * 131072,
             [&] { return launch_nchw_to_nhwc(audio, ar[A::A0], B, 256, 512, r.s, dt()); });
-      ir(kAudioW[0], ar[A::A0], 256, ar[A::AC1], 256, AE1, AE2);
+      if (dt() == DT_BF16) {
+        // conv1 is a residual block on the network's fp32 input, and the reference keeps that sum in fp32 under bf16 autocast.  The
+        // bf16 window A0 feeds the expand conv; the residual add takes the window to 16 mantissa bits, A0 + A0L with A0L =
+        // R(x - R(x)): the project GEMM adds A0 behind its activation (post_res), then the running-sum output adds A0L to the fp32
+        // value and rounds ONCE into AC1.  (The GEMM's own C output, rounded before A0L, lands in the dead expand slot AE1.)
+        r.run("audio.nchw_to_nhwc_lo", 0, (4.0 + dtype_size(dt())) * B * 131072,
+              [&] { return launch_nchw_to_nhwc(audio, ar[A::A0L], B, 256, 512, r.s, dt(), 1); });
+        GemmEpilogue lo;
+        lo.acc_in = (const void*)ar[A::A0L];
+        lo.acc_out = (void*)ar[A::AC1];
+        lo.ld_acc = 256;
+        ir(kAudioW[0], ar[A::A0], 256, AE1, 256, AE1, AE2, &lo);
+      } else {
+        ir(kAudioW[0], ar[A::A0], 256, ar[A::AC1], 256, AE1, AE2);
+      }
       ir(kAudioW[1], ar[A::AC1], 256, ar[A::AC2], 256, AE1, AE2);
       conv3x3("audio.conv3", ar[A::AC2], "audio_model.conv3.w", ar[A::AC3], 16, 32, 256, 256, 1, 2, 1, 2);
       ir(kAudio[2], ar[A::AC3], 256, ar[A::AC4], 256, AE1, AE2);
@@ -1182,7 +1200,7 @@ static int run_forward(casync_handle h, const FwdArgs& A, hipStream_t caller, st
     Runner r;
     r.s = lane_stream(l);
     r.profile = serial;
-    Plan p{*h, Arena(o, A.batch, h->mode), r, bl};
+    Plan p{*h, Arena(o, A.batch, h->mode, esz), r, bl};
     p.lane = l;
     p.kv_in_encode = o.kv_early >= 2 || (o.kv_early == 1 && lanes == 1);
     p.skip_early = lanes == 1 && h->dtype == DT_F32 && skip_early_batch(o, A.batch) &&
@@ -1284,7 +1302,7 @@ int casync_profile_forward(casync_handle h, const float* x, const float* a, floa
 int64_t casync_tap(casync_handle h, const char* name, int batch, void* ws, void* dst, int64_t dst_floats,
                    casync_stream stream) {
   CASYNC_REQUIRE(h && name && ws && dst && batch > 0, "tap: bad args");
-  Arena ar(h->opt, batch, h->mode);
+  Arena ar(h->opt, batch, h->mode, dtype_size(h->dtype));
   ar.bind(ws, batch, dtype_size(h->dtype));
   using A = Arena;
   struct T { const char* n; Ptr p; int ld, c, rows; };

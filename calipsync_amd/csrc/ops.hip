@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const T* __restrict__ i
 template <typename T>
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ in,
                                                            T* __restrict__ out, int C, int HW,
-                                                           long long total) {
+                                                           long long total, int lo) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const int p = (int)(idx % HW);
@@ -249,6 +249,11 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
   const int b = (int)(t / c4n);
   const float* src = in + ((size_t)b * C + c) * HW + p;
   f32x4 v = {src[0], src[HW], src[2 * (size_t)HW], src[3 * (size_t)HW]};
+  if constexpr (sizeof(T) == 2) {
+    // lo: what the bf16 image of this launch's lo = 0 sibling lost -- x = R(x) + R(x - R(x)) to 16 mantissa bits (AudioConvWenet's
+    // conv1 is a residual block on the fp32 input: its residual add takes both halves, engine.hip encode())
+    if (lo) v = f32x4{v[0] - (float)(bf16_t)v[0], v[1] - (float)(bf16_t)v[1], v[2] - (float)(bf16_t)v[2], v[3] - (float)(bf16_t)v[3]};
+  }
   st4(out + ((size_t)b * HW + p) * C + c, v);
 }
 
@@ -683,14 +688,15 @@ int launch_upsample2x(const void* in, void* out, int ldc, int batch, int h, int 
                                    (const bf16_t*)in, (bf16_t*)out, ldc, h, wdt, c, total));
 }
 
-int launch_nchw_to_nhwc(const float* in, void* out, int batch, int c, int hw, hipStream_t stream, int dtype) {
+int launch_nchw_to_nhwc(const float* in, void* out, int batch, int c, int hw, hipStream_t stream, int dtype, int lo) {
   CASYNC_REQUIRE(in && out && batch > 0 && c % 4 == 0 && hw > 0, "nchw_to_nhwc: bad args");
+  CASYNC_REQUIRE(!lo || dtype == DT_BF16, "nchw_to_nhwc: the low half exists for bf16 storage only");
   const long long total = (long long)batch * (c / 4) * hw;
   DT_DISPATCH(dtype,
               return casync_launch(nchw_to_nhwc_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, stream, in,
-                                   (float*)out, c, hw, total),
+                                   (float*)out, c, hw, total, 0),
               return casync_launch(nchw_to_nhwc_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, stream, in,
-                                   (bf16_t*)out, c, hw, total));
+                                   (bf16_t*)out, c, hw, total, lo));
 }
 
 int launch_crop_to_input(const unsigned char* crops, float* x, int batch, hipStream_t stream) {
