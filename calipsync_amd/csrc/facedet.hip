@@ -16,10 +16,12 @@
 // extras 0 and 2 on the data-parallel fp32 ring GEMM (launch_rows_gemm): no stream-K, no K split.  No kernel here sums across
 // frames or uses an atomic: frame i of a batch has the bits of that frame forwarded alone.
 //
-// A handle made with precision 1 (casync_s3fd_create_ex) runs det_pass16 instead: the same walk on bf16 activations, with the
-// kernels of facedet_bf16.hip, the bf16 ring conv (launch_conv3x3_gemm, DT_BF16) and launch_rows_gemm_bf16 on a bf16 image of
-// the packed buffer made at weight load; the stem, the heads and det_decode_kernel keep fp32 weights and outputs.  The fp32
-// handle launches what it launched before that precision existed.
+// The network's order is written once, in det_pass<P>; a precision is a policy P (DetF32, DetBF16) that names its element type,
+// its launchers and the weight image its matrices come from.  A handle made with precision 1 (casync_s3fd_create_ex) runs
+// det_pass<DetBF16>: the same walk on bf16 activations, with the kernels of facedet_bf16.hip, the bf16 ring conv
+// (launch_conv3x3_gemm, DT_BF16) and launch_rows_gemm_bf16 on a bf16 image of the packed buffer made at weight load; the stem,
+// the heads and det_decode_kernel keep fp32 weights and outputs.  The fp32 handle launches what it launched before that
+// precision existed.
 #include <string.h>
 
 #include <mutex>
@@ -417,54 +419,31 @@ const DetLayout& det_layout() {
   return L;
 }
 
-// frames of one pass through the network: the whole batch unless its largest activation (conv1's, H W 64 floats a frame)
-// would reach 2 GiB
-int det_sub_batch(int batch, int H, int W) {
-  const long long per_frame = (long long)H * W * SC * 4;
+// frames of one pass through the network: the whole batch unless its largest activation (conv1's, H W 64 values a frame, of 4
+// bytes in fp32 and 2 in bf16) would reach 2 GiB
+int det_sub_batch(int batch, int H, int W, int bytes_per_value) {
+  const long long per_frame = (long long)H * W * SC * bytes_per_value;
   const long long fit = (kMaxBytes - 1) / per_frame;
   return (int)(fit < batch ? fit : batch);
 }
 
-// ... of the bf16 handle: the same rule on two bytes a value
-int det_sub_batch16(int batch, int H, int W) {
-  const long long per_frame = (long long)H * W * SC * 2;
-  const long long fit = (kMaxBytes - 1) / per_frame;
-  return (int)(fit < batch ? fit : batch);
-}
-
+// the arena of one pass: two activations and fc6's im2col matrix of T, fp32 loc / conf, every part on a 256-B boundary.  In
+// fp32 this is the rule in floats it replaces: round64(n) * 4 == (4 n + 255) / 256 * 256, so the offsets and the total are the same.
+template <class T>
 struct DetWs {
-  float *a, *b, *col, *loc, *conf;
-  int64_t floats;
-  DetWs(float* base, int nb, const DetGeom& G) {
-    int64_t off = 0;
-    auto take = [&](int64_t n) {
-      float* p = base ? base + off : nullptr;
-      off += round64(n);
-      return p;
-    };
-    const int64_t act = (int64_t)nb * G.H * G.W * SC;
-    a = take(act), b = take(act);
-    col = take((int64_t)nb * G.h[3] * G.w[3] * 9 * 512);
-    loc = take((int64_t)nb * G.off[6] * 4), conf = take((int64_t)nb * G.off[6] * 2);
-    floats = off;
-  }
-};
-
-// the bf16 handle's arena: two bf16 activations, fc6's bf16 im2col matrix, fp32 loc / conf (every part on a 256-B boundary)
-struct DetWs16 {
-  bf16_t *a, *b, *col;
+  T *a, *b, *col;
   float *loc, *conf;
   int64_t bytes;
-  DetWs16(char* base, int nb, const DetGeom& G) {
+  DetWs(void* base, int nb, const DetGeom& G) {
     int64_t off = 0;
     auto take = [&](int64_t n_bytes) {
-      char* p = base ? base + off : nullptr;
+      char* p = base ? static_cast<char*>(base) + off : nullptr;
       off += (n_bytes + 255) / 256 * 256;
       return p;
     };
-    const int64_t act = (int64_t)nb * G.H * G.W * SC * 2;
-    a = reinterpret_cast<bf16_t*>(take(act)), b = reinterpret_cast<bf16_t*>(take(act));
-    col = reinterpret_cast<bf16_t*>(take((int64_t)nb * G.h[3] * G.w[3] * 9 * 512 * 2));
+    const int64_t act = (int64_t)nb * G.H * G.W * SC * sizeof(T);
+    a = reinterpret_cast<T*>(take(act)), b = reinterpret_cast<T*>(take(act));
+    col = reinterpret_cast<T*>(take((int64_t)nb * G.h[3] * G.w[3] * 9 * 512 * sizeof(T)));
     loc = reinterpret_cast<float*>(take((int64_t)nb * G.off[6] * 16)), conf = reinterpret_cast<float*>(take((int64_t)nb * G.off[6] * 8));
     bytes = off;
   }
@@ -474,7 +453,7 @@ struct DetWs16 {
 
 struct casync_s3fd {
   int device = 0;
-  int precision = 0;             // 0 fp32, 1 bf16 (det_pass16)
+  int precision = 0;             // 0 fp32 (DetF32), 1 bf16 (DetBF16)
   PackedWeights pw;              // precision 1: the conv / GEMM matrices are read from the bf16 image
   hipEvent_t ev_fwd = nullptr;   // forward gate slot
 };
@@ -485,134 +464,113 @@ namespace {
     if (int st__ = (call)) return st__; \
   } while (0)
 
-// one pass of nb frames; `out` is the stage's tensor for these frames.  Returns after the stage asked for.
-int det_pass(const float* w, const void* x, bool u8, int nb, const DetGeom& G, const DetWs& ws, float* out, int stage, hipStream_t s) {
-  const DetLayout& L = det_layout();
-  const int P = G.off[6];
-  auto copy_out = [&](const float* src, int64_t floats) -> int {
-    CASYNC_CHECK_HIP(hipMemcpyAsync(out, src, (size_t)floats * 4, hipMemcpyDeviceToDevice, s));
+// A precision of the handle: the element type of the activations, the launchers of that type (named where their arguments are
+// what det_pass hands them, wrapped in a line where not) and the image the conv / GEMM matrices are read from.  What the network
+// does is in det_pass.
+struct DetF32 {
+  using T = float;
+  static constexpr auto stem = launch_det_stem;
+  static constexpr auto l2norm = launch_det_l2norm;
+  static constexpr auto maxpool = launch_det_maxpool;
+  static constexpr auto im2col = launch_det_im2col_dil;
+  static constexpr auto head = launch_det_head;
+  static const T* mats(const casync_s3fd* D) { return D->pw.w; }
+  static int conv3x3(const T* in, const T* w, T* out, int nb, int h, int wd, int cin, int cout, int stride, const GemmEpilogue& epi,
+                     hipStream_t s) {
+    return launch_conv3x3_gemm(in, w, out, cout, nb, h, wd, cin, cout, stride, stride, 1, epi, s);
+  }
+  static int dense(const T* a, int m, int k, const T* w, const float* bias, T* c, int n, hipStream_t s) {   // rows GEMM, ReLU pass
+    GemmEpilogue epi;
+    epi.bias = bias;
+    DT(launch_rows_gemm(a, k, w, c, n, m, n, k, epi, s));
+    return launch_det_relu(c, (long long)m * n, s);
+  }
+  static int tap_out(const T* src, float* out, int64_t n, hipStream_t s) {
+    CASYNC_CHECK_HIP(hipMemcpyAsync(out, src, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     return CASYNC_OK;
+  }
+};
+
+// the contract: DESIGN section 8d, "bf16 precision"; a tap of a bf16 stage is widened
+struct DetBF16 {
+  using T = bf16_t;
+  static constexpr auto stem = launch_det16_stem;
+  static constexpr auto l2norm = launch_det16_l2norm;
+  static constexpr auto maxpool = launch_det16_maxpool;
+  static constexpr auto im2col = launch_det16_im2col_dil;
+  static constexpr auto head = launch_det16_head;
+  static constexpr auto tap_out = launch_det16_widen;
+  static const T* mats(const casync_s3fd* D) { return D->pw.w16; }
+  static int conv3x3(const T* in, const T* w, T* out, int nb, int h, int wd, int cin, int cout, int stride, const GemmEpilogue& epi,
+                     hipStream_t s) {
+    return launch_conv3x3_gemm(in, w, out, cout, nb, h, wd, cin, cout, stride, stride, 1, epi, s, DT_BF16);
+  }
+  static int dense(const T* a, int m, int k, const T* w, const float* bias, T* c, int n, hipStream_t s) {
+    DT(launch_rows_gemm_bf16(a, k, w, bias, c, n, m, n, k, s));
+    return launch_det16_relu(c, (long long)m * n, s);
+  }
+};
+
+// One pass of nb frames in the precision P; `out` is the stage's tensor for these frames.  Returns after the stage asked for.
+// w is the fp32 packed buffer (biases, stem, heads), wm the image the 3x3 conv and GEMM matrices come from.
+template <class P>
+int det_pass(const casync_s3fd* D, const void* x, bool u8, int nb, const DetGeom& G, const DetWs<typename P::T>& ws, float* out, int stage,
+             hipStream_t s) {
+  using T = typename P::T;
+  const DetLayout& L = det_layout();
+  const float* w = D->pw.w;
+  const T* wm = P::mats(D);
+  const int np = G.off[6];
+  auto head = [&](int k, const T* src) -> int {
+    return P::head(src, w + L.head_w[k], w + L.head_b[k], ws.loc, ws.conf, nb, G.h[k], G.w[k], kSrcC[k], np, G.off[k], k == 0, s);
   };
-  auto head = [&](int k, const float* src) -> int {
-    return launch_det_head(src, w + L.head_w[k], w + L.head_b[k], ws.loc, ws.conf, nb, G.h[k], G.w[k], kSrcC[k], P, G.off[k], k == 0, s);
+  auto relu_bias = [&](int64_t b_off) {
+    GemmEpilogue epi;
+    epi.bias = w + b_off;
+    epi.act = 2;
+    return epi;
   };
-  float *cur = ws.a, *nxt = ws.b;
-  DT(launch_det_stem(x, u8, w + L.stem_w, w + L.stem_b, cur, nb, G.H, G.W, s));
+  T *cur = ws.a, *nxt = ws.b;
+  DT(P::stem(x, u8, w + L.stem_w, w + L.stem_b, cur, nb, G.H, G.W, s));
   int h = G.H, wd = G.W;
   for (int i = 0; i < kNVgg; ++i) {
     const VggStep& v = kVgg[i];
-    GemmEpilogue epi;
-    epi.bias = w + L.vgg_b[i];
-    epi.act = 2;
-    DT(launch_conv3x3_gemm(cur, w + L.vgg_w[i], nxt, v.c.cout, nb, h, wd, v.c.cin, v.c.cout, 1, 1, 1, epi, s));
+    DT(P::conv3x3(cur, wm + L.vgg_w[i], nxt, nb, h, wd, v.c.cin, v.c.cout, 1, relu_bias(L.vgg_b[i]), s));
     std::swap(cur, nxt);
-    if (v.stage == stage) return copy_out(cur, (int64_t)nb * h * wd * v.c.cout);
+    if (v.stage == stage) return P::tap_out(cur, out, (int64_t)nb * h * wd * v.c.cout, s);
     if (v.source >= 0) {   // the normalised map feeds the two heads only
-      DT(launch_det_l2norm(cur, nxt, (long long)nb * h * wd, v.c.cout, s));
+      DT(P::l2norm(cur, nxt, (long long)nb * h * wd, v.c.cout, s));
       DT(head(v.source, nxt));
     }
     if (v.pool) {
-      DT(launch_det_maxpool(cur, nxt, nb, h, wd, v.c.cout, v.pool == 2, s));
+      DT(P::maxpool(cur, nxt, nb, h, wd, v.c.cout, v.pool == 2, s));
       std::swap(cur, nxt);
       h = v.pool == 2 ? (h + 1) / 2 : h / 2, wd = v.pool == 2 ? (wd + 1) / 2 : wd / 2;
     }
   }
   // a 1x1 conv (or fc6 on its im2col matrix) + ReLU over m pixels
-  auto dense = [&](const float* a, int m, int k, int64_t w_off, int64_t b_off, float* c, int n) -> int {
-    GemmEpilogue epi;
-    epi.bias = w + b_off;
-    DT(launch_rows_gemm(a, k, w + w_off, c, n, m, n, k, epi, s));
-    return launch_det_relu(c, (long long)m * n, s);
+  auto dense = [&](const T* a, int m, int k, int64_t w_off, int64_t b_off, T* c, int n) -> int {
+    return P::dense(a, m, k, wm + w_off, w + b_off, c, n, s);
   };
   const int m = nb * h * wd;   // pixels at 1/32 resolution
-  DT(launch_det_im2col_dil(cur, ws.col, nb, h, wd, 512, 6, s));
+  DT(P::im2col(cur, ws.col, nb, h, wd, 512, 6, s));
   DT(dense(ws.col, m, 9 * 512, L.fc6_w, L.fc6_b, nxt, 1024));
   std::swap(cur, nxt);
-  if (stage == ST_FC6) return copy_out(cur, (int64_t)m * 1024);
+  if (stage == ST_FC6) return P::tap_out(cur, out, (int64_t)m * 1024, s);
   DT(dense(cur, m, 1024, L.fc7_w, L.fc7_b, nxt, 1024));
   std::swap(cur, nxt);
-  if (stage == ST_FC7) return copy_out(cur, (int64_t)m * 1024);
+  if (stage == ST_FC7) return P::tap_out(cur, out, (int64_t)m * 1024, s);
   DT(head(3, cur));
   const int ex_c[5] = {1024, 256, 512, 128, 256};
   for (int j = 0; j < 2; ++j) {   // extras 2j (1x1) and 2j + 1 (3x3, stride 2, pad 1): nets.py:135-138
     DT(dense(cur, nb * G.h[3 + j] * G.w[3 + j], ex_c[2 * j], L.ex_w[2 * j], L.ex_b[2 * j], nxt, ex_c[2 * j + 1]));
-    GemmEpilogue epi;
-    epi.bias = w + L.ex_b[2 * j + 1];
-    epi.act = 2;
-    DT(launch_conv3x3_gemm(nxt, w + L.ex_w[2 * j + 1], cur, ex_c[2 * j + 2], nb, G.h[3 + j], G.w[3 + j], ex_c[2 * j + 1], ex_c[2 * j + 2], 2, 2,
-                           1, epi, s));
-    const int64_t n_out = (int64_t)nb * G.h[4 + j] * G.w[4 + j] * ex_c[2 * j + 2];
-    if (stage == ST_CONV6_2 + j) return copy_out(cur, n_out);
+    DT(P::conv3x3(nxt, wm + L.ex_w[2 * j + 1], cur, nb, G.h[3 + j], G.w[3 + j], ex_c[2 * j + 1], ex_c[2 * j + 2], 2,
+                  relu_bias(L.ex_b[2 * j + 1]), s));
+    if (stage == ST_CONV6_2 + j) return P::tap_out(cur, out, (int64_t)nb * G.h[4 + j] * G.w[4 + j] * ex_c[2 * j + 2], s);
     DT(head(4 + j, cur));
   }
-  if (stage == ST_LOC) return copy_out(ws.loc, (int64_t)nb * P * 4);
-  if (stage == ST_CONF) return copy_out(ws.conf, (int64_t)nb * P * 2);
-  return launch_det_decode(ws.loc, ws.conf, out, nb, G, s);
-}
-
-// det_pass on bf16 activations (the contract: DESIGN section 8d, "bf16 precision").  w16 is the bf16 image of w; a tap of a
-// bf16 stage is widened into `out`.
-int det_pass16(const float* w, const bf16_t* w16, const void* x, bool u8, int nb, const DetGeom& G, const DetWs16& ws, float* out, int stage,
-               hipStream_t s) {
-  const DetLayout& L = det_layout();
-  const int P = G.off[6];
-  auto widen_out = [&](const bf16_t* src, int64_t n) -> int { return launch_det16_widen(src, out, n, s); };
-  auto copy_out = [&](const float* src, int64_t floats) -> int {
-    CASYNC_CHECK_HIP(hipMemcpyAsync(out, src, (size_t)floats * 4, hipMemcpyDeviceToDevice, s));
-    return CASYNC_OK;
-  };
-  auto head = [&](int k, const bf16_t* src) -> int {
-    return launch_det16_head(src, w + L.head_w[k], w + L.head_b[k], ws.loc, ws.conf, nb, G.h[k], G.w[k], kSrcC[k], P, G.off[k], k == 0, s);
-  };
-  bf16_t *cur = ws.a, *nxt = ws.b;
-  DT(launch_det16_stem(x, u8, w + L.stem_w, w + L.stem_b, cur, nb, G.H, G.W, s));
-  int h = G.H, wd = G.W;
-  for (int i = 0; i < kNVgg; ++i) {
-    const VggStep& v = kVgg[i];
-    GemmEpilogue epi;
-    epi.bias = w + L.vgg_b[i];
-    epi.act = 2;
-    DT(launch_conv3x3_gemm(cur, w16 + L.vgg_w[i], nxt, v.c.cout, nb, h, wd, v.c.cin, v.c.cout, 1, 1, 1, epi, s, DT_BF16));
-    std::swap(cur, nxt);
-    if (v.stage == stage) return widen_out(cur, (int64_t)nb * h * wd * v.c.cout);
-    if (v.source >= 0) {
-      DT(launch_det16_l2norm(cur, nxt, (long long)nb * h * wd, v.c.cout, s));
-      DT(head(v.source, nxt));
-    }
-    if (v.pool) {
-      DT(launch_det16_maxpool(cur, nxt, nb, h, wd, v.c.cout, v.pool == 2, s));
-      std::swap(cur, nxt);
-      h = v.pool == 2 ? (h + 1) / 2 : h / 2, wd = v.pool == 2 ? (wd + 1) / 2 : wd / 2;
-    }
-  }
-  // a 1x1 conv (or fc6 on its im2col matrix) on the bf16 rows GEMM (bias only), then the ReLU pass
-  auto dense = [&](const bf16_t* a, int m, int k, int64_t w_off, int64_t b_off, bf16_t* c, int n) -> int {
-    DT(launch_rows_gemm_bf16(a, k, w16 + w_off, w + b_off, c, n, m, n, k, s));
-    return launch_det16_relu(c, (long long)m * n, s);
-  };
-  const int m = nb * h * wd;
-  DT(launch_det16_im2col_dil(cur, ws.col, nb, h, wd, 512, 6, s));
-  DT(dense(ws.col, m, 9 * 512, L.fc6_w, L.fc6_b, nxt, 1024));
-  std::swap(cur, nxt);
-  if (stage == ST_FC6) return widen_out(cur, (int64_t)m * 1024);
-  DT(dense(cur, m, 1024, L.fc7_w, L.fc7_b, nxt, 1024));
-  std::swap(cur, nxt);
-  if (stage == ST_FC7) return widen_out(cur, (int64_t)m * 1024);
-  DT(head(3, cur));
-  const int ex_c[5] = {1024, 256, 512, 128, 256};
-  for (int j = 0; j < 2; ++j) {
-    DT(dense(cur, nb * G.h[3 + j] * G.w[3 + j], ex_c[2 * j], L.ex_w[2 * j], L.ex_b[2 * j], nxt, ex_c[2 * j + 1]));
-    GemmEpilogue epi;
-    epi.bias = w + L.ex_b[2 * j + 1];
-    epi.act = 2;
-    DT(launch_conv3x3_gemm(nxt, w16 + L.ex_w[2 * j + 1], cur, ex_c[2 * j + 2], nb, G.h[3 + j], G.w[3 + j], ex_c[2 * j + 1], ex_c[2 * j + 2], 2,
-                           2, 1, epi, s, DT_BF16));
-    const int64_t n_out = (int64_t)nb * G.h[4 + j] * G.w[4 + j] * ex_c[2 * j + 2];
-    if (stage == ST_CONV6_2 + j) return widen_out(cur, n_out);
-    DT(head(4 + j, cur));
-  }
-  if (stage == ST_LOC) return copy_out(ws.loc, (int64_t)nb * P * 4);
-  if (stage == ST_CONF) return copy_out(ws.conf, (int64_t)nb * P * 2);
+  if (stage == ST_LOC) return DetF32::tap_out(ws.loc, out, (int64_t)nb * np * 4, s);   // loc, conf and det are fp32 in both
+  if (stage == ST_CONF) return DetF32::tap_out(ws.conf, out, (int64_t)nb * np * 2, s);
   return launch_det_decode(ws.loc, ws.conf, out, nb, G, s);
 }
 
@@ -629,6 +587,28 @@ int64_t det_stage_floats(const DetGeom& G, int stage) {   // per frame
   return (int64_t)G.off[6] * 5;
 }
 
+// the checked batch in passes of nb frames at the most, in the arena of the precision P
+template <class P>
+int det_batches(casync_s3fd* D, const void* x, bool u8, int batch, int nb, const DetGeom& G, float* out, void* ws_dev, int64_t ws_bytes,
+                hipStream_t s, int stage) {
+  const DetWs<typename P::T> ws(ws_dev, nb, G);
+  if (ws_bytes < ws.bytes) {
+    casync_set_error("s3fd forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)ws.bytes);
+    return CASYNC_ERR_STATE;
+  }
+  DeviceGuard guard(D->device);
+  CASYNC_CHECK_HIP(guard.err);
+  std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
+  if (int st = casync_gate_enter(D->device, D, &D->ev_fwd, s, &gate_lock)) return st;
+  const int64_t in_frame = (int64_t)G.H * G.W * 3 * (u8 ? 1 : 4), out_frame = det_stage_floats(G, stage);
+  // every pass takes the tile choices of its own frame count; the kernels' sums do not depend on it (see the header comment)
+  for (int b0 = 0; b0 < batch; b0 += nb) {
+    const int n = batch - b0 < nb ? batch - b0 : nb;
+    DT(det_pass<P>(D, static_cast<const char*>(x) + (size_t)b0 * in_frame, u8, n, G, ws, out + (size_t)b0 * out_frame, stage, s));
+  }
+  return CASYNC_OK;
+}
+
 int det_run(casync_s3fd* D, const void* x, bool u8, int batch, int H, int W, float* out, void* ws_dev, int64_t ws_bytes, hipStream_t s,
             int stage) {
   CASYNC_REQUIRE(D, "s3fd forward: null handle");
@@ -639,31 +619,13 @@ int det_run(casync_s3fd* D, const void* x, bool u8, int batch, int H, int W, flo
   DetGeom G;
   CASYNC_REQUIRE(det_geometry(H, W, &G), "s3fd forward: frames of %d x %d pool to nothing (or exceed 8192): the network needs 16 x 16 at least",
                  H, W);
-  const int nb = h16 ? det_sub_batch16(batch, H, W) : det_sub_batch(batch, H, W);
+  const int nb = det_sub_batch(batch, H, W, h16 ? 2 : 4);
   CASYNC_REQUIRE(batch == 0 || nb >= 1, "s3fd forward: one %d x %d frame alone has an activation of 2 GiB or more", H, W);
   if (batch == 0) return CASYNC_OK;
   CASYNC_REQUIRE(x && out && ws_dev, "s3fd forward: null pointer");
   CASYNC_REQUIRE((uintptr_t)x % (u8 ? 1 : 4) == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws_dev % 256 == 0, "s3fd forward: alignment");
-  DetWs ws(static_cast<float*>(ws_dev), nb, G);
-  DetWs16 ws16(static_cast<char*>(ws_dev), nb, G);
-  const int64_t need = h16 ? ws16.bytes : ws.floats * 4;
-  if (ws_bytes < need) {
-    casync_set_error("s3fd forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)need);
-    return CASYNC_ERR_STATE;
-  }
-  DeviceGuard guard(D->device);
-  CASYNC_CHECK_HIP(guard.err);
-  std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
-  if (int st = casync_gate_enter(D->device, D, &D->ev_fwd, s, &gate_lock)) return st;
-  const int64_t in_frame = (int64_t)H * W * 3 * (u8 ? 1 : 4), out_frame = det_stage_floats(G, stage);
-  // every pass takes the tile choices of its own frame count; the kernels' sums do not depend on it (see the header comment)
-  for (int b0 = 0; b0 < batch; b0 += nb) {
-    const int n = batch - b0 < nb ? batch - b0 : nb;
-    const void* xb = static_cast<const char*>(x) + (size_t)b0 * in_frame;
-    if (h16) DT(det_pass16(D->pw.w, D->pw.w16, xb, u8, n, G, ws16, out + (size_t)b0 * out_frame, stage, s));
-    else DT(det_pass(D->pw.w, xb, u8, n, G, ws, out + (size_t)b0 * out_frame, stage, s));
-  }
-  return CASYNC_OK;
+  return h16 ? det_batches<DetBF16>(D, x, u8, batch, nb, G, out, ws_dev, ws_bytes, s, stage)
+             : det_batches<DetF32>(D, x, u8, batch, nb, G, out, ws_dev, ws_bytes, s, stage);
 }
 #undef DT
 }  // namespace
@@ -689,12 +651,9 @@ int casync_s3fd_map_size(int h, int w, int k, int* map_h, int* map_w) {
 int64_t casync_s3fd_workspace_bytes_ex(int precision, int batch, int h, int w) {
   DetGeom G;
   if ((precision != 0 && precision != 1) || batch < 1 || batch > 65536 || !det_geometry(h, w, &G)) return 0;
-  if (precision == 1) {
-    const int nb = det_sub_batch16(batch, h, w);
-    return nb >= 1 ? DetWs16(nullptr, nb, G).bytes : 0;
-  }
-  const int nb = det_sub_batch(batch, h, w);
-  return nb >= 1 ? DetWs(nullptr, nb, G).floats * 4 : 0;
+  const int nb = det_sub_batch(batch, h, w, precision == 1 ? 2 : 4);
+  if (nb < 1) return 0;
+  return precision == 1 ? DetWs<bf16_t>(nullptr, nb, G).bytes : DetWs<float>(nullptr, nb, G).bytes;
 }
 int64_t casync_s3fd_workspace_bytes(int batch, int h, int w) { return casync_s3fd_workspace_bytes_ex(0, batch, h, w); }
 

@@ -304,44 +304,52 @@ int launch_attention(const float* qkv, float* out, int batch, int T, hipStream_t
 // ---- packed layout ---------------------------------------------------------------------------------------------------
 constexpr int kMaxLayers = 48;
 
-const PackedLayout* hb_layout(int layers) {   // null outside 1..kMaxLayers
-  static PackedLayout cache[kMaxLayers + 1];
-  static std::once_flag once[kMaxLayers + 1];
-  if (layers < 1 || layers > kMaxLayers) return nullptr;
-  std::call_once(once[layers], [layers] {
-    PackedLayout& L = cache[layers];
+// the packed layout of a model of `layers` layers with every tensor's offset resolved once (as DetLayout of facedet.hip): a
+// forward builds no name and searches nothing
+struct HbLayout {
+  struct Conv {
+    int64_t w, b, g, be;   // conv weight and bias, LayerNorm gain and bias
+  };
+  struct Layer {
+    int64_t ln1_g, ln1_b, qkv_w, qkv_b, o_w, o_b, ln2_g, ln2_b, ff1_w, ff1_b, ff2_w, ff2_b;
+  };
+  PackedLayout packed;
+  Conv fe[7];
+  int64_t fp_ln_g, fp_ln_b, fp_w, fp_b, pos_w, pos_b, enc_ln_g, enc_ln_b;
+  std::vector<Layer> layer;
+  explicit HbLayout(int layers) : layer(layers) {
+    auto add = [this](const std::string& n, int64_t size) { return packed.add(n, size); };
     for (int i = 0; i < 7; ++i) {
-      const std::string p = "fe.conv" + std::to_string(i);
-      L.add(p + ".w", (int64_t)kConvC * (i ? kConvC : 1) * kConvK[i]);   // [cout][tap][cin]
-      L.add(p + ".b", kConvC);
-      L.add("fe.ln" + std::to_string(i) + ".g", kConvC);
-      L.add("fe.ln" + std::to_string(i) + ".b", kConvC);
+      const std::string p = "fe.conv" + std::to_string(i), ln = "fe.ln" + std::to_string(i);
+      fe[i].w = add(p + ".w", (int64_t)kConvC * (i ? kConvC : 1) * kConvK[i]);   // [cout][tap][cin]
+      fe[i].b = add(p + ".b", kConvC);
+      fe[i].g = add(ln + ".g", kConvC), fe[i].be = add(ln + ".b", kConvC);
     }
-    L.add("fp.ln.g", kConvC);
-    L.add("fp.ln.b", kConvC);
-    L.add("fp.w", (int64_t)kHid * kConvC);
-    L.add("fp.b", kHid);
-    L.add("pos.w", (int64_t)kPosG * kPosK * kPosC * kPosC);   // [group][tap][n][c], weight norm folded
-    L.add("pos.b", kHid);
+    fp_ln_g = add("fp.ln.g", kConvC), fp_ln_b = add("fp.ln.b", kConvC);
+    fp_w = add("fp.w", (int64_t)kHid * kConvC), fp_b = add("fp.b", kHid);
+    pos_w = add("pos.w", (int64_t)kPosG * kPosK * kPosC * kPosC);   // [group][tap][n][c], weight norm folded
+    pos_b = add("pos.b", kHid);
     for (int l = 0; l < layers; ++l) {
       const std::string p = "layer" + std::to_string(l);
-      L.add(p + ".ln1.g", kHid);
-      L.add(p + ".ln1.b", kHid);
-      L.add(p + ".qkv.w", (int64_t)3 * kHid * kHid);   // [q | k | v][1024], q rows scaled by 1/8
-      L.add(p + ".qkv.b", 3 * kHid);
-      L.add(p + ".o.w", (int64_t)kHid * kHid);
-      L.add(p + ".o.b", kHid);
-      L.add(p + ".ln2.g", kHid);
-      L.add(p + ".ln2.b", kHid);
-      L.add(p + ".ff1.w", (int64_t)kFF * kHid);
-      L.add(p + ".ff1.b", kFF);
-      L.add(p + ".ff2.w", (int64_t)kHid * kFF);
-      L.add(p + ".ff2.b", kHid);
+      Layer& y = layer[l];
+      y.ln1_g = add(p + ".ln1.g", kHid), y.ln1_b = add(p + ".ln1.b", kHid);
+      y.qkv_w = add(p + ".qkv.w", (int64_t)3 * kHid * kHid);   // [q | k | v][1024], q rows scaled by 1/8
+      y.qkv_b = add(p + ".qkv.b", 3 * kHid);
+      y.o_w = add(p + ".o.w", (int64_t)kHid * kHid), y.o_b = add(p + ".o.b", kHid);
+      y.ln2_g = add(p + ".ln2.g", kHid), y.ln2_b = add(p + ".ln2.b", kHid);
+      y.ff1_w = add(p + ".ff1.w", (int64_t)kFF * kHid), y.ff1_b = add(p + ".ff1.b", kFF);
+      y.ff2_w = add(p + ".ff2.w", (int64_t)kHid * kFF), y.ff2_b = add(p + ".ff2.b", kHid);
     }
-    L.add("enc.ln.g", kHid);
-    L.add("enc.ln.b", kHid);
-  });
-  return &cache[layers];
+    enc_ln_g = add("enc.ln.g", kHid), enc_ln_b = add("enc.ln.b", kHid);
+  }
+};
+
+const HbLayout* hb_layout(int layers) {   // null outside 1..kMaxLayers; built on first use, kept for the process
+  static const HbLayout* cache[kMaxLayers + 1];
+  static std::once_flag once[kMaxLayers + 1];
+  if (layers < 1 || layers > kMaxLayers) return nullptr;
+  std::call_once(once[layers], [layers] { cache[layers] = new HbLayout(layers); });
+  return cache[layers];
 }
 
 // time steps after each feature-encoder conv; T[7] = tokens (0 when the waveform is shorter than one receptive field)
@@ -397,12 +405,12 @@ struct HbWs16 {
 struct casync_hubert {
   int device = 0;
   int layers = 0;
-  int dtype = DT_F32;         // DT_BF16: the bf16 precision (hb_run16)
-  PackedWeights pw;           // DT_BF16: the GEMM weight matrices are read from the bf16 image
-  const bf16_t* W16(const std::string& n) const { return pw.w16 + hb_layout(layers)->off(n); }
-  hipEvent_t ev_fwd = nullptr;   // FwdGate slot
-  const float* W(const char* n) const { return pw.w + hb_layout(layers)->off(n); }
-  const float* W(const std::string& n) const { return pw.w + hb_layout(layers)->off(n); }
+  int dtype = DT_F32;              // DT_BF16: the bf16 precision (hb_walk16)
+  const HbLayout* lay = nullptr;   // hb_layout(layers), set at create
+  PackedWeights pw;                // DT_BF16: the GEMM weight matrices are read from the bf16 image
+  hipEvent_t ev_fwd = nullptr;     // FwdGate slot
+  const float* w(int64_t off) const { return pw.w + off; }   // off: a member of *lay
+  const bf16_t* w16(int64_t off) const { return pw.w16 + off; }
 };
 
 namespace {
@@ -416,179 +424,160 @@ int gemm(const float* a, int lda, const float* w, const float* bias, float* c, i
   return launch_rows_gemm(a, lda, w, c, ldc, m, n, k, e, s);
 }
 
-// stage 0: final hidden states [B,T,1024]; 1: conv-stack output [B,T,512]; 2: input to layer 0 [B,T,1024];
-// 3: hidden states after `n_layers` layers, before the final LayerNorm [B,T,1024]
-int hb_run(casync_hubert* H, const float* wave, int batch, int64_t S, float* out, void* ws_dev, int64_t ws_bytes, hipStream_t s,
-           int stage, int n_layers) {
-  CASYNC_REQUIRE(H && wave && out && ws_dev, "hubert forward: null pointer");
-  CASYNC_REQUIRE(H->pw.w, "hubert forward: weights not loaded");
-  CASYNC_REQUIRE(batch > 0 && batch <= 65535, "hubert forward: batch %d", batch);
-  CASYNC_REQUIRE(S < (1ll << 31), "hubert forward: %lld samples", (long long)S);
-  const HbGeom G(S);
-  CASYNC_REQUIRE(G.tokens() >= 1, "hubert forward: %lld samples give no token (at least 400 are needed)", (long long)S);
-  CASYNC_REQUIRE(stage >= 0 && stage <= 3, "hubert forward: stage %d", stage);
-  CASYNC_REQUIRE(n_layers >= 0 && n_layers <= H->layers, "hubert forward: %d layers of %d", n_layers, H->layers);
-  CASYNC_REQUIRE((uintptr_t)wave % 4 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws_dev % 16 == 0, "hubert forward: alignment");
-  HbWs ws(static_cast<float*>(ws_dev), batch, G);
-  if (ws_bytes < ws.floats * 4) {
-    casync_set_error("hubert forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)ws.floats * 4);
-    return CASYNC_ERR_STATE;
-  }
-  const int T = (int)G.tokens(), M = batch * T;
-  DeviceGuard guard(H->device);
-  CASYNC_CHECK_HIP(guard.err);
-  std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
-  if (int st = casync_gate_enter(H->device, H, &H->ev_fwd, s, &gate_lock)) return st;
-#define HB(call)                       \
-  do {                                 \
+int copy_out(float* out, const float* src, size_t floats, hipStream_t s) {
+  CASYNC_CHECK_HIP(hipMemcpyAsync(out, src, floats * 4, hipMemcpyDeviceToDevice, s));
+  return CASYNC_OK;
+}
+
+#define HB(call)                        \
+  do {                                  \
     if (int st__ = (call)) return st__; \
   } while (0)
+
+// The fp32 walk of a forward hb_run has checked; stage and n_layers as there.
+int hb_walk32(const casync_hubert* H, const float* wave, int batch, const HbGeom& G, float* out, const HbWs& ws, hipStream_t s, int stage,
+              int n_layers) {
+  const HbLayout& L = *H->lay;
+  const int T = (int)G.tokens(), M = batch * T;
   // feature encoder: conv0 -> a, then ping-pong a <-> b
-  HB(launch_conv0(wave, batch, (int)S, H->W("fe.conv0.w"), H->W("fe.conv0.b"), H->W("fe.ln0.g"), H->W("fe.ln0.b"), ws.a, s));
+  HB(launch_conv0(wave, batch, (int)G.t[0], H->w(L.fe[0].w), H->w(L.fe[0].b), H->w(L.fe[0].g), H->w(L.fe[0].be), ws.a, s));
   float *cur = ws.a, *nxt = ws.b;
   for (int i = 1; i < 7; ++i) {
     const int tin = (int)G.t[i], tout = (int)G.t[i + 1];
-    const std::string p = "fe.conv" + std::to_string(i), ln = "fe.ln" + std::to_string(i);
+    const HbLayout::Conv& c = L.fe[i];
     for (int b = 0; b < batch; ++b)
-      HB(gemm(cur + (size_t)b * tin * kConvC, kConvS[i] * kConvC, H->W(p + ".w"), H->W(p + ".b"), nxt + (size_t)b * tout * kConvC,
-              kConvC, tout, kConvC, kConvK[i] * kConvC, 0, nullptr, s));
-    HB(launch_layernorm(nxt, kConvC, nxt, kConvC, batch * tout, kConvC, H->W(ln + ".g"), H->W(ln + ".b"), kEps, true, s));
+      HB(gemm(cur + (size_t)b * tin * kConvC, kConvS[i] * kConvC, H->w(c.w), H->w(c.b), nxt + (size_t)b * tout * kConvC, kConvC, tout,
+              kConvC, kConvK[i] * kConvC, 0, nullptr, s));
+    HB(launch_layernorm(nxt, kConvC, nxt, kConvC, batch * tout, kConvC, H->w(c.g), H->w(c.be), kEps, true, s));
     float* t = cur;
     cur = nxt, nxt = t;
   }
-  if (stage == 1) {
-    CASYNC_CHECK_HIP(hipMemcpyAsync(out, cur, (size_t)M * kConvC * 4, hipMemcpyDeviceToDevice, s));
-    return CASYNC_OK;
-  }
+  if (stage == 1) return copy_out(out, cur, (size_t)M * kConvC, s);
   // feature projection, positional conv
-  HB(launch_layernorm(cur, kConvC, nxt, kConvC, M, kConvC, H->W("fp.ln.g"), H->W("fp.ln.b"), kEps, false, s));
-  HB(gemm(nxt, kConvC, H->W("fp.w"), H->W("fp.b"), ws.x, kHid, M, kHid, kConvC, 0, nullptr, s));
-  HB(launch_posconv(ws.x, H->W("pos.w"), H->W("pos.b"), ws.h, batch, T, s));
-  if (stage == 2) {
-    CASYNC_CHECK_HIP(hipMemcpyAsync(out, ws.h, (size_t)M * kHid * 4, hipMemcpyDeviceToDevice, s));
-    return CASYNC_OK;
-  }
+  HB(launch_layernorm(cur, kConvC, nxt, kConvC, M, kConvC, H->w(L.fp_ln_g), H->w(L.fp_ln_b), kEps, false, s));
+  HB(gemm(nxt, kConvC, H->w(L.fp_w), H->w(L.fp_b), ws.x, kHid, M, kHid, kConvC, 0, nullptr, s));
+  HB(launch_posconv(ws.x, H->w(L.pos_w), H->w(L.pos_b), ws.h, batch, T, s));
+  if (stage == 2) return copy_out(out, ws.h, (size_t)M * kHid, s);
   const int nl = stage == 3 ? n_layers : H->layers;
   for (int l = 0; l < nl; ++l) {
-    const std::string p = "layer" + std::to_string(l);
-    HB(launch_layernorm(ws.h, kHid, ws.x, kHid, M, kHid, H->W(p + ".ln1.g"), H->W(p + ".ln1.b"), kEps, false, s));
-    HB(gemm(ws.x, kHid, H->W(p + ".qkv.w"), H->W(p + ".qkv.b"), ws.big, 3 * kHid, M, 3 * kHid, kHid, 0, nullptr, s));
+    const HbLayout::Layer& y = L.layer[l];
+    HB(launch_layernorm(ws.h, kHid, ws.x, kHid, M, kHid, H->w(y.ln1_g), H->w(y.ln1_b), kEps, false, s));
+    HB(gemm(ws.x, kHid, H->w(y.qkv_w), H->w(y.qkv_b), ws.big, 3 * kHid, M, 3 * kHid, kHid, 0, nullptr, s));
     HB(launch_attention(ws.big, ws.x, batch, T, s));
-    HB(gemm(ws.x, kHid, H->W(p + ".o.w"), H->W(p + ".o.b"), ws.h, kHid, M, kHid, kHid, 0, ws.h, s));
-    HB(launch_layernorm(ws.h, kHid, ws.x, kHid, M, kHid, H->W(p + ".ln2.g"), H->W(p + ".ln2.b"), kEps, false, s));
-    HB(gemm(ws.x, kHid, H->W(p + ".ff1.w"), H->W(p + ".ff1.b"), ws.big, kFF, M, kFF, kHid, 3, nullptr, s));
-    HB(gemm(ws.big, kFF, H->W(p + ".ff2.w"), H->W(p + ".ff2.b"), ws.h, kHid, M, kHid, kFF, 0, ws.h, s));
+    HB(gemm(ws.x, kHid, H->w(y.o_w), H->w(y.o_b), ws.h, kHid, M, kHid, kHid, 0, ws.h, s));
+    HB(launch_layernorm(ws.h, kHid, ws.x, kHid, M, kHid, H->w(y.ln2_g), H->w(y.ln2_b), kEps, false, s));
+    HB(gemm(ws.x, kHid, H->w(y.ff1_w), H->w(y.ff1_b), ws.big, kFF, M, kFF, kHid, 3, nullptr, s));
+    HB(gemm(ws.big, kFF, H->w(y.ff2_w), H->w(y.ff2_b), ws.h, kHid, M, kHid, kFF, 0, ws.h, s));
   }
-  if (stage == 3) {
-    CASYNC_CHECK_HIP(hipMemcpyAsync(out, ws.h, (size_t)M * kHid * 4, hipMemcpyDeviceToDevice, s));
-    return CASYNC_OK;
-  }
-  HB(launch_layernorm(ws.h, kHid, out, kHid, M, kHid, H->W("enc.ln.g"), H->W("enc.ln.b"), kEps, false, s));
-#undef HB
-  return CASYNC_OK;
+  if (stage == 3) return copy_out(out, ws.h, (size_t)M * kHid, s);
+  return launch_layernorm(ws.h, kHid, out, kHid, M, kHid, H->w(L.enc_ln_g), H->w(L.enc_ln_b), kEps, false, s);
 }
 
 // The bf16 precision: bf16 GEMM operands and activations, fp32 sums, fp32 residual stream.  The out-proj
 // and FF2 GEMMs write a bf16 delta; h += delta happens inside the LayerNorm that follows (LN2, the next layer's LN1, the
 // final one), so `pending` says whether d16 still has to be added to h.
-int hb_run16(casync_hubert* H, const float* wave, int batch, int64_t S, float* out, void* ws_dev, int64_t ws_bytes, hipStream_t s,
-             int stage, int n_layers) {
-  CASYNC_REQUIRE(H && wave && out && ws_dev, "hubert forward: null pointer");
-  CASYNC_REQUIRE(H->pw.w && H->pw.w16, "hubert forward: weights not loaded");
-  CASYNC_REQUIRE(batch > 0 && batch <= 65535, "hubert forward: batch %d", batch);
-  CASYNC_REQUIRE(S < (1ll << 31), "hubert forward: %lld samples", (long long)S);
-  const HbGeom G(S);
-  CASYNC_REQUIRE(G.tokens() >= 1, "hubert forward: %lld samples give no token (at least 400 are needed)", (long long)S);
-  CASYNC_REQUIRE(stage >= 0 && stage <= 3, "hubert forward: stage %d", stage);
-  CASYNC_REQUIRE(n_layers >= 0 && n_layers <= H->layers, "hubert forward: %d layers of %d", n_layers, H->layers);
-  CASYNC_REQUIRE((uintptr_t)wave % 4 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws_dev % 16 == 0, "hubert forward: alignment");
-  HbWs16 ws(ws_dev, batch, G);
-  if (ws_bytes < ws.bytes) {
-    casync_set_error("hubert forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)ws.bytes);
-    return CASYNC_ERR_STATE;
-  }
+int hb_walk16(const casync_hubert* H, const float* wave, int batch, const HbGeom& G, float* out, const HbWs16& ws, hipStream_t s, int stage,
+              int n_layers) {
+  const HbLayout& L = *H->lay;
   const int T = (int)G.tokens(), M = batch * T;
-  DeviceGuard guard(H->device);
-  CASYNC_CHECK_HIP(guard.err);
-  std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
-  if (int st = casync_gate_enter(H->device, H, &H->ev_fwd, s, &gate_lock)) return st;
-#define HB(call)                       \
-  do {                                 \
-    if (int st__ = (call)) return st__; \
-  } while (0)
   // feature encoder: conv0 -> a, then ping-pong a <-> b (bf16)
-  HB(launch_hb16_conv0(wave, batch, (int)S, H->W("fe.conv0.w"), H->W("fe.conv0.b"), H->W("fe.ln0.g"), H->W("fe.ln0.b"), ws.a, s));
+  HB(launch_hb16_conv0(wave, batch, (int)G.t[0], H->w(L.fe[0].w), H->w(L.fe[0].b), H->w(L.fe[0].g), H->w(L.fe[0].be), ws.a, s));
   bf16_t *cur = ws.a, *nxt = ws.b;
   for (int i = 1; i < 7; ++i) {
     const int tin = (int)G.t[i], tout = (int)G.t[i + 1];
-    const std::string p = "fe.conv" + std::to_string(i), ln = "fe.ln" + std::to_string(i);
+    const HbLayout::Conv& c = L.fe[i];
     for (int b = 0; b < batch; ++b)
-      HB(launch_rows_gemm_bf16(cur + (size_t)b * tin * kConvC, kConvS[i] * kConvC, H->W16(p + ".w"), H->W(p + ".b"),
-                               nxt + (size_t)b * tout * kConvC, kConvC, tout, kConvC, kConvK[i] * kConvC, s));
-    HB(launch_hb16_layernorm512(nxt, kConvC, nxt, kConvC, batch * tout, H->W(ln + ".g"), H->W(ln + ".b"), kEps, false, true, s));
+      HB(launch_rows_gemm_bf16(cur + (size_t)b * tin * kConvC, kConvS[i] * kConvC, H->w16(c.w), H->w(c.b), nxt + (size_t)b * tout * kConvC,
+                               kConvC, tout, kConvC, kConvK[i] * kConvC, s));
+    HB(launch_hb16_layernorm512(nxt, kConvC, nxt, kConvC, batch * tout, H->w(c.g), H->w(c.be), kEps, false, true, s));
     bf16_t* t = cur;
     cur = nxt, nxt = t;
   }
   if (stage == 1) return launch_hb16_widen(cur, out, (long long)M * kConvC, s);
   // feature projection and positional conv on the fp32 kernels
   float* ln32 = reinterpret_cast<float*>(ws.big);
-  HB(launch_hb16_layernorm512(cur, kConvC, ln32, kConvC, M, H->W("fp.ln.g"), H->W("fp.ln.b"), kEps, true, false, s));
-  HB(gemm(ln32, kConvC, H->W("fp.w"), H->W("fp.b"), ws.x, kHid, M, kHid, kConvC, 0, nullptr, s));
-  HB(launch_posconv(ws.x, H->W("pos.w"), H->W("pos.b"), ws.h, batch, T, s));
-  if (stage == 2) {
-    CASYNC_CHECK_HIP(hipMemcpyAsync(out, ws.h, (size_t)M * kHid * 4, hipMemcpyDeviceToDevice, s));
-    return CASYNC_OK;
-  }
+  HB(launch_hb16_layernorm512(cur, kConvC, ln32, kConvC, M, H->w(L.fp_ln_g), H->w(L.fp_ln_b), kEps, true, false, s));
+  HB(gemm(ln32, kConvC, H->w(L.fp_w), H->w(L.fp_b), ws.x, kHid, M, kHid, kConvC, 0, nullptr, s));
+  HB(launch_posconv(ws.x, H->w(L.pos_w), H->w(L.pos_b), ws.h, batch, T, s));
+  if (stage == 2) return copy_out(out, ws.h, (size_t)M * kHid, s);
   const int nl = stage == 3 ? n_layers : H->layers;
   bool pending = false;
   for (int l = 0; l < nl; ++l) {
-    const std::string p = "layer" + std::to_string(l);
-    HB(launch_hb16_layernorm1024(ws.h, kHid, pending ? ws.d16 : nullptr, kHid, true, ws.x16, kHid, M, H->W(p + ".ln1.g"),
-                                 H->W(p + ".ln1.b"), kEps, false, s));
-    HB(launch_rows_gemm_bf16(ws.x16, kHid, H->W16(p + ".qkv.w"), H->W(p + ".qkv.b"), ws.big, 3 * kHid, M, 3 * kHid, kHid, s));
-    HB(launch_hb16_attention(ws.big, ws.x16, batch, T, s));
-    HB(launch_rows_gemm_bf16(ws.x16, kHid, H->W16(p + ".o.w"), H->W(p + ".o.b"), ws.d16, kHid, M, kHid, kHid, s));
-    HB(launch_hb16_layernorm1024(ws.h, kHid, ws.d16, kHid, true, ws.x16, kHid, M, H->W(p + ".ln2.g"), H->W(p + ".ln2.b"), kEps,
+    const HbLayout::Layer& y = L.layer[l];
+    HB(launch_hb16_layernorm1024(ws.h, kHid, pending ? ws.d16 : nullptr, kHid, true, ws.x16, kHid, M, H->w(y.ln1_g), H->w(y.ln1_b), kEps,
                                  false, s));
-    HB(launch_rows_gemm_bf16(ws.x16, kHid, H->W16(p + ".ff1.w"), H->W(p + ".ff1.b"), ws.big, kFF, M, kFF, kHid, s));
+    HB(launch_rows_gemm_bf16(ws.x16, kHid, H->w16(y.qkv_w), H->w(y.qkv_b), ws.big, 3 * kHid, M, 3 * kHid, kHid, s));
+    HB(launch_hb16_attention(ws.big, ws.x16, batch, T, s));
+    HB(launch_rows_gemm_bf16(ws.x16, kHid, H->w16(y.o_w), H->w(y.o_b), ws.d16, kHid, M, kHid, kHid, s));
+    HB(launch_hb16_layernorm1024(ws.h, kHid, ws.d16, kHid, true, ws.x16, kHid, M, H->w(y.ln2_g), H->w(y.ln2_b), kEps, false, s));
+    HB(launch_rows_gemm_bf16(ws.x16, kHid, H->w16(y.ff1_w), H->w(y.ff1_b), ws.big, kFF, M, kFF, kHid, s));
     HB(launch_hb16_gelu(ws.big, (long long)M * kFF, s));
-    HB(launch_rows_gemm_bf16(ws.big, kFF, H->W16(p + ".ff2.w"), H->W(p + ".ff2.b"), ws.d16, kHid, M, kHid, kFF, s));
+    HB(launch_rows_gemm_bf16(ws.big, kFF, H->w16(y.ff2_w), H->w(y.ff2_b), ws.d16, kHid, M, kHid, kFF, s));
     pending = true;
   }
   if (stage == 3) {
     // the tap includes the pending delta: one more pass of the LayerNorm kernel folds it into h (its bf16 output is unused)
     if (pending)
-      HB(launch_hb16_layernorm1024(ws.h, kHid, ws.d16, kHid, true, ws.x16, kHid, M, H->W("enc.ln.g"), H->W("enc.ln.b"), kEps, false, s));
-    CASYNC_CHECK_HIP(hipMemcpyAsync(out, ws.h, (size_t)M * kHid * 4, hipMemcpyDeviceToDevice, s));
-    return CASYNC_OK;
+      HB(launch_hb16_layernorm1024(ws.h, kHid, ws.d16, kHid, true, ws.x16, kHid, M, H->w(L.enc_ln_g), H->w(L.enc_ln_b), kEps, false, s));
+    return copy_out(out, ws.h, (size_t)M * kHid, s);
   }
-  HB(launch_hb16_layernorm1024(ws.h, kHid, pending ? ws.d16 : nullptr, kHid, false, out, kHid, M, H->W("enc.ln.g"),
-                               H->W("enc.ln.b"), kEps, true, s));
+  return launch_hb16_layernorm1024(ws.h, kHid, pending ? ws.d16 : nullptr, kHid, false, out, kHid, M, H->w(L.enc_ln_g), H->w(L.enc_ln_b),
+                                   kEps, true, s);
+}
 #undef HB
-  return CASYNC_OK;
+
+int64_t hb_workspace_bytes(int dtype, int batch, const HbGeom& G) {
+  return dtype == DT_BF16 ? HbWs16(nullptr, batch, G).bytes : HbWs(nullptr, batch, G).floats * 4;
+}
+
+// One forward of either precision: the checks, the geometry, the workspace, the device and the forward gate, then the walk.
+// stage 0: final hidden states [B,T,1024]; 1: conv-stack output [B,T,512]; 2: input to layer 0 [B,T,1024];
+// 3: hidden states after `n_layers` layers, before the final LayerNorm [B,T,1024]
+int hb_run(casync_hubert* H, const float* wave, int batch, int64_t S, float* out, void* ws_dev, int64_t ws_bytes, hipStream_t s,
+           int stage, int n_layers) {
+  CASYNC_REQUIRE(H && wave && out && ws_dev, "hubert forward: null pointer");
+  const bool h16 = H->dtype == DT_BF16;
+  CASYNC_REQUIRE(H->pw.w && (!h16 || H->pw.w16), "hubert forward: weights not loaded");
+  CASYNC_REQUIRE(batch > 0 && batch <= 65535, "hubert forward: batch %d", batch);
+  CASYNC_REQUIRE(S < (1ll << 31), "hubert forward: %lld samples", (long long)S);
+  const HbGeom G(S);
+  CASYNC_REQUIRE(G.tokens() >= 1, "hubert forward: %lld samples give no token (at least 400 are needed)", (long long)S);
+  CASYNC_REQUIRE(stage >= 0 && stage <= 3, "hubert forward: stage %d", stage);
+  CASYNC_REQUIRE(n_layers >= 0 && n_layers <= H->layers, "hubert forward: %d layers of %d", n_layers, H->layers);
+  CASYNC_REQUIRE((uintptr_t)wave % 4 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)ws_dev % 16 == 0, "hubert forward: alignment");
+  const int64_t need = hb_workspace_bytes(H->dtype, batch, G);
+  if (ws_bytes < need) {
+    casync_set_error("hubert forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)need);
+    return CASYNC_ERR_STATE;
+  }
+  DeviceGuard guard(H->device);
+  CASYNC_CHECK_HIP(guard.err);
+  std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
+  if (int st = casync_gate_enter(H->device, H, &H->ev_fwd, s, &gate_lock)) return st;
+  if (h16) return hb_walk16(H, wave, batch, G, out, HbWs16(ws_dev, batch, G), s, stage, n_layers);
+  return hb_walk32(H, wave, batch, G, out, HbWs(static_cast<float*>(ws_dev), batch, G), s, stage, n_layers);
 }
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------
 extern "C" {
 
-int casync_hubert_packed_count(int layers) { return hb_layout(layers) ? hb_layout(layers)->count() : 0; }
-const char* casync_hubert_packed_name(int layers, int i) { return hb_layout(layers) ? hb_layout(layers)->name(i) : nullptr; }
-int64_t casync_hubert_packed_offset(int layers, int i) { return hb_layout(layers) ? hb_layout(layers)->offset(i) : -1; }
-int64_t casync_hubert_packed_size(int layers, int i) { return hb_layout(layers) ? hb_layout(layers)->size(i) : -1; }
-int64_t casync_hubert_packed_total(int layers) { return hb_layout(layers) ? hb_layout(layers)->total : 0; }
+int casync_hubert_packed_count(int layers) { return hb_layout(layers) ? hb_layout(layers)->packed.count() : 0; }
+const char* casync_hubert_packed_name(int layers, int i) { return hb_layout(layers) ? hb_layout(layers)->packed.name(i) : nullptr; }
+int64_t casync_hubert_packed_offset(int layers, int i) { return hb_layout(layers) ? hb_layout(layers)->packed.offset(i) : -1; }
+int64_t casync_hubert_packed_size(int layers, int i) { return hb_layout(layers) ? hb_layout(layers)->packed.size(i) : -1; }
+int64_t casync_hubert_packed_total(int layers) { return hb_layout(layers) ? hb_layout(layers)->packed.total : 0; }
 int64_t casync_hubert_tokens(int64_t samples) { return samples > 0 ? HbGeom(samples).tokens() : 0; }
 int64_t casync_hubert_workspace_bytes(int batch, int64_t samples) {
   if (batch <= 0 || samples <= 0) return 0;
   const HbGeom G(samples);
-  return G.tokens() > 0 ? HbWs(nullptr, batch, G).floats * 4 : 0;
+  return G.tokens() > 0 ? hb_workspace_bytes(DT_F32, batch, G) : 0;
 }
 
 int64_t casync_hubert_workspace_bytes_h(casync_hubert_handle h, int batch, int64_t samples) {
   if (!h || batch <= 0 || samples <= 0) return 0;
   const HbGeom G(samples);
-  if (G.tokens() <= 0) return 0;
-  return h->dtype == DT_BF16 ? HbWs16(nullptr, batch, G).bytes : HbWs(nullptr, batch, G).floats * 4;
+  return G.tokens() > 0 ? hb_workspace_bytes(h->dtype, batch, G) : 0;
 }
 
 int casync_hubert_create(int device_id, int layers, casync_hubert_handle* out) {
@@ -605,6 +594,7 @@ int casync_hubert_create_ex(int device_id, int layers, int dtype, casync_hubert_
   h->device = device_id;
   h->layers = layers;
   h->dtype = dtype;
+  h->lay = hb_layout(layers);
   *out = h;
   return CASYNC_OK;
 }
@@ -619,26 +609,22 @@ void casync_hubert_destroy(casync_hubert_handle h) {
 
 int casync_hubert_load_weights_host(casync_hubert_handle h, const float* packed, int64_t n_floats) {
   CASYNC_REQUIRE(h, "hubert_load_weights: null");
-  return h->pw.load_host("hubert_load_weights", h->device, packed, n_floats, hb_layout(h->layers)->total, h->dtype == DT_BF16);
+  return h->pw.load_host("hubert_load_weights", h->device, packed, n_floats, h->lay->packed.total, h->dtype == DT_BF16);
 }
 
 int casync_hubert_load_weights_device(casync_hubert_handle h, const float* packed_dev, int64_t n_floats) {
   CASYNC_REQUIRE(h, "hubert_load_weights_device: null");
-  return h->pw.adopt_device("hubert_load_weights_device", h->device, packed_dev, n_floats, hb_layout(h->layers)->total,
-                            h->dtype == DT_BF16);
+  return h->pw.adopt_device("hubert_load_weights_device", h->device, packed_dev, n_floats, h->lay->packed.total, h->dtype == DT_BF16);
 }
 
 int casync_hubert_forward(casync_hubert_handle h, const float* wave_dev, int batch, int64_t samples, float* out_dev,
                           void* workspace_dev, int64_t workspace_bytes, casync_stream stream) {
-  if (h && h->dtype == DT_BF16) return hb_run16(h, wave_dev, batch, samples, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream, 0, 0);
   return hb_run(h, wave_dev, batch, samples, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream, 0, 0);
 }
 
 int casync_hubert_forward_tap(casync_hubert_handle h, const float* wave_dev, int batch, int64_t samples, int stage, int n_layers,
                               float* out_dev, void* workspace_dev, int64_t workspace_bytes, casync_stream stream) {
   CASYNC_REQUIRE(stage >= 1 && stage <= 3, "hubert_forward_tap: stage %d (1 conv stack, 2 layer-0 input, 3 after n layers)", stage);
-  if (h && h->dtype == DT_BF16)
-    return hb_run16(h, wave_dev, batch, samples, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream, stage, n_layers);
   return hb_run(h, wave_dev, batch, samples, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream, stage, n_layers);
 }
 
