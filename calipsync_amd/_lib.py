@@ -227,6 +227,27 @@ _PROTOS = {
     "casync_op_jpegdec_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int, C.c_int, c_i64]),
     "casync_op_jpegdec_decode": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i64,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    # SyncNet_color, the lip-sync judge (additive to ABI 13); mode is AUDIO_MODES' number
+    "casync_sync_packed_count": (C.c_int, [C.c_int]),
+    "casync_sync_packed_name": (C.c_char_p, [C.c_int, C.c_int]),
+    "casync_sync_packed_offset": (c_i64, [C.c_int, C.c_int]),
+    "casync_sync_packed_size": (c_i64, [C.c_int, C.c_int]),
+    "casync_sync_packed_total": (c_i64, [C.c_int]),
+    "casync_sync_workspace_bytes": (c_i64, [C.c_int, C.c_int]),
+    "casync_sync_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "casync_sync_destroy": (None, [C.c_void_p]),
+    "casync_sync_load_weights_host": (C.c_int, [C.c_void_p, C.c_void_p, c_i64]),
+    "casync_sync_load_weights_device": (C.c_int, [C.c_void_p, c_f32p, c_i64]),
+    "casync_sync_forward": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, c_f32p, c_f32p, C.c_void_p, c_i64, C.c_void_p]),
+    "casync_sync_forward_tap": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, c_f32p, C.c_void_p, c_i64, C.c_void_p]),
+    "casync_op_sync_stem7": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_sync_conv5": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_sync_conv3": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p]),
+    "casync_op_sync_relu": (C.c_int, [c_f32p, c_i64, C.c_void_p]),
+    "casync_op_sync_to_nchw": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_sync_embed": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_void_p]),
+    "casync_op_sync_curve": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -325,6 +346,11 @@ def pfld_layout():
 def s3fd_layout():
     """The layout of the S3FD face-detector engine's packed buffer."""
     return _layout("s3fd_")
+
+
+def sync_layout(mode: str = "hubert"):
+    """The layout of the SyncNet_color engine's packed buffer for one audio mode."""
+    return _layout("sync_", AUDIO_MODES[mode])
 
 
 def pack_named(named: dict, layout) -> np.ndarray:

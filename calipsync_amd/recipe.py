@@ -255,3 +255,44 @@ def make_s3fd_inputs(batch: int, h: int = 77, w: int = 93, seed: int = S3FD_INPU
             img += (160.0 * u[4 * i + 3] - 60.0) * g[:, :, None] * (0.5 + u[32 + 3 * i:35 + 3 * i])
         x[b] = np.clip(np.floor(img), 0, 255).astype(np.uint8)
     return x
+
+
+# ---- SyncNet_color, the lip-sync judge (calipsync_amd/syncnet.py) ----------------------------------------------------
+SYNCNET_WEIGHT_SEED = 0x5C1E
+SYNCNET_INPUT_SEED = 0x5C1F
+
+
+def make_syncnet_state_dict(mode: str = "hubert", seed: int = SYNCNET_WEIGHT_SEED) -> Dict[str, np.ndarray]:
+    """The 217 entries of a ``SyncNet_color(mode)`` state dict: conv weights N(0, 1 / fan_in) (gain 1.0: at G1.2's 1.2 the
+    residual trunk grows to 35), conv biases N(0, 0.05^2), BatchNorm weight and running_var U(0.8, 1.2), bias and running_mean
+    N(0, 0.1^2).  Every stage's max |x| then stays between 1.5 and 12 (tests/golden/make_syncnet_golden.py asserts [0.1, 16]).  A
+    key of both modes with one shape has one value."""
+    from . import syncnet
+    sd: Dict[str, np.ndarray] = {}
+    for key, shape in syncnet.manifest(mode):
+        n = int(np.prod(shape)) if shape else 1
+        s = _stream("syncnet." + key)
+        block, leaf = key.rsplit(".", 2)[1:]
+        if leaf == "num_batches_tracked":
+            sd[key] = np.zeros(shape, dtype=np.int64)
+            continue
+        if block == "0":
+            v = normal01(seed, s, n) / np.sqrt(int(np.prod(shape[1:]))) if leaf == "weight" else normal01(seed, s, n) * 0.05
+        elif leaf in ("weight", "running_var"):
+            v = 0.8 + 0.4 * uniform01(seed, s, n)
+        else:
+            v = normal01(seed, s, n) * 0.1
+        sd[key] = v.astype(np.float32).reshape(shape)
+    return sd
+
+
+def make_syncnet_inputs(batch: int, mode: str = "hubert", seed: int = SYNCNET_INPUT_SEED) -> Tuple[np.ndarray, np.ndarray]:
+    """Synthetic pairs: face ~ U(0,1) [B,3,160,160], audio ~ N(0,1) [B,32,32,32] (wenet: [B,256,16,32]); pair b depends only on
+    (seed, b) and, the audio window, on the mode's shape."""
+    from . import syncnet
+    x = np.empty((batch, 3, syncnet.FACE_HW, syncnet.FACE_HW), dtype=np.float32)
+    a = np.empty((batch,) + syncnet.AUDIO_SHAPE[mode], dtype=np.float32)
+    for b in range(batch):
+        x[b] = uniform01(seed, 0x7000000 + b, x[b].size).astype(np.float32).reshape(x[b].shape)
+        a[b] = normal01(seed, 0x8000000 + b, a[b].size).astype(np.float32).reshape(a[b].shape)
+    return x, a

@@ -735,6 +735,59 @@ int     casync_op_jpegdec_decode(const uint8_t* data, int64_t data_bytes, const 
                                  int chunk_bits, uint8_t* scratch, int64_t scratch_bytes, uint8_t* out, int32_t* status,
                                  casync_stream stream);
 
+/* ---- SyncNet_color, the lip-sync judge (additive to ABI 13: new symbols, nothing else changed) --------------------- */
+/* The reference's SyncNet_color (module/syncnet.py:155-246) in eval mode, fp32: a face encoder of 17 conv + BatchNorm (+ x)
+ * + ReLU blocks on [batch,3,160,160] NCHW in [0,1] (BGR: the layout of the U-Net's output), an audio encoder of 14 such
+ * blocks on [batch,32,32,32] (mode CASYNC_AUDIO_HUBERT) or [batch,256,16,32] (CASYNC_AUDIO_WENET), each ending in [batch,512,
+ * 3,3]; then view(batch, -1) in NCHW order (index c * 9 + y * 3 + x), x / max(|x|_2, 1e-12) and LeakyReLU(0.01).  BatchNorm
+ * is folded into the convs on the host (calipsync_amd/syncnet.py).  Packed tensors per block, `face.<i>` / `audio.<i>`:
+ *   .w  [cout][(ky,kx,cin)] (face.0: [(ky,kx,cin) = 147][32]),  .b  [cout].
+ * Activations are NHWC.  face.0 (7x7) has a kernel of its own, face.1 (5x5, stride 2) and the 27 3x3 blocks run on one implicit-GEMM
+ * kernel that sums K in chunks of 32 (one fma chain over K = 4608 leaves several times the reference's own float32 error), the
+ * two 1x1 blocks on the data-parallel ring GEMM followed by a ReLU pass (the pointwise GEMM has no ReLU epilogue and may split K
+ * at small M): no stream-K, no K split, no atomics, no sum across frames, so frame i of a batch has the bits of that frame
+ * forwarded alone.  A batch above 256 frames runs in passes of 256.
+ *   sync_workspace_bytes: 0 for a mode other than the two or a batch outside 1..65536.
+ *   sync_forward: audio_emb_dev and face_emb_dev [batch,4608] fp32, 16-byte aligned; workspace 256-byte aligned.  Enqueues on
+ *     `stream`, does not synchronise.  batch 0 returns 0.
+ *   sync_forward_tap: stage 0..16 = face.0..face.16, 17..30 = audio.0..audio.13: that block's output in the reference's NCHW
+ *     order into out_dev; the other encoder's input may be NULL.
+ * Single operators (the kernel ledger's entries), all fp32, 16-byte aligned, enqueue and return:
+ *   sync_stem7:   x [batch,3,h,w] NCHW, w [147][32], bias [32] -> out [batch,h,w,32] = relu(conv7x7 pad 3 + bias).
+ *   sync_conv5:   in [batch,h,w,32] NHWC, w [64][(ky,kx,c) = 800], bias [64] -> out [batch,ho,wo,64], 5x5, stride 2, pad 1, ReLU;
+ *                 ho = (h - 3) / 2 + 1, h and w >= 3.
+ *   sync_conv3:   in [batch,h,w,cin] NHWC, w [cout][(ky,kx,c) = 9 cin], bias [cout], res NULL or [batch,ho,wo,cout] -> out [batch,ho,
+ *                 wo,cout] = relu(conv3x3 + bias + res); cin a multiple of 32, cout of 64, strides 1..8, pad 0..8.
+ *   sync_relu:    ReLU in place, n a multiple of 4.
+ *   sync_to_nchw: in [batch,hw,c] -> out [batch,c,hw].
+ *   sync_embed:   in [batch,9,512] NHWC -> out [batch,4608] as above; the norm is summed in float64 in a fixed order.
+ *   sync_curve:   face_emb, audio_emb [n,d] (d a multiple of 4) -> sim [2 max_shift + 1, n], sim[s + max_shift, i] =
+ *                 dot(face_i, audio_(i+s)) / max(|face_i| |audio_(i+s)|, 1e-8), sums in float64, one wave per pair;
+ *                 0 where i + s is outside [0, n).  n >= 1, 0 <= max_shift <= 4096.                                         */
+typedef struct casync_sync* casync_sync_handle;
+int         casync_sync_packed_count(int mode);
+const char* casync_sync_packed_name(int mode, int i);
+int64_t     casync_sync_packed_offset(int mode, int i);
+int64_t     casync_sync_packed_size(int mode, int i);
+int64_t     casync_sync_packed_total(int mode);
+int64_t     casync_sync_workspace_bytes(int mode, int batch);
+int  casync_sync_create(int device_id, int mode, casync_sync_handle* out);
+void casync_sync_destroy(casync_sync_handle h);
+int  casync_sync_load_weights_host(casync_sync_handle h, const float* packed, int64_t n_floats);
+int  casync_sync_load_weights_device(casync_sync_handle h, const float* packed_dev, int64_t n_floats);
+int  casync_sync_forward(casync_sync_handle h, const float* face_dev, const float* audio_dev, int batch, float* audio_emb_dev,
+                         float* face_emb_dev, void* workspace_dev, int64_t workspace_bytes, casync_stream stream);
+int  casync_sync_forward_tap(casync_sync_handle h, const float* face_dev, const float* audio_dev, int batch, int stage,
+                             float* out_dev, void* workspace_dev, int64_t workspace_bytes, casync_stream stream);
+int  casync_op_sync_stem7(const float* x, const float* w, const float* bias, float* out, int batch, int h, int w_, casync_stream stream);
+int  casync_op_sync_conv5(const float* in, const float* w, const float* bias, float* out, int batch, int h, int w_, casync_stream stream);
+int  casync_op_sync_conv3(const float* in, const float* w, const float* bias, const float* res, float* out, int batch, int h, int w_,
+                          int cin, int cout, int stride_h, int stride_w, int pad, casync_stream stream);
+int  casync_op_sync_relu(float* x, int64_t n, casync_stream stream);
+int  casync_op_sync_to_nchw(const float* in, float* out, int batch, int hw, int c, casync_stream stream);
+int  casync_op_sync_embed(const float* in, float* out, int batch, casync_stream stream);
+int  casync_op_sync_curve(const float* face_emb, const float* audio_emb, int n, int d, int max_shift, float* sim, casync_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
