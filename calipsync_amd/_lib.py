@@ -248,6 +248,16 @@ _PROTOS = {
     "casync_op_sync_to_nchw": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_sync_embed": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_void_p]),
     "casync_op_sync_curve": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p]),
+    # its bf16 precision (additive to ABI 13); precision is SYNC_PRECISIONS' number, pointers typed c_void_p are bf16
+    "casync_syncnet_create_ex": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "casync_syncnet_precision": (C.c_int, [C.c_void_p]),
+    "casync_syncnet_workspace_bytes_ex": (c_i64, [C.c_int, C.c_int, C.c_int]),
+    "casync_op_sync16_stem7": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_sync16_conv5": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_sync16_conv3": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_sync16_conv1": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_sync16_to_nchw": (C.c_int, [C.c_void_p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -18,14 +18,15 @@
 // section 8k).  The two 1x1 blocks (K = 512) run on the data-parallel ring GEMM (launch_rows_gemm), the audio window goes to NHWC
 // with launch_nchw_to_nhwc: no stream-K, no K split.  No kernel here sums across frames or uses an atomic: frame i of a batch has
 // the bits of that frame forwarded alone.
+// The block table, the handle and what the bf16 precision of this handle (syncnet_bf16.hip) calls of this file are declared in
+// syncnet_common.h; a handle of precision 1 takes sync_run's checks and gate and then that file's pass.
 #include <string.h>
 
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "common.h"
-#include "handle.h"
+#include "syncnet_common.h"
 
 namespace {
 
@@ -318,6 +319,9 @@ int launch_sync_relu(float* x, long long n, hipStream_t s) {
   return casync_launch(sync_relu_kernel, dim3(grid), dim3(256), 0, s, x, n / 4);
 }
 
+}  // namespace
+
+// (declared in syncnet_common.h: the bf16 pass of syncnet_bf16.hip calls these two)
 int launch_sync_to_nchw(const float* in, float* out, int batch, int hw, int c, hipStream_t s) {
   CASYNC_REQUIRE(in && out && batch > 0 && hw >= 1 && c >= 1, "sync to_nchw: B=%d hw=%d c=%d", batch, hw, c);
   const long long total = (long long)batch * hw * c;
@@ -333,6 +337,8 @@ int launch_sync_embed(const float* in, float* out, int batch, hipStream_t s) {
   return casync_launch(sync_embed_kernel, dim3((unsigned)batch), dim3(256), 0, s, in, out);
 }
 
+namespace {
+
 int launch_sync_curve(const float* f, const float* a, int n, int d, int max_shift, float* sim, hipStream_t s) {
   CASYNC_REQUIRE(f && a && sim, "sync curve: null pointer");
   CASYNC_REQUIRE(n >= 1 && n <= (1 << 24) && d >= 4 && d % 4 == 0 && d <= (1 << 20) && max_shift >= 0 && max_shift <= 4096,
@@ -345,59 +351,8 @@ int launch_sync_curve(const float* f, const float* a, int n, int d, int max_shif
 }
 
 // ------------------------------------------------------------------------------------------------ network, packed layout
-struct SyncBlock {
-  int k, cin, cout, sh, sw, pad, res;
-};
-constexpr int kFaceBlocks = 17, kAudioBlocks = 14, kBlocks = kFaceBlocks + kAudioBlocks;
-constexpr int kFaceHW = 160, kMaxPass = 256;   // frames of one pass through the network
-
-// the 31 blocks of one mode with their sizes and the packed layout, every offset resolved once
-struct SyncNet {
-  SyncBlock blk[kBlocks];
-  int h_in[kBlocks], w_in[kBlocks], h_out[kBlocks], w_out[kBlocks];
-  PackedLayout packed;
-  int64_t w_off[kBlocks], b_off[kBlocks];
-  int audio_c, audio_h, audio_w;
-  int64_t act_floats = 0;   // the largest activation of one frame
-  explicit SyncNet(int mode) {
-    const bool wenet = mode == CASYNC_AUDIO_WENET;
-    audio_c = wenet ? 256 : 32, audio_h = wenet ? 16 : 32, audio_w = 32;
-    int n = 0;
-    auto add = [&](int k, int cin, int cout, int sh, int sw, int pad, int res) { blk[n++] = SyncBlock{k, cin, cout, sh, sw, pad, res}; };
-    auto stage = [&](int cin, int cout, int sh, int sw, int pad, int n_res) {   // a 3x3 conv and the residual blocks behind it
-      add(3, cin, cout, sh, sw, pad, 0);
-      for (int i = 0; i < n_res; ++i) add(3, cout, cout, 1, 1, 1, 1);
-    };
-    add(7, 3, 32, 1, 1, 3, 0);
-    add(5, 32, 64, 2, 2, 1, 0);
-    add(3, 64, 64, 1, 1, 1, 1), add(3, 64, 64, 1, 1, 1, 1);
-    stage(64, 128, 2, 2, 1, 3), stage(128, 256, 2, 2, 1, 2), stage(256, 512, 2, 2, 1, 2);
-    stage(512, 512, 2, 2, 1, 0), stage(512, 512, 1, 1, 0, 0);
-    add(1, 512, 512, 1, 1, 0, 0);
-    stage(audio_c, 256, 1, 1, 1, 2), stage(256, 256, wenet ? 1 : 2, 2, 1, 2), stage(256, 256, 2, 2, 2, 2), stage(256, 512, 2, 2, 1, 2);
-    stage(512, 512, 1, 1, 0, 0);
-    add(1, 512, 512, 1, 1, 0, 0);
-    for (int i = 0; i < kBlocks; ++i) {
-      const SyncBlock& b = blk[i];
-      const bool first = i == 0 || i == kFaceBlocks;
-      h_in[i] = first ? (i == 0 ? kFaceHW : audio_h) : h_out[i - 1];
-      w_in[i] = first ? (i == 0 ? kFaceHW : audio_w) : w_out[i - 1];
-      h_out[i] = (h_in[i] + 2 * b.pad - b.k) / b.sh + 1, w_out[i] = (w_in[i] + 2 * b.pad - b.k) / b.sw + 1;
-      const int64_t act = (int64_t)h_out[i] * w_out[i] * b.cout;
-      act_floats = act > act_floats ? act : act_floats;
-      const std::string p = i < kFaceBlocks ? "face." + std::to_string(i) : "audio." + std::to_string(i - kFaceBlocks);
-      w_off[i] = packed.add(p + ".w", (int64_t)b.cout * b.k * b.k * b.cin), b_off[i] = packed.add(p + ".b", b.cout);
-    }
-    const int64_t audio_in = (int64_t)audio_c * audio_h * audio_w;
-    act_floats = audio_in > act_floats ? audio_in : act_floats;
-  }
-  int64_t out_floats(int i) const { return (int64_t)h_out[i] * w_out[i] * blk[i].cout; }
-};
-bool sync_mode_ok(int mode) { return mode == CASYNC_AUDIO_HUBERT || mode == CASYNC_AUDIO_WENET; }
-const SyncNet& sync_net(int mode) {
-  static const SyncNet nets[2] = {SyncNet(CASYNC_AUDIO_HUBERT), SyncNet(CASYNC_AUDIO_WENET)};
-  return nets[mode == CASYNC_AUDIO_WENET ? 1 : 0];
-}
+// (the block table SyncNet, sync_net() and the handle: syncnet_common.h)
+constexpr int kFaceBlocks = kSyncFaceBlocks, kBlocks = kSyncBlocks, kFaceHW = kSyncFaceHW, kMaxPass = kSyncMaxPass;
 
 // the arena of one pass: two activations, each on a 256-B boundary
 struct SyncWs {
@@ -410,16 +365,6 @@ struct SyncWs {
   }
 };
 
-}  // namespace
-
-struct casync_sync {
-  int device = 0;
-  int mode = 0;
-  PackedWeights pw;
-  hipEvent_t ev_fwd = nullptr;   // forward gate slot
-};
-
-namespace {
 #define DT(call)                        \
   do {                                  \
     if (int st__ = (call)) return st__; \
@@ -491,10 +436,13 @@ int sync_run(casync_sync* D, const float* face, const float* audio, int batch, i
   const SyncNet& N = sync_net(D->mode);
   const int nb = batch < kMaxPass ? batch : kMaxPass;
   const SyncWs ws(ws_dev, nb, N);
-  if (ws_bytes < ws.bytes) {
-    casync_set_error("sync forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)ws.bytes);
+  const bool bf16 = D->precision == 1;   // its pass (syncnet_bf16.hip) lays out its own, smaller arena
+  const int64_t need = bf16 ? sync16_ws_bytes(nb, N) : ws.bytes;
+  if (ws_bytes < need) {
+    casync_set_error("sync forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)need);
     return CASYNC_ERR_STATE;
   }
+  CASYNC_REQUIRE(!bf16 || D->pw.w16, "sync forward: bf16 weight image not made");
   DeviceGuard guard(D->device);
   CASYNC_CHECK_HIP(guard.err);
   std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
@@ -504,9 +452,11 @@ int sync_run(casync_sync* D, const float* face, const float* audio, int batch, i
   // every pass takes the tile choices of its own frame count; the kernels' sums do not depend on it (see the header comment)
   for (int b0 = 0; b0 < batch; b0 += nb) {
     const int n = batch - b0 < nb ? batch - b0 : nb;
-    DT(sync_pass(D, face ? face + (size_t)b0 * face_frame : nullptr, audio ? audio + (size_t)b0 * audio_frame : nullptr, n, ws, stage,
-                 out ? out + (size_t)b0 * out_frame : nullptr, audio_emb ? audio_emb + (size_t)b0 * EMB_D : nullptr,
-                 face_emb ? face_emb + (size_t)b0 * EMB_D : nullptr, s));
+    const float *fp = face ? face + (size_t)b0 * face_frame : nullptr, *ap = audio ? audio + (size_t)b0 * audio_frame : nullptr;
+    float* op = out ? out + (size_t)b0 * out_frame : nullptr;
+    float *ae = audio_emb ? audio_emb + (size_t)b0 * EMB_D : nullptr, *fe = face_emb ? face_emb + (size_t)b0 * EMB_D : nullptr;
+    if (bf16) DT(sync16_pass(D, fp, ap, n, ws_dev, stage, op, ae, fe, s));
+    else DT(sync_pass(D, fp, ap, n, ws, stage, op, ae, fe, s));
   }
   return CASYNC_OK;
 }
@@ -526,17 +476,27 @@ int64_t casync_sync_workspace_bytes(int mode, int batch) {
   return SyncWs(nullptr, batch < kMaxPass ? batch : kMaxPass, sync_net(mode)).bytes;
 }
 
-int casync_sync_create(int device_id, int mode, casync_sync_handle* out) {
+int64_t casync_syncnet_workspace_bytes_ex(int mode, int precision, int batch) {
+  if (precision == 0) return casync_sync_workspace_bytes(mode, batch);
+  if (precision != 1 || !sync_mode_ok(mode) || batch < 1 || batch > 65536) return 0;
+  return sync16_ws_bytes(batch < kMaxPass ? batch : kMaxPass, sync_net(mode));
+}
+
+int casync_syncnet_create_ex(int device_id, int mode, int precision, casync_sync_handle* out) {
   CASYNC_REQUIRE(out, "sync_create: null out");
   *out = nullptr;
   CASYNC_REQUIRE(sync_mode_ok(mode), "sync_create: mode %d (0 hubert, 1 wenet)", mode);
+  CASYNC_REQUIRE(precision == 0 || precision == 1, "sync_create: precision %d (0 fp32, 1 bf16)", precision);
   if (int st = casync_require_gfx950("sync_create", device_id)) return st;
   casync_sync* h = new casync_sync();
   h->device = device_id;
   h->mode = mode;
+  h->precision = precision;
   *out = h;
   return CASYNC_OK;
 }
+int casync_sync_create(int device_id, int mode, casync_sync_handle* out) { return casync_syncnet_create_ex(device_id, mode, 0, out); }
+int casync_syncnet_precision(casync_sync_handle h) { return h ? h->precision : -1; }
 
 void casync_sync_destroy(casync_sync_handle h) {
   if (!h) return;
@@ -548,12 +508,12 @@ void casync_sync_destroy(casync_sync_handle h) {
 
 int casync_sync_load_weights_host(casync_sync_handle h, const float* packed, int64_t n_floats) {
   CASYNC_REQUIRE(h, "sync_load_weights: null");
-  return h->pw.load_host("sync_load_weights", h->device, packed, n_floats, sync_net(h->mode).packed.total, false);
+  return h->pw.load_host("sync_load_weights", h->device, packed, n_floats, sync_net(h->mode).packed.total, h->precision == 1);
 }
 
 int casync_sync_load_weights_device(casync_sync_handle h, const float* packed_dev, int64_t n_floats) {
   CASYNC_REQUIRE(h, "sync_load_weights_device: null");
-  return h->pw.adopt_device("sync_load_weights_device", h->device, packed_dev, n_floats, sync_net(h->mode).packed.total, false);
+  return h->pw.adopt_device("sync_load_weights_device", h->device, packed_dev, n_floats, sync_net(h->mode).packed.total, h->precision == 1);
 }
 
 int casync_sync_forward(casync_sync_handle h, const float* face_dev, const float* audio_dev, int batch, float* audio_emb_dev,

@@ -28,6 +28,14 @@ EMBED_DIM = 4608                   # 512 channels x 3 x 3
 BN_EPS = 1e-5                      # nn.BatchNorm2d's default
 AUDIO_SHAPE = {"hubert": (32, 32, 32), "wenet": (256, 16, 32)}
 MAX_SHIFT = 4096                   # casync_op_sync_curve's limit
+PRECISIONS = {"fp32": 0, "bf16": 1}   # casync_syncnet_create_ex's numbers
+
+
+def check_precision(precision: str) -> int:
+    """-> the C ABI's number; ValueError for anything but "fp32" / "bf16" (before any device call)."""
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"SyncNet precision {precision!r}; the engine has {sorted(PRECISIONS)}")
+    return PRECISIONS[precision]
 
 
 def _stage(cin, cout, stride, pad, n_res):
@@ -141,18 +149,20 @@ def _stream(device) -> int:
 
 class SyncNetEngine(_PackedEngine):
     """SyncNet_color(mode).eval() on the HIP engine.  Inputs are float32 device tensors, contiguous: face [B,3,160,160] in
-    [0,1] (BGR), audio [B,32,32,32] (hubert) or [B,256,16,32] (wenet)."""
+    [0,1] (BGR), audio [B,32,32,32] (hubert) or [B,256,16,32] (wenet).  precision "bf16" runs the blocks on bf16 activations
+    and a bf16 image of the same packed buffer (include/casync_hip.h); inputs, embeddings and taps stay float32."""
 
     _destroy = "casync_sync_destroy"
 
-    def __init__(self, packed: np.ndarray, mode: str = "hubert", device: str = "cuda:0"):
+    def __init__(self, packed: np.ndarray, mode: str = "hubert", device: str = "cuda:0", precision: str = "fp32"):
         if mode not in AUDIO_SHAPE:
             raise ValueError(f"SyncNet mode {mode!r} ('hubert' or 'wenet')")
-        self.mode = mode
-        self._open(device, "casync_sync_create", (_lib.AUDIO_MODES[mode],), "casync_sync_load_weights_host", packed)
+        self._precision = check_precision(precision)
+        self.mode, self.precision = mode, precision
+        self._open(device, "casync_syncnet_create_ex", (_lib.AUDIO_MODES[mode], self._precision), "casync_sync_load_weights_host", packed)
 
     def workspace_bytes(self, batch: int) -> int:
-        need = self._lib.casync_sync_workspace_bytes(_lib.AUDIO_MODES[self.mode], batch)
+        need = self._lib.casync_syncnet_workspace_bytes_ex(_lib.AUDIO_MODES[self.mode], self._precision, batch)
         if need <= 0:
             raise ValueError(f"SyncNet engine: batch {batch} (1..65536)")
         return need
@@ -250,12 +260,13 @@ def curve_of(sim: torch.Tensor) -> OffsetCurve:
 
 class SyncNetColor:
     """The reference's SyncNet_color(mode) in eval mode: load_state_dict takes its 217 keys, forward returns
-    (audio_embedding, face_embedding)."""
+    (audio_embedding, face_embedding).  precision "fp32" (the default) or "bf16": SyncNetEngine's."""
 
-    def __init__(self, mode: str = "hubert", device: str = "cuda:0", state_dict=None):
+    def __init__(self, mode: str = "hubert", device: str = "cuda:0", state_dict=None, precision: str = "fp32"):
         if mode not in AUDIO_SHAPE:
             raise ValueError(f"SyncNet mode {mode!r} ('hubert' or 'wenet')")
-        self.mode = mode
+        check_precision(precision)
+        self.mode, self.precision = mode, precision
         self.device = torch.device(device)
         self._packed: Optional[np.ndarray] = None
         self._engine: Optional[SyncNetEngine] = None
@@ -282,7 +293,7 @@ class SyncNetColor:
             raise RuntimeError("SyncNetColor: no weights loaded (load_state_dict)")
         if self._engine is None:
             dev = self.device if self.device.index is not None else torch.device(self.device.type, 0)
-            self._engine = SyncNetEngine(self._packed, self.mode, dev)
+            self._engine = SyncNetEngine(self._packed, self.mode, dev, self.precision)
         return self._engine
 
     def forward(self, face_sequences: torch.Tensor, audio_sequences: torch.Tensor):

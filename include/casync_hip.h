@@ -788,6 +788,42 @@ int  casync_op_sync_to_nchw(const float* in, float* out, int batch, int hw, int 
 int  casync_op_sync_embed(const float* in, float* out, int batch, casync_stream stream);
 int  casync_op_sync_curve(const float* face_emb, const float* audio_emb, int n, int d, int max_shift, float* sim, casync_stream stream);
 
+/* ---- SyncNet_color, bf16 precision (additive to ABI 13) ---------------------- */
+/* A second precision of the handle above, chosen at creation: precision 0 is the fp32 handle (casync_sync_create is the _ex
+ * form with 0), 1 runs the network on bf16 activations; any other value is refused before any device call.  The three entries
+ * are spelled casync_syncnet_*: the set of casync_sync_* names is closed.  Precision 1:
+ *   face.0 (7x7) in fp32 from the fp32 weights on the fp32 NCHW input, one rounding to bf16 on the NHWC store; the audio window
+ *   rounded once to bf16 NHWC; every other block with bf16 operands (the weights from a bf16 image, round to nearest even, of
+ *   the packed buffer, made on the device at load_weights_*), fp32 accumulation over K in one fixed order, + the fp32 bias, +
+ *   the residual (bf16, widened) in fp32 before the ReLU, one rounding to bf16 on the store; the last block of each encoder
+ *   (face.16, audio.13) stores its fp32 sum unrounded and the embedding is computed from it as in the fp32 handle (float64
+ *   norm in a fixed order, LeakyReLU).  No K split, no atomics, no sum across frames: frame i of a batch has the bits of that
+ *   frame forwarded alone, whatever tile it lies in.  A batch above 256 frames runs in passes of 256.
+ * The packed layout is the same fp32 buffer.  casync_sync_load_weights_host / _device, casync_sync_forward, casync_sync_forward_tap
+ * and casync_sync_destroy take a handle of either precision: fp32 inputs, fp32 embeddings [batch,4608], every tap of a bf16
+ * stage widened to fp32 NCHW; the same forward gate.  _precision: 0 or 1 (-1 for a null handle).  _workspace_bytes_ex: the
+ * workspace of one precision (0 for an unknown precision or mode or a batch outside 1..65536); precision 1 needs half of
+ * precision 0.
+ * Single operators (the kernel ledger's entries), one per kernel of the bf16 precision; pointers named void* are bf16, NHWC,
+ * 16-byte aligned; weights of the convs bf16 [cout][(ky,kx,c)], bias fp32:
+ *   sync16_stem7:   casync_op_sync_stem7's arithmetic (x, w, bias fp32) -> out [batch,h,w,32] bf16.
+ *   sync16_conv5:   in [batch,h,w,32], w [64][800] -> out [batch,ho,wo,64] bf16 = relu(conv5x5 stride 2 pad 1 + bias).
+ *   sync16_conv3:   in [batch,h,w,cin], w [cout][9 cin], res NULL or [batch,ho,wo,cout] bf16 -> out bf16 = relu(conv3x3 + bias + res);
+ *                   cin a multiple of 32, cout of 64, strides 1..8, pad 0..8; tile = 64 or 16 output channels per workgroup (the
+ *                   handle takes 16 where 64 would make fewer than 64 workgroups); both tiles return the same bits.
+ *   sync16_conv1:   in [batch,h,w,cin], w [cout][cin] -> out [batch,h,w,cout] FP32 = relu(conv1x1 + bias), not rounded.
+ *   sync16_to_nchw: in [batch,hw,c] bf16 -> out [batch,c,hw] fp32.                                                         */
+int     casync_syncnet_create_ex(int device_id, int mode, int precision, casync_sync_handle* out);
+int     casync_syncnet_precision(casync_sync_handle h);
+int64_t casync_syncnet_workspace_bytes_ex(int mode, int precision, int batch);
+int  casync_op_sync16_stem7(const float* x, const float* w, const float* bias, void* out, int batch, int h, int w_, casync_stream stream);
+int  casync_op_sync16_conv5(const void* in, const void* w, const float* bias, void* out, int batch, int h, int w_, casync_stream stream);
+int  casync_op_sync16_conv3(const void* in, const void* w, const float* bias, const void* res, void* out, int batch, int h, int w_,
+                            int cin, int cout, int stride_h, int stride_w, int pad, int tile, casync_stream stream);
+int  casync_op_sync16_conv1(const void* in, const void* w, const float* bias, float* out, int batch, int h, int w_, int cin, int cout,
+                            casync_stream stream);
+int  casync_op_sync16_to_nchw(const void* in, float* out, int batch, int hw, int c, casync_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

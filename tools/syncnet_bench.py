@@ -2,11 +2,15 @@
 torch (tests/syncnet_ref.py) on the same GPU, in one process, the two alternating round by round.
 
     python tools/syncnet_bench.py [--modes hubert,wenet] [--batches 1,8,64] [--rounds 5] [--steps 10] [--warmup 3]
-                                  [--curve 1500,15] [--no-baseline] [--json profiles/syncnet.json]
+                                  [--curve 1500,15] [--no-baseline] [--json profiles/syncnet.json] [--precisions fp32,bf16]
 
 One JSON line per (mode, batch): the median and the range over the rounds of ms per forward (both encoders, both embeddings),
 pairs per second, and the same for torch; then one line for offset_curve's kernel at N x S (embeddings in, sim out) beside the
 same cosines in torch.  5.04 GMAC of convolution a pair (hubert; wenet 5.34): the TFLOP/s of the engine's median is quoted.
+
+--precisions fp32,bf16 adds the bf16 handle (precision="bf16") and, with the baseline, eager torch under bf16 autocast to the
+functions that alternate: bf16_* and torch_autocast_* figures on the same line, and the bf16 handle's median against the fp32
+handle, torch and torch under autocast.  The default, fp32 alone, prints what it always printed.
 
 The profiler run is a run of its own (never timed):
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/syncnet_bench.py --modes hubert --batches 8 --no-baseline --curve 0,0
@@ -83,6 +87,7 @@ def main():
     ap.add_argument("--curve", default="1500,15", help="N,S of the offset_curve line (0,0: none)")
     ap.add_argument("--no-baseline", action="store_true")
     ap.add_argument("--json")
+    ap.add_argument("--precisions", default="fp32", help="fp32, bf16 or fp32,bf16: the handles that alternate")
     ap.add_argument("--stats-from", help="directory of a rocprofv3 --kernel-trace --stats run")
     ap.add_argument("--forwards", type=int, default=0, help="forwards of the profiled process")
     a = ap.parse_args()
@@ -97,27 +102,55 @@ def main():
     import syncnet_ref
     from calipsync_amd import recipe, syncnet
     lines = []
+    precisions = a.precisions.split(",")
+    for p in precisions:
+        syncnet.check_precision(p)
     for mode in a.modes.split(","):
         sd = recipe.make_syncnet_state_dict(mode)
         net = syncnet.SyncNetColor(mode, "cuda:0", sd)
+        net16 = syncnet.SyncNetColor(mode, "cuda:0", sd, precision="bf16") if "bf16" in precisions else None
         folded = {k: torch.from_numpy(v).cuda() for k, v in syncnet.fold(sd, mode).items()}
         for b in (int(v) for v in a.batches.split(",")):
             x, au = (torch.from_numpy(v).cuda() for v in recipe.make_syncnet_inputs(min(b, 8), mode))
             x = x.repeat((b + x.shape[0] - 1) // x.shape[0], 1, 1, 1)[:b].contiguous()
             au = au.repeat((b + au.shape[0] - 1) // au.shape[0], 1, 1, 1)[:b].contiguous()
-            fns = {"engine": lambda: net(x, au)}
+            fns = {}
+            if "fp32" in precisions:
+                fns["engine"] = lambda: net(x, au)
+            if net16 is not None:
+                fns["bf16"] = lambda: net16(x, au)
+
+            def torch_forward():
+                with torch.no_grad():
+                    return syncnet_ref.forward(folded, x, au, mode)[:2]
+
+            def torch_autocast():
+                with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+                    return syncnet_ref.forward(folded, x, au, mode)[:2]
             if not a.no_baseline:
-                def torch_forward():
-                    with torch.no_grad():
-                        return syncnet_ref.forward(folded, x, au, mode)[:2]
                 fns["torch"] = torch_forward
+                if net16 is not None:
+                    fns["torch_autocast"] = torch_autocast
             ts = alternate(fns, a.rounds, a.steps, a.warmup)
-            res = {"mode": mode, "batch": b, **spread("engine", ts["engine"], b)}
-            res["engine_tflops"] = 2.0 * macs_per_pair(mode) * b / statistics.median(ts["engine"]) / 1e12
+            med = {k: statistics.median(v) for k, v in ts.items()}
+            res = {"mode": mode, "batch": b}
+            if "engine" in ts:
+                res.update(spread("engine", ts["engine"], b))
+                res["engine_tflops"] = 2.0 * macs_per_pair(mode) * b / med["engine"] / 1e12
+            if "bf16" in ts:
+                res.update(spread("bf16", ts["bf16"], b))
+                res["bf16_tflops"] = 2.0 * macs_per_pair(mode) * b / med["bf16"] / 1e12
+                if "engine" in ts:
+                    res["bf16_vs_fp32_engine"] = med["engine"] / med["bf16"]
             if not a.no_baseline:
-                d = max(float((p - q).abs().max()) for p, q in zip(torch_forward(), net(x, au)))
                 res.update(spread("torch", ts["torch"], b))
-                res.update(speedup_vs_torch=statistics.median(ts["torch"]) / statistics.median(ts["engine"]), max_abs_diff_vs_torch=d)
+                if "engine" in ts:
+                    d = max(float((p - q).abs().max()) for p, q in zip(torch_forward(), net(x, au)))
+                    res.update(speedup_vs_torch=med["torch"] / med["engine"], max_abs_diff_vs_torch=d)
+                if "bf16" in ts:
+                    res.update(spread("torch_autocast", ts["torch_autocast"], b))
+                    res.update(bf16_vs_torch=med["torch"] / med["bf16"], bf16_vs_torch_autocast=med["torch_autocast"] / med["bf16"],
+                               bf16_max_abs_diff_vs_torch=max(float((p - q).abs().max()) for p, q in zip(torch_forward(), net16(x, au))))
             lines.append(res)
             print(json.dumps(res), flush=True)
     n, s = (int(v) for v in a.curve.split(","))
