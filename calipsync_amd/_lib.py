@@ -258,6 +258,13 @@ _PROTOS = {
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_sync16_conv1": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "casync_op_sync16_to_nchw": (C.c_int, [C.c_void_p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # the audio front end, WAV bytes -> the normalised 16 kHz waveform (additive to ABI 13); audio_out_samples is host only, mono is
+    # calipsync_amd/audio.py MONO's number, the workspace holds float64 {mean, variance} at its head once audio_normalize has run
+    "casync_audio_out_samples": (c_i64, [c_i64, C.c_int]),
+    "casync_op_audio_workspace_bytes": (c_i64, [c_i64]),
+    "casync_op_audio_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, C.c_int, c_f32p, c_i64, c_f32p, c_i64,
+                                           C.c_void_p]),
+    "casync_op_audio_normalize": (C.c_int, [c_f32p, c_i64, C.c_void_p, c_f32p, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -224,8 +224,9 @@ class FrameSynthesizer:
         return originals() if callable(originals) else originals
 
     # ------------------------------------------------------------------ the loop (infer_api.py:359-451)
-    def iterate_synthesized_frames(self, features: np.ndarray, start_frame_idx: int = 0,
+    def iterate_synthesized_frames(self, features, start_frame_idx: int = 0,
                                    is_generate_sync_frame: bool = True) -> Iterator[Dict]:
+        """``features``: the [T,2,1024] array, uploaded once, or a torch tensor, used where it lies when it is on this device."""
         self.last_logical_index = start_frame_idx - 1
         time_stats = {"load_frame": 0.0, "get_audio": 0.0, "process_batch": 0.0}
         total_frames = len(features)
@@ -234,7 +235,10 @@ class FrameSynthesizer:
         try:
             if is_generate_sync_frame and total_frames:
                 t0 = time.time()   # one upload of the whole [T,2,1024] array replaces B x 128 KB per batch
-                features_dev = torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32)).to(self.device)
+                if isinstance(features, torch.Tensor):   # already a tensor (HubertExtractor.extract_features_device): no host hop
+                    features_dev = features.to(self.device, torch.float32).contiguous()
+                else:
+                    features_dev = torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32)).to(self.device)
                 time_stats["get_audio"] += time.time() - t0
             if self.resident and self._clip is None and total_frames:
                 from .resident_clip import ResidentClip
@@ -320,17 +324,22 @@ class VideoStreamManager:
     ``hubert_path`` is what the reference takes, a HuBERT checkpoint directory: the extractor
     (``calipsync_amd.hubert.HubertExtractor``, HubertModel on the HIP engine) is built from it on the first audio file
     that is not a ``.npy``, in ``hubert_precision`` ("fp32", the default, or "bf16").  It may also be a callable ``audio_path -> [T,2,1024] array``, and it is not used when
-    ``audio_path`` is itself a ``.npy`` of features.  The mp4 writer / ffmpeg mux (inference.py:88-110) is used when cv2 / ffmpeg exist; otherwise
+    ``audio_path`` is itself a ``.npy`` of features.  ``hubert_frontend`` ("reference", the default, or "device") is that extractor's
+    ``frontend``: "device" reads a PCM WAV of any rate without ffmpeg, resamples it on the device and hands the features to the frame
+    loop as a device tensor.  The mp4 writer / ffmpeg mux (inference.py:88-110) is used when cv2 / ffmpeg exist; otherwise
     the frames are written as a Motion-JPEG ``.avi`` with Pillow (``mjpeg_avi.py``; no audio track).  With ``output="jpeg",
     resident=True`` (passed on to ``FrameSynthesizer``) the frames are JPEG-encoded on the device and ``<stem>.avi`` is written
     from those bytes, wherever cv2 exists or not: no raw frame is held on the host.  ``jpeg_quality`` and ``jpeg_subsampling``
     travel the same way."""
 
     def __init__(self, data_dir: str, unet_checkpoint: Optional[str], hubert_path=None, device: str = "cuda:0",
-                 batch_size: int = 8, output_sample_rate: int = 24000, hubert_precision: str = "fp32", **synth_kwargs):
+                 batch_size: int = 8, output_sample_rate: int = 24000, hubert_precision: str = "fp32", hubert_frontend: str = "reference",
+                 **synth_kwargs):
+        from .audio import check_frontend
         from .hubert import check_precision
         check_precision(hubert_precision)   # ValueError before anything touches the device
         self._hubert_precision = hubert_precision
+        self._hubert_frontend = check_frontend(hubert_frontend)
         self.synthesizer = FrameSynthesizer(unet_checkpoint=unet_checkpoint, data_dir=data_dir, device=device,
                                             batch_size=batch_size, **synth_kwargs)
         self.hubert_extractor = hubert_path if callable(hubert_path) else None
@@ -346,8 +355,9 @@ class VideoStreamManager:
         else:
             if self.hubert_extractor is None and self._hubert_dir is not None:   # built on first use
                 from .hubert import HubertExtractor
-                self.hubert_extractor = HubertExtractor(os.fspath(self._hubert_dir), self._device,
-                                                        self._hubert_precision).extract_from_file
+                extractor = HubertExtractor(os.fspath(self._hubert_dir), self._device, self._hubert_precision, self._hubert_frontend)
+                # the "device" front end keeps the features on the device: the frame loop takes the tensor as it is
+                self.hubert_extractor = extractor.extract_features_device if self._hubert_frontend == "device" else extractor.extract_from_file
             if self.hubert_extractor is None:
                 raise RuntimeError("no HuBERT extractor configured: pass pre-extracted features (.npy), a HuBERT checkpoint "
                                    "directory or a callable")

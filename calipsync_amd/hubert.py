@@ -236,8 +236,10 @@ def normalize(speech: np.ndarray, do_normalize: bool = True) -> np.ndarray:
     return x
 
 
-def chunked_features(input_values: torch.Tensor, encode: Callable[[List[torch.Tensor]], List[torch.Tensor]]) -> torch.Tensor:
-    """The reference's chunking (hubert_extractor.py:27-58) over a [1, N] tensor.  ``encode(chunks)`` gets the chunk
+def chunked_features(input_values: torch.Tensor, encode: Callable[[List[torch.Tensor]], List[torch.Tensor]],
+                     keep_device: bool = False) -> torch.Tensor:
+    """The reference's chunking (hubert_extractor.py:27-58) over a [1, N] tensor; keep_device leaves the features where
+    ``encode`` made them (the same pad, trim and even length, the same bits) instead of downloading them.  ``encode(chunks)`` gets the chunk
     tensors ([1, n_i]) in order and returns one [T_i, 1024] tensor per chunk; it is called with the full-length chunks
     (320080 samples) of the clip first, then once more with the rest (a cut-short last chunk, the tail), so an engine
     can run each call as one batched forward."""
@@ -253,7 +255,9 @@ def chunked_features(input_values: torch.Tensor, encode: Callable[[List[torch.Te
     rest = [c for c in chunks if c.shape[1] != CHUNK]
     feats = (list(encode(full)) if full else []) + (list(encode(rest)) if rest else [])
     # (full chunks always precede the rest: only the last full-step chunk can be cut short, and the tail follows it)
-    features = torch.cat(feats, dim=0).cpu()      # raises on an empty list, as the reference does
+    features = torch.cat(feats, dim=0)            # raises on an empty list, as the reference does
+    if not keep_device:
+        features = features.cpu()
     if features.shape[0] < expected_t:
         features = torch.nn.functional.pad(features, (0, 0, 0, expected_t - features.shape[0]))
     else:
@@ -305,10 +309,20 @@ def load_audio_16k(path: str) -> np.ndarray:
 
 
 class HubertExtractor:
-    """The reference's HubertExtractor(hubert_path, device) on the HIP engine."""
+    """The reference's HubertExtractor(hubert_path, device) on the HIP engine.
 
-    def __init__(self, hubert_path: str, device: str = "cuda:0", precision: str = "fp32"):
+    ``frontend`` chooses what stands between an audio file and the engine.  "reference" (the default) is the reference's own:
+    ``ffmpeg -ar 16000 -ac 1`` where ffmpeg exists, else a 16 kHz WAV, normalised on the host.  "device" reads a PCM WAV of any
+    rate with the standard library and decodes, downmixes (``mono``: "mean" or "first"), resamples and normalises it on the
+    device (calipsync_amd/audio.py): it never looks for ffmpeg, and its resampler is scipy's polyphase filter, not ffmpeg's."""
+
+    def __init__(self, hubert_path: str, device: str = "cuda:0", precision: str = "fp32", frontend: str = "reference",
+                 mono: str = "mean"):
+        from . import audio
         check_precision(precision)
+        self.frontend = audio.check_frontend(frontend)     # ValueErrors before anything touches the device
+        audio.check_mono(mono)
+        self.mono = mono
         self.device = device
         cfg, sd, self.do_normalize = load_checkpoint(hubert_path)
         self.model = HubertEngine(sd, cfg["num_hidden_layers"], device, precision)
@@ -327,7 +341,21 @@ class HubertExtractor:
         input_values = torch.from_numpy(normalize(speech, self.do_normalize))[None]
         return chunked_features(input_values, self._encode)
 
+    @torch.no_grad()
+    def extract_features_device(self, audio_path: str) -> torch.Tensor:
+        """extract_from_file of the "device" front end without the download: the [T/2,2,1024] features as a tensor on the
+        device.  ValueError for an extractor of the "reference" front end, whose waveform is made on the host."""
+        if self.frontend != "device":
+            raise ValueError('extract_features_device needs HubertExtractor(frontend="device")')
+        from . import audio
+        pcm, rate, width = audio.read_pcm_wav(audio_path)
+        wave16k, normalised = audio.frontend_device(pcm, rate, width, self.mono, self.device)
+        input_values = (normalised if self.do_normalize else wave16k)[None]
+        return chunked_features(input_values, self._encode, keep_device=True)
+
     def extract_from_file(self, audio_path: str) -> np.ndarray:
+        if self.frontend == "device":
+            return self.extract_features_device(audio_path).cpu().numpy()
         return self.extract_features(load_audio_16k(audio_path)).detach().numpy()
 
     __call__ = extract_from_file

@@ -824,6 +824,32 @@ int  casync_op_sync16_conv1(const void* in, const void* w, const float* bias, fl
                             casync_stream stream);
 int  casync_op_sync16_to_nchw(const void* in, float* out, int batch, int hw, int c, casync_stream stream);
 
+/* ---- the audio front end: WAV bytes -> the normalised 16 kHz waveform (additive to ABI 13: four new symbols) ------- */
+/* What stands between a RIFF PCM file of any rate and casync_hubert_forward, on the device (calipsync_amd/audio.py frontend_host is
+ * the numpy twin; tests/golden/audio_resample_cases.npz holds recorded cases):
+ *   decode:    little-endian PCM of `width` bytes: u8 (v - 128) / 128, i16 v / 2^15, i24 v / 2^23, i32 v / 2^31, each an fp32 value.
+ *   downmix:   mono 0 ("mean"): the `channels` samples of a frame summed in channel order in fp32, divided once by channels;
+ *              mono 1 ("first"): channel 0.
+ *   resample:  y[k] = sum_i x[i] taps[k down + half - i up], half = (n_taps - 1) / 2, zeros outside both arrays, summed over
+ *              ascending i in one fp32 fma chain.  With the taps of audio.py resample_taps(rate) this is scipy.signal.resample_poly(x,
+ *              up, down) at its defaults.  up == down copies: y = x, taps_dev may be NULL.
+ *   normalise: out = (x - (float)mean) * (float)((var + 1e-7)^-1/2), mean and the population variance of the n samples summed in
+ *              float64, per block over a fixed span and then over the blocks: no atomics, the bits repeat from call to call.
+ *   audio_out_samples:        HOST ONLY.  ceil(n up / down) for up / down = 16000 / rate in lowest terms; -1 for n < 0 or rate < 1.
+ *   audio_workspace_bytes:    what audio_normalize needs for n_out samples (-1 for n_out < 1).
+ *   audio_resample:           pcm [frames * channels * width] bytes, taps_dev [n_taps] fp32 and out [n_out] fp32 are DEVICE memory;
+ *     n_out must be ceil(frames up / down).  pcm needs no alignment (16-byte loads are used where a frame never straddles one).
+ *   audio_normalize:          x [n] -> out [n] (out may be x); workspace 8-byte aligned, audio_workspace_bytes long.  When it
+ *     has run, the workspace starts with float64 mean, float64 variance.
+ * Refused with CASYNC_ERR_ARG before anything is launched: a null pointer, width outside 1..4, channels outside 1..16, mono
+ * other than 0 / 1, up or down < 1, frames < 1, an even n_taps, an n_out other than the formula's, a ratio whose outputs reach
+ * further than the kernel's input tile (down / up above about 15).  Enqueue on `stream`; no allocation, no synchronisation.   */
+int64_t casync_audio_out_samples(int64_t n, int rate);
+int64_t casync_op_audio_workspace_bytes(int64_t n_out);
+int     casync_op_audio_resample(const uint8_t* pcm, int width, int channels, int64_t frames, int mono, int up, int down,
+                                 const float* taps_dev, int64_t n_taps, float* out, int64_t n_out, casync_stream stream);
+int     casync_op_audio_normalize(const float* x, int64_t n, void* workspace, float* out, casync_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
