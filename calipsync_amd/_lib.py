@@ -227,6 +227,10 @@ _PROTOS = {
     "casync_op_jpegdec_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int, C.c_int, c_i64]),
     "casync_op_jpegdec_decode": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i64,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    # Motion-JPEG files -> frames (additive to ABI 13): the same record, its sampling word 0 (4:4:4), 1 (4:2:2), 2 (4:2:0) or 3 (gray)
+    "casync_op_mjpegdec_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int, c_i64]),
+    "casync_op_mjpegdec_decode": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_i64, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
     # SyncNet_color, the lip-sync judge (additive to ABI 13); mode is AUDIO_MODES' number
     "casync_sync_packed_count": (C.c_int, [C.c_int]),
     "casync_sync_packed_name": (C.c_char_p, [C.c_int, C.c_int]),

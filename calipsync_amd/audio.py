@@ -61,6 +61,15 @@ def read_pcm_wav(path: str) -> Tuple[np.ndarray, int, int]:
             raise ValueError(f"{path}: compressed WAV ({w.getcomptype()}); only PCM is read")
         ch, width, rate, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
         raw = w.readframes(n)
+    try:
+        return pcm_from_bytes(raw, ch, width), rate, width
+    except ValueError as exc:
+        raise ValueError(f"{path}: {exc}") from None
+
+
+def pcm_from_bytes(raw, channels: int, width: int) -> np.ndarray:
+    """Little-endian PCM bytes -> the integers [frames, C] of read_pcm_wav (the inverse of pcm_bytes): uint8 for 8-bit samples
+    (offset binary, as stored), int16, and int32 for 24- and 32-bit ones.  ValueError for another sample size."""
     if width == 1:
         x = np.frombuffer(raw, np.uint8)
     elif width == 2:
@@ -72,8 +81,8 @@ def read_pcm_wav(path: str) -> Tuple[np.ndarray, int, int]:
     elif width == 4:
         x = np.frombuffer(raw, "<i4")
     else:
-        raise ValueError(f"{path}: {8 * width}-bit samples")
-    return x.reshape(-1, ch), rate, width
+        raise ValueError(f"{8 * width}-bit samples")
+    return x.reshape(-1, channels)
 
 
 def pcm_bytes(pcm: np.ndarray, width: int) -> np.ndarray:

@@ -327,17 +327,28 @@ class VideoStreamManager:
     ``audio_path`` is itself a ``.npy`` of features.  ``hubert_frontend`` ("reference", the default, or "device") is that extractor's
     ``frontend``: "device" reads a PCM WAV of any rate without ffmpeg, resamples it on the device and hands the features to the frame
     loop as a device tensor.  The mp4 writer / ffmpeg mux (inference.py:88-110) is used when cv2 / ffmpeg exist; otherwise
-    the frames are written as a Motion-JPEG ``.avi`` with Pillow (``mjpeg_avi.py``; no audio track).  With ``output="jpeg",
+    the frames are written as a Motion-JPEG ``.avi`` with Pillow (``mjpeg_avi.py``).  With ``output="jpeg",
     resident=True`` (passed on to ``FrameSynthesizer``) the frames are JPEG-encoded on the device and ``<stem>.avi`` is written
     from those bytes, wherever cv2 exists or not: no raw frame is held on the host.  ``jpeg_quality`` and ``jpeg_subsampling``
-    travel the same way."""
+    travel the same way.
+
+    ``audio_track`` decides the sound of those two ``.avi`` files: "none", the default, writes them silent, as before; "pcm"
+    writes the input WAV's own samples beside the frames as an uncompressed PCM stream (``mjpeg_avi.write_mjpeg_avi(audio=)``),
+    so ``audio_path`` must then be a PCM WAV: a ``.npy`` of features, or a file ``audio.read_pcm_wav`` refuses, raises
+    ValueError before any frame is synthesised.  The samples keep their rate and width: ``output_sample_rate`` (kept for the
+    reference's signature) is not used on this path, nothing is resampled.  The cv2 + ffmpeg branch muxes as it always did."""
+
+    AUDIO_TRACKS = ("none", "pcm")
 
     def __init__(self, data_dir: str, unet_checkpoint: Optional[str], hubert_path=None, device: str = "cuda:0",
                  batch_size: int = 8, output_sample_rate: int = 24000, hubert_precision: str = "fp32", hubert_frontend: str = "reference",
-                 **synth_kwargs):
+                 audio_track: str = "none", **synth_kwargs):
         from .audio import check_frontend
         from .hubert import check_precision
         check_precision(hubert_precision)   # ValueError before anything touches the device
+        if audio_track not in self.AUDIO_TRACKS:
+            raise ValueError(f"VideoStreamManager: audio_track {audio_track!r} is neither 'none' nor 'pcm'")
+        self.audio_track = audio_track
         self._hubert_precision = hubert_precision
         self._hubert_frontend = check_frontend(hubert_frontend)
         self.synthesizer = FrameSynthesizer(unet_checkpoint=unet_checkpoint, data_dir=data_dir, device=device,
@@ -349,7 +360,23 @@ class VideoStreamManager:
         self.output_sample_rate = output_sample_rate
         self.fps = 25
 
+    def _pcm_track(self, audio_path: str):
+        """the (pcm, rate, width) that audio_track 'pcm' writes beside the frames; None for 'none'"""
+        if self.audio_track != "pcm":
+            return None
+        if audio_path.endswith(".npy"):
+            raise ValueError(f"VideoStreamManager: audio_track='pcm' needs a PCM WAV to write, {audio_path} holds features")
+        from .audio import read_pcm_wav
+        try:
+            return read_pcm_wav(audio_path)
+        except ValueError:
+            raise
+        except Exception as exc:                # wave.Error, EOFError: not a RIFF WAV at all
+            raise ValueError(f"VideoStreamManager: audio_track='pcm': {audio_path} is not a PCM WAV ({exc})") from exc
+
     def process_single_file(self, audio_path: str, output_path: str):
+        track = self._pcm_track(audio_path)     # before any frame is synthesised
+        sound = "NO audio track" if track is None else f"PCM audio at {track[1]} Hz"
         if audio_path.endswith(".npy"):
             features = np.load(audio_path)
         else:
@@ -369,8 +396,8 @@ class VideoStreamManager:
                 raise ValueError("no video frame was generated")
             out = os.path.splitext(output_path)[0] + ".avi"
             print(f"VideoStreamManager: output='jpeg' -- writing {out} (Motion-JPEG AVI of the device-encoded frames, {self.fps} fps, "
-                  f"NO audio track) instead of {output_path}")
-            mjpeg_avi.write_mjpeg_avi(out, files, fps=self.fps)
+                  f"{sound}) instead of {output_path}")
+            mjpeg_avi.write_mjpeg_avi(out, files, fps=self.fps, audio=track)
             return out
         frames = [info["frame"] for info in self.synthesizer.iterate_synthesized_frames(features, 0, True)]
         if not frames:
@@ -383,9 +410,9 @@ class VideoStreamManager:
             try:
                 from . import mjpeg_avi
                 out = os.path.splitext(output_path)[0] + ".avi"
-                print(f"VideoStreamManager: no OpenCV / ffmpeg here -- writing {out} (Motion-JPEG AVI, {self.fps} fps, NO audio track) "
+                print(f"VideoStreamManager: no OpenCV / ffmpeg here -- writing {out} (Motion-JPEG AVI, {self.fps} fps, {sound}) "
                       f"instead of {output_path}")
-                mjpeg_avi.write_mjpeg_avi(out, frames, fps=self.fps)
+                mjpeg_avi.write_mjpeg_avi(out, frames, fps=self.fps, audio=track)
                 return out
             except (ImportError, ValueError) as exc:      # no Pillow, or a clip past the 4 GiB AVI limit: the raw frames
                 print(f"VideoStreamManager: {exc}; writing the raw frames to {output_path}.npy")

@@ -18,7 +18,11 @@ a frame whose row outgrew its scratch slot, the subject of the CPU tests and the
 The way back, baseline JPEG files -> frames (csrc/jpeg_dec.hip), is the second half of this file:
 
     frames_dev = decode_jpeg_device(files)                 # B files of one size -> [B,H,W,3] uint8 BGR on the device
-    frame_bgr = decode_jpeg_host(data)                     # the same bytes from numpy: Pillow's, reversed to BGR"""
+    frame_bgr = decode_jpeg_host(data)                     # the same bytes from numpy: Pillow's, reversed to BGR
+
+``subset="mjpeg"`` on the decoding entries (csrc/jpeg_dec_mjpeg.hip) widens what they read from 4:4:4 and
+4:2:0 to what Motion-JPEG writers produce: 4:2:2, grayscale, and frames that leave out their Huffman tables.  "baseline" stays the
+default."""
 from __future__ import annotations
 
 import ctypes as C
@@ -508,23 +512,41 @@ class JpegCorrupt(ValueError):
         self.status = int(status)
 
 
+SUBSETS = ("baseline", "mjpeg")
+GRAY = 3                          # JpegInfo.subsampling of a one-component file; 0, 1 and 2 are Pillow's numbers for 4:4:4, 4:2:2 and 4:2:0
+# per sampling: the component of each block of an MCU (the slot map), and the MCU's height and width in pixels
+SLOT_MAPS = {0: (0, 1, 2), 1: (0, 0, 1, 2), 2: (0, 0, 0, 0, 1, 2), GRAY: (0,)}
+MCU_SIZES = {0: (8, 8), 1: (8, 16), 2: (16, 16), GRAY: (8, 8)}
+
+
+def _subset(subset) -> str:
+    if subset not in SUBSETS:
+        raise ValueError(f"jpeg: subset {subset!r} is neither 'baseline' nor 'mjpeg'")
+    return subset
+
+
 class JpegInfo:
-    """What parse_jpeg reads from the headers.  H, W; subsampling 0 (4:4:4) or 2 (4:2:0); qtables: per component int32 [64] in
-    zigzag order; dc_tables / ac_tables: per component (bits[16], vals) as the scan selects them; dc_sel / ac_sel: the table
-    ids (0 / 1); restart_interval in MCUs (0: none); scan_offset, scan_length: the entropy-coded bytes, markers included;
-    restart_offsets: byte offsets in the file of every RSTn marker."""
+    """What parse_jpeg reads from the headers.  H, W; subsampling 0 (4:4:4) or 2 (4:2:0), under subset="mjpeg" also 1 (4:2:2) and
+    3 (GRAY, one component); qtables: per component int32 [64] in zigzag order; dc_tables / ac_tables: per component (bits[16],
+    vals) as the scan selects them; dc_sel / ac_sel: the table ids (0 / 1); restart_interval in MCUs (0: none); scan_offset,
+    scan_length: the entropy-coded bytes, markers included; restart_offsets: byte offsets in the file of every RSTn marker."""
     __slots__ = ("H", "W", "subsampling", "qtables", "dc_tables", "ac_tables", "dc_sel", "ac_sel", "restart_interval", "scan_offset",
                  "scan_length", "restart_offsets")
 
     @property
+    def slot_components(self):
+        """the component of each block of an MCU, in stream order"""
+        return SLOT_MAPS[self.subsampling]
+
+    @property
     def blocks_per_mcu(self) -> int:
-        return 6 if self.subsampling else 3
+        return len(SLOT_MAPS[self.subsampling])
 
     @property
     def mcu_grid(self):
         """(MCU rows, MCUs per row)"""
-        s = 16 if self.subsampling else 8
-        return (self.H + s - 1) // s, (self.W + s - 1) // s
+        sh, sw = MCU_SIZES[self.subsampling]
+        return (self.H + sh - 1) // sh, (self.W + sw - 1) // sw
 
     def segments(self):
         """[(start, end)] of the restart segments, byte offsets relative to the scan's first byte, markers excluded"""
@@ -548,9 +570,13 @@ def _huff_ok(bits, vals) -> bool:
     return sum(bits) == len(vals) and len(vals) <= 256
 
 
-def parse_jpeg(data) -> JpegInfo:
+def parse_jpeg(data, subset: str = "baseline") -> JpegInfo:
     """The headers of a baseline file of the supported subset (SOF0, 8 bits, three components sampled 1x1 or 2x2 / 1x1 / 1x1, one
-    interleaved scan, 8-bit quantisation tables, Huffman tables 0 and 1, any restart interval); JpegUnsupported otherwise."""
+    interleaved scan, 8-bit quantisation tables, Huffman tables 0 and 1, any restart interval); JpegUnsupported otherwise.
+    ``subset="mjpeg"`` admits what Motion-JPEG writers add to that: 2x1 / 1x1 / 1x1 sampling (4:2:2), one component (grayscale:
+    a scan of single blocks), and a scan that names a Huffman table no DHT segment defines, which is then the Annex K table of
+    its class and id (the ``MJPG`` convention: libjpeg-turbo supplies the same tables)."""
+    wide = _subset(subset) == "mjpeg"
     data = bytes(data)
     n = len(data)
     if n < 4 or data[:2] != b"\xff\xd8":
@@ -585,22 +611,27 @@ def parse_jpeg(data) -> JpegInfo:
                 raise JpegUnsupported(f"jpeg: {body[0]}-bit samples")
             H, W = struct.unpack(">HH", body[1:5])
             nf = body[5]
-            if nf == 1:
+            if nf == 1 and not wide:
                 raise JpegUnsupported("jpeg: a grayscale file")
             if nf == 4:
                 raise JpegUnsupported("jpeg: a four-component (CMYK) file")
-            if nf != 3:
+            if nf not in (1, 3):
                 raise JpegUnsupported(f"jpeg: {nf} components")
             if H < 1 or W < 1:
                 raise JpegUnsupported("jpeg: a frame without a size (DNL)")
-            comps = [(body[6 + 3 * i], body[7 + 3 * i], body[8 + 3 * i]) for i in range(3)]
+            comps = [(body[6 + 3 * i], body[7 + 3 * i], body[8 + 3 * i]) for i in range(nf)]
             samp = tuple(c[1] for c in comps)
             if samp == (0x11, 0x11, 0x11):
                 sub = 0
             elif samp == (0x22, 0x11, 0x11):
                 sub = 2
+            elif wide and samp == (0x21, 0x11, 0x11):
+                sub = 1
+            elif nf == 1 and samp == (0x11,):
+                sub = GRAY
             else:
-                raise JpegUnsupported("jpeg: chroma sampling other than 4:4:4 and 4:2:0 (" + ", ".join(f"{s >> 4}x{s & 15}" for s in samp) + ")")
+                known = "4:4:4, 4:2:2 and 4:2:0" if wide else "4:4:4 and 4:2:0"
+                raise JpegUnsupported(f"jpeg: chroma sampling other than {known} (" + ", ".join(f"{s >> 4}x{s & 15}" for s in samp) + ")")
             frame = (H, W, sub, comps)
         elif m in (0xC1, 0xC2, 0xC3, 0xC5, 0xC6, 0xC7, 0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF, 0xCC):
             what = {0xC2: "a progressive file", 0xC1: "an extended sequential file", 0xC3: "a lossless file"}.get(
@@ -639,14 +670,16 @@ def parse_jpeg(data) -> JpegInfo:
             if frame is None:
                 raise JpegUnsupported("jpeg: a scan ahead of the frame header")
             H, W, sub, comps = frame
-            if adobe != 1:
+            nf = len(comps)
+            if adobe != 1 and nf == 3:
                 raise JpegUnsupported(f"jpeg: Adobe colour transform {adobe}, not YCbCr")
-            if len(body) < 1 or body[0] != 3 or len(body) < 10:
-                raise JpegUnsupported("jpeg: a scan that does not interleave the three components (several scans)")
-            sel = [(body[1 + 2 * i], body[2 + 2 * i]) for i in range(3)]
+            if len(body) < 1 or body[0] != nf or len(body) < 4 + 2 * nf:
+                raise JpegUnsupported("jpeg: a scan that does not interleave the three components (several scans)" if nf == 3 else
+                                      "jpeg: a scan that does not hold the file's one component")
+            sel = [(body[1 + 2 * i], body[2 + 2 * i]) for i in range(nf)]
             if [s[0] for s in sel] != [c[0] for c in comps]:
                 raise JpegUnsupported("jpeg: scan components out of frame order")
-            if tuple(body[7:10]) != (0, 63, 0):
+            if tuple(body[1 + 2 * nf:4 + 2 * nf]) != (0, 63, 0):
                 raise JpegUnsupported("jpeg: a scan with spectral selection or successive approximation")
             break
         # every other segment (APPn, COM, ...) is skipped
@@ -655,6 +688,9 @@ def parse_jpeg(data) -> JpegInfo:
     info.dc_sel, info.ac_sel = tuple(s[1] >> 4 for s in sel), tuple(s[1] & 15 for s in sel)
     if max(info.dc_sel + info.ac_sel) > 1:
         raise JpegUnsupported("jpeg: a Huffman table id above 1")
+    if wide:                                                     # a table the scan names and no DHT defines is Annex K's of that class and id
+        for key, table in (((0, 0), DC_LUMA), ((1, 0), AC_LUMA), ((0, 1), DC_CHROMA), ((1, 1), AC_CHROMA)):
+            huff.setdefault(key, (tuple(table[0]), bytes(table[1])))
     try:
         info.qtables = [qt[c[2]] for c in comps]
         info.dc_tables = [huff[(0, t)] for t in info.dc_sel]
@@ -732,7 +768,7 @@ class _Scan:
         self.info = info
         self.scan = bytes(data[info.scan_offset:info.scan_offset + info.scan_length])
         self.bpm = info.blocks_per_mcu
-        self.comp = Y420 if info.subsampling else (0, 1, 2)
+        self.comp = info.slot_components
         self.dc = [_lut16(*t).tolist() for t in info.dc_tables]
         self.ac = [_lut16(*t).tolist() for t in info.ac_tables]
         rows, cols = info.mcu_grid
@@ -824,9 +860,9 @@ def _decode_scan(info: JpegInfo, data: bytes):
     return coef, status
 
 
-def scan_status(data) -> int:
+def scan_status(data, subset: str = "baseline") -> int:
     """The status the device gives a file of the subset: 0, or the code of the first restart segment that breaks a rule"""
-    return _decode_scan(parse_jpeg(data), bytes(data))[1]
+    return _decode_scan(parse_jpeg(data, subset), bytes(data))[1]
 
 
 def _idct_pass(c, shift: int):
@@ -871,13 +907,34 @@ def _upsample_h2v2(c: np.ndarray, H: int, W: int) -> np.ndarray:
     return out[:H, :W]
 
 
+def _upsample_h2v1(c: np.ndarray, W: int) -> np.ndarray:
+    """libjpeg's h2v1_fancy_upsample of the real downsampled plane c [H, ceil(W/2)] -> [H, W]: the triangle filter along the row,
+    the first and the last column copied (what repeating the edge column gives under this rounding), no vertical filter"""
+    left = np.concatenate([c[:, :1], c[:, :-1]], axis=1)
+    right = np.concatenate([c[:, 1:], c[:, -1:]], axis=1)
+    out = np.empty((c.shape[0], 2 * c.shape[1]), dtype=np.int64)
+    out[:, 0::2] = (3 * c + left + 1) >> 2
+    out[:, 1::2] = (3 * c + right + 2) >> 2
+    return out[:, :W]
+
+
 def _pixels(info: JpegInfo, coef: np.ndarray) -> np.ndarray:
     """coefficients [blocks, 64] (zigzag order, stream order) -> BGR uint8 [H, W, 3]"""
     H, W = info.H, info.W
     rows, cols = info.mcu_grid
     bpm = info.blocks_per_mcu
     coef = coef.reshape(rows, cols, bpm, 64)
-    if info.subsampling:
+    if info.subsampling == GRAY:                                 # the Y plane is B, G and R
+        y = _idct_blocks(coef[:, :, 0].reshape(-1, 64), info.qtables[0]).reshape(rows, cols, 8, 8)
+        y = y.transpose(0, 2, 1, 3).reshape(rows * 8, cols * 8)[:H, :W]
+        return np.ascontiguousarray(np.repeat(y[:, :, None], 3, axis=2).astype(np.uint8))
+    if info.subsampling == 1:                                    # 4:2:2: an MCU of 16 x 8 pixels, slots (Y, Y, Cb, Cr)
+        y = _idct_blocks(coef[:, :, :2].reshape(-1, 64), info.qtables[0]).reshape(rows, cols, 2, 8, 8)
+        planes = [y.transpose(0, 3, 1, 2, 4).reshape(rows * 8, cols * 16)[:H, :W]]
+        for c in (1, 2):
+            p = _idct_blocks(coef[:, :, 1 + c].reshape(-1, 64), info.qtables[c]).reshape(rows, cols, 8, 8)
+            planes.append(_upsample_h2v1(p.transpose(0, 2, 1, 3).reshape(rows * 8, cols * 8)[:H, :(W + 1) // 2], W))
+    elif info.subsampling:
         y = _idct_blocks(coef[:, :, :4].reshape(-1, 64), info.qtables[0]).reshape(rows, cols, 2, 2, 8, 8)
         y = y.transpose(0, 2, 4, 1, 3, 5).reshape(rows * 16, cols * 16)[:H, :W]
         planes = [y]
@@ -897,12 +954,12 @@ def _pixels(info: JpegInfo, coef: np.ndarray) -> np.ndarray:
     return np.clip(np.stack([b, g, r], axis=-1), 0, 255).astype(np.uint8)
 
 
-def decode_jpeg_host(data) -> np.ndarray:
+def decode_jpeg_host(data, subset: str = "baseline") -> np.ndarray:
     """A baseline JPEG file of the subset -> BGR uint8 [H, W, 3], the numpy twin of the device decoder: the bytes of Pillow's
-    ``Image.open(...).convert("RGB")``, reversed to BGR.  JpegUnsupported for a file outside the subset, JpegCorrupt (with the
-    device's status code) for a scan that breaks a rule."""
+    ``Image.open(...).convert("RGB")``, reversed to BGR.  JpegUnsupported for a file outside the subset (``subset="mjpeg"``: the
+    wider one of parse_jpeg), JpegCorrupt (with the device's status code) for a scan that breaks a rule."""
     data = bytes(data)
-    info = parse_jpeg(data)
+    info = parse_jpeg(data, subset)
     coef, status = _decode_scan(info, data)
     if status:
         raise JpegCorrupt(status, f"jpeg: the scan is damaged (status {status})")
@@ -1024,9 +1081,9 @@ def _device_tables(info: JpegInfo) -> bytes:
     """The table block of one frame, TAB_BYTES: quantisation [3][64] u16 in natural order | the DC table (0 / 1) of each component,
     0 | the AC table of each, 0 | the Huffman tables DC 0, DC 1, AC 0, AC 1 (zeros where the file has none)"""
     q = np.zeros((3, 64), dtype=np.uint16)
-    for c in range(3):
+    for c in range(len(info.qtables)):                           # a grayscale file fills component 0 alone
         q[c, list(ZIGZAG)] = info.qtables[c]
-    out = q.tobytes() + bytes(info.dc_sel) + b"\0" + bytes(info.ac_sel) + b"\0"
+    out = q.tobytes() + bytes(info.dc_sel).ljust(4, b"\0") + bytes(info.ac_sel).ljust(4, b"\0")
     for cls, sel, tables in ((0, info.dc_sel, info.dc_tables), (1, info.ac_sel, info.ac_tables)):
         for t in (0, 1):
             out += _device_huffman(*tables[sel.index(t)]) if t in sel else b"\0" * 832
@@ -1037,13 +1094,15 @@ def _device_tables(info: JpegInfo) -> bytes:
 class DecodePlan:
     """What casync_op_jpegdec_decode wants for a batch of files: blob (uint8: each file's scan, segment list and table block,
     4-byte aligned), rec (int32 [B, 16], see include/casync_hip.h), infos (JpegInfo, or the JpegUnsupported of a file outside the
-    subset, whose record carries status 1 and nothing else), total_sub, subsampling (2: every file is 4:2:0, else 0)"""
-    __slots__ = ("blob", "rec", "infos", "total_sub", "subsampling", "H", "W", "chunk_bits")
+    subset, whose record carries status 1 and nothing else), total_sub, subsampling (2: every file is 4:2:0, else 0), subset
+    ("mjpeg": the records are casync_op_mjpegdec_decode's, whose sampling word also takes 1, 4:2:2, and 3, grayscale)"""
+    __slots__ = ("blob", "rec", "infos", "total_sub", "subsampling", "H", "W", "chunk_bits", "subset")
 
 
-def plan_decode(files, chunk_bits: int = 0) -> DecodePlan:
+def plan_decode(files, chunk_bits: int = 0, subset: str = "baseline") -> DecodePlan:
     chunk = _chunk_bits(chunk_bits)
     plan = DecodePlan()
+    plan.subset = _subset(subset)
     plan.chunk_bits = chunk
     plan.infos = []
     parts, at, total = [], 0, 0
@@ -1061,7 +1120,7 @@ def plan_decode(files, chunk_bits: int = 0) -> DecodePlan:
         data = bytes(data)
         rec[i, 8] = total
         try:
-            info = parse_jpeg(data)
+            info = parse_jpeg(data, subset)
             if info.scan_length >= 1 << 27:
                 raise JpegUnsupported("jpeg: a scan of 128 MiB or more")
         except JpegUnsupported as exc:
@@ -1098,10 +1157,16 @@ def plan_decode(files, chunk_bits: int = 0) -> DecodePlan:
 
 
 def decode_jpeg_op(plan: DecodePlan, data, scratch, out, status, H: int = 0, W: int = 0) -> None:
-    """casync_op_jpegdec_decode on torch's current stream, every buffer the caller's (uint8 data holding plan.blob, uint8 scratch,
-    uint8 out [B,H,W,3], int32 status [B]); nothing is waited for."""
+    """casync_op_jpegdec_decode (casync_op_mjpegdec_decode for a plan of subset "mjpeg") on torch's current stream, every buffer
+    the caller's (uint8 data holding plan.blob, uint8 scratch, uint8 out [B,H,W,3], int32 status [B]); nothing is waited for."""
     import torch
     from . import _lib
+    if plan.subset == "mjpeg":
+        _lib.check(_lib.load().casync_op_mjpegdec_decode(data.data_ptr(), data.numel(), plan.rec.ctypes.data, plan.rec.shape[0], H or plan.H,
+                                                         W or plan.W, plan.chunk_bits, scratch.data_ptr(), scratch.numel(), out.data_ptr(),
+                                                         status.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream),
+                   "casync_op_mjpegdec_decode")
+        return
     _lib.check(_lib.load().casync_op_jpegdec_decode(data.data_ptr(), data.numel(), plan.rec.ctypes.data, plan.rec.shape[0], H or plan.H, W or plan.W,
                                                     plan.subsampling, plan.chunk_bits, scratch.data_ptr(), scratch.numel(), out.data_ptr(),
                                                     status.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream), "casync_op_jpegdec_decode")
@@ -1115,20 +1180,36 @@ def _decode_pillow(data) -> np.ndarray:
         return np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, ::-1])
 
 
-def decode_jpeg_device(files, *, device="cuda:0", chunk_bits: int = 0, fallback: str = "host", out=None):
+def workspace_bytes(plan: DecodePlan, B: int, H: int, W: int) -> int:
+    """the scratch the plan's entry wants for B frames of H x W (the entry's own error where it refuses the arguments)"""
+    from . import _lib
+    lib = _lib.load()
+    if plan.subset == "mjpeg":
+        entry, need = "casync_op_mjpegdec_workspace_bytes", lib.casync_op_mjpegdec_workspace_bytes(B, H, W, plan.total_sub)
+    else:
+        entry, need = "casync_op_jpegdec_workspace_bytes", lib.casync_op_jpegdec_workspace_bytes(B, H, W, plan.subsampling, plan.total_sub)
+    if need < 0:
+        _lib.check(int(need), entry)
+    return int(need)
+
+
+def decode_jpeg_device(files, *, device="cuda:0", chunk_bits: int = 0, fallback: str = "host", out=None, subset: str = "baseline"):
     """A sequence of JPEG files (bytes) of one size -> uint8 [B,H,W,3] BGR on the device, decoded there (csrc/jpeg_dec.hip): the
     compressed bytes go up in one pinned copy, and what comes back is the B status words.  A file outside the subset
     (parse_jpeg), or one whose device status is non-zero, is decoded on the host with Pillow and uploaded into its slot; with
     ``fallback="raise"`` it raises instead, naming the file's index.  ``chunk_bits`` (0: the default, 2048) is the length of the
-    subsequences the entropy stage cuts a scan into.  ``out``: a contiguous uint8 [B,H,W,3] device tensor to decode into."""
+    subsequences the entropy stage cuts a scan into.  ``out``: a contiguous uint8 [B,H,W,3] device tensor to decode into.
+    ``subset="mjpeg"`` sends the whole batch through the wider decoder (csrc/jpeg_dec_mjpeg.hip): 4:2:2 and grayscale files and
+    files without their Huffman tables are decoded on the device as well, and one batch may mix all four samplings."""
     import torch
+    _subset(subset)
     if fallback not in ("host", "raise"):
         raise ValueError(f"decode_jpeg_device: fallback {fallback!r} is neither 'host' nor 'raise'")
     files = [bytes(f) for f in files]
     dev = torch.device(device) if out is None else out.device
     if dev.type != "cuda":
         raise RuntimeError("decode_jpeg_device needs a ROCm device (decode_jpeg_host is the host decoder)")
-    plan = plan_decode(files, chunk_bits)
+    plan = plan_decode(files, chunk_bits, subset)
     B = len(files)
     if B == 0:
         return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=dev) if out is None else out
@@ -1147,11 +1228,8 @@ def decode_jpeg_device(files, *, device="cuda:0", chunk_bits: int = 0, fallback:
     H, W = (int(v) for v in next(iter(sizes)))
     if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W, 3) or not out.is_contiguous()):
         raise ValueError(f"decode_jpeg_device: out must be a contiguous uint8 {(B, H, W, 3)} tensor, got {tuple(out.shape)} {out.dtype}")
-    from . import _lib, frame_loop
-    lib = _lib.load()
-    need = lib.casync_op_jpegdec_workspace_bytes(B, H, W, plan.subsampling, plan.total_sub)
-    if need < 0:
-        _lib.check(int(need), "casync_op_jpegdec_workspace_bytes")
+    from . import frame_loop
+    need = workspace_bytes(plan, B, H, W)
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)

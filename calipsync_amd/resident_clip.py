@@ -161,6 +161,7 @@ class ResidentClip:
         if self.device.type != "cuda":
             raise RuntimeError("ResidentClip needs a ROCm device (no CPU fallback)")
         self.source_index = None
+        self.audio, self.fps = None, None       # from_video: the file's PCM sound track (pcm, rate, width) and its frame rate
         self._inflight: list = []            # (event, pinned record block) of batches the GPU may still be reading
         if isinstance(frames, torch.Tensor) and (frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3):
             raise ValueError(f"ResidentClip: frames {tuple(frames.shape)} {frames.dtype}, expected uint8 [N,H,W,3]")
@@ -333,11 +334,19 @@ class ResidentClip:
         if n_in < 1:
             raise ValueError("ResidentClip.from_frames: no frames")
         shape = tuple(int(v) for v in frames_bgr.shape[1:]) if is_tensor else tuple(np.asarray(frames_bgr[0]).shape)
+        parts = (frames_bgr[at:at + chunk] for at in range(0, n_in, chunk))
+        return cls._from_parts(parts, n_in, shape, landmark_detector, boxes, chunk, masks, "ResidentClip.from_frames")
+
+    @classmethod
+    def _from_parts(cls, parts, n_in: int, shape, landmark_detector, boxes, chunk: int, masks, who: str) -> "ResidentClip":
+        """from_frames on frames that arrive ``chunk`` at a time (host frames, or uint8 [n,H,W,3] tensors already on the device)"""
+        from . import face_ops
+        dev = landmark_detector.pfld_backbone.device
         cls._check_size(n_in, shape)
         stager = face_ops.FrameStager(dev)
         kept, landmarks, store = [], [], None
-        for at in range(0, n_in, chunk):
-            part = stager.upload(frames_bgr[at:at + chunk], "ResidentClip.from_frames", "frame_loop.submit_batch_device")
+        for at, frames in zip(range(0, n_in, chunk), parts):
+            part = stager.upload(frames, who, "frame_loop.submit_batch_device")
             if store is None:
                 store = torch.empty((n_in,) + tuple(part.shape[1:]), dtype=torch.uint8, device=part.device)
             found = landmark_detector.detect_landmarks_device(part.flip(-1).contiguous(),
@@ -348,9 +357,43 @@ class ResidentClip:
             kept += [at + i for i in keep]
             landmarks += [found[i][0] for i in keep]
         if not kept:
-            raise ValueError("ResidentClip.from_frames: no face in any frame")
+            raise ValueError(f"{who}: no face in any frame")
         clip = cls(store[:len(kept)], landmarks, None if masks is None else [masks[i] for i in kept], dev)
         clip.source_index = kept
+        return clip
+
+    @classmethod
+    def from_video(cls, path: str, landmark_detector, *, chunk: int = 32, decode: str = "device", boxes=None, masks=None) -> "ResidentClip":
+        """A Motion-JPEG AVI file to a clip (``mjpeg_avi.read_avi``): ``chunk`` frames at a time are decoded and go the way of
+        ``from_frames`` (landmarks from ``landmark_detector``, or from ``boxes``; frames without a face are left out and
+        ``source_index`` names the kept ones).  ``decode="device"``: ``jpeg.decode_jpeg_device(subset="mjpeg")`` decodes the
+        files where the clip lives, so that the compressed bytes cross to the device, not the pixels (4:4:4, 4:2:2, 4:2:0 and
+        grayscale frames, with or without their Huffman tables; any other JPEG is decoded by Pillow and uploaded);
+        ``decode="host"``: Pillow decodes every frame.  Both give the same bytes.  ``clip.audio`` holds the file's PCM sound
+        track as ``audio.read_pcm_wav`` would return it, or None; ``clip.fps`` its frame rate."""
+        from . import jpeg, mjpeg_avi
+        if decode not in ("host", "device"):
+            raise ValueError(f"ResidentClip.from_video: decode {decode!r} is neither 'host' nor 'device'")
+        if int(chunk) < 1:
+            raise ValueError(f"ResidentClip.from_video: chunk {chunk}")
+        avi = mjpeg_avi.read_avi(path)
+        dev = landmark_detector.pfld_backbone.device
+        files, n_in = avi.frames, len(avi.frames)
+
+        def parts():
+            for at in range(0, n_in, chunk):
+                try:
+                    if decode == "device":
+                        yield jpeg.decode_jpeg_device(files[at:at + chunk], device=dev, subset="mjpeg")
+                    else:
+                        yield [jpeg._decode_pillow(f) for f in files[at:at + chunk]]
+                except jpeg.JpegUnreadable as exc:
+                    raise ValueError(f"ResidentClip.from_video: cannot read frame {at + exc.index} of {path}") from exc
+                except OSError as exc:
+                    raise ValueError(f"ResidentClip.from_video: cannot read a frame in {at}..{at + chunk - 1} of {path}: {exc}") from exc
+
+        clip = cls._from_parts(parts(), n_in, (avi.height, avi.width, 3), landmark_detector, boxes, int(chunk), masks, "ResidentClip.from_video")
+        clip.audio, clip.fps = avi.audio, avi.fps
         return clip
 
     def __len__(self) -> int:

@@ -46,7 +46,7 @@ enum {
 #define CASYNC_ABI_VERSION 13  /* 12: S3FD face detector handle (casync_s3fd_*, casync_op_s3fd_*); 13: its bf16 precision
                                 * (casync_s3fd_create_ex, _precision, _workspace_bytes_ex, casync_op_s3fd16_*).  The face-pipeline
                                 * operators at the end of this file (casync_op_resize_linear_u8, _face_crops192, _s3fd_candidates,
-                                * _landmarks_finalize), casync_op_s3fd_nms, casync_op_clip_gather / _compose, casync_op_jpeg_*, casync_op_jpeg420_* and casync_op_jpegdec_* were added under 13: new symbols only, no prototype or layout changed */
+                                * _landmarks_finalize), casync_op_s3fd_nms, casync_op_clip_gather / _compose, casync_op_jpeg_*, casync_op_jpeg420_*, casync_op_jpegdec_* and casync_op_mjpegdec_* were added under 13: new symbols only, no prototype or layout changed */
 int         casync_abi_version(void);
 const char* casync_last_error(void);           /* thread-local message         */
 
@@ -734,6 +734,23 @@ int64_t casync_op_jpegdec_workspace_bytes(int batch, int H, int W, int subsampli
 int     casync_op_jpegdec_decode(const uint8_t* data, int64_t data_bytes, const int32_t* rec, int batch, int H, int W, int subsampling,
                                  int chunk_bits, uint8_t* scratch, int64_t scratch_bytes, uint8_t* out, int32_t* status,
                                  casync_stream stream);
+
+/* ---- Motion-JPEG files -> frames (additive to ABI 13: two new symbols, nothing else changed) ----------------------- */
+/* casync_op_jpegdec_decode's wider sibling (csrc/jpeg_dec_mjpeg.hip; what the two share is csrc/jpeg_dec_common.h): the same
+ * data, segment lists, table blocks, records, status codes, refusals and four stages, with the sampling word of a record taking
+ *   0: 4:4:4, an MCU of 8 x 8 pixels, slots Y Cb Cr;          1: 4:2:2 (2x1 / 1x1 / 1x1), 16 x 8, slots Y Y Cb Cr;
+ *   2: 4:2:0, 16 x 16, slots Y Y Y Y Cb Cr;                    3: grayscale, one component, a scan of single 8 x 8 blocks,
+ * and any other value refused.  One call decodes a batch whose records mix the four; the scratch is sized for the largest of them,
+ * so there is no `subsampling` argument.  4:2:2 chroma goes through libjpeg's h2v1 fancy upsampling of the real ceil(W/2)
+ * columns (out[2i] = (3 c[i] + c[i-1] + 1) >> 2, out[2i+1] = (3 c[i] + c[i+1] + 2) >> 2, the first and last column copied, no
+ * vertical filter); a grayscale file's Y is written to B, G and R; its table block holds component 0's quantisation table and
+ * table selectors, the rest zero.  A file that leaves out Huffman tables (the MJPG convention) is the host's business: its table
+ * block carries the Annex K table of the class and id the scan names (calipsync_amd/jpeg.py parse_jpeg(subset="mjpeg")).
+ * calipsync_amd/jpeg.py decode_jpeg_host(subset="mjpeg") is the numpy twin; tests/golden/mjpeg_decode_cases.npz holds recorded
+ * files and Pillow's pixels.  4:4:4 and 4:2:0 records give the bytes casync_op_jpegdec_decode gives.                        */
+int64_t casync_op_mjpegdec_workspace_bytes(int batch, int H, int W, int64_t total_subsequences);
+int     casync_op_mjpegdec_decode(const uint8_t* data, int64_t data_bytes, const int32_t* rec, int batch, int H, int W, int chunk_bits,
+                                  uint8_t* scratch, int64_t scratch_bytes, uint8_t* out, int32_t* status, casync_stream stream);
 
 /* ---- SyncNet_color, the lip-sync judge (additive to ABI 13: new symbols, nothing else changed) --------------------- */
 /* The reference's SyncNet_color (module/syncnet.py:155-246) in eval mode, fp32: a face encoder of 17 conv + BatchNorm (+ x)
