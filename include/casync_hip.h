@@ -711,7 +711,7 @@ int     casync_op_jpeg420_encode(const uint8_t* frames_bgr, int batch, int H, in
  *     { scan byte offset in data, scan bytes, sampling (0: 4:4:4, 2: 4:2:0), restart interval in MCUs (0: none), segments,
  *       segment list byte offset, table block byte offset, subsequences, index of its first subsequence among the batch's,
  *       status decided on the host (0; otherwise the frame gets that status, no subsequences and no work), 0 ... }
- *   subsampling: 2 sizes the scratch for 4:2:0 files only, 0 for either.  chunk_bits: a multiple of 32 in 32..2^30.  A frame has
+ *   subsampling: 2 sizes the scratch for 4:2:0 files only (a 4:4:4 record without a status is then refused), 0 for either.  chunk_bits: a multiple of 32 in 32..2^30.  A frame has
  *     at most 2^17 subsequences: the plan runs at most as many rounds as a frame has subsequences and a round sweeps them all, so
  *     this bounds the time one workgroup can be kept busy by a file that never synchronises (a record above it is refused; the
  *     caller takes a longer chunk_bits or the host path, as calipsync_amd/jpeg.py plan_decode does).
