@@ -52,7 +52,7 @@ SOURCES_JPEG420 = ["jpeg_enc420.hip"]
 OBJ_DIR_JPEGDEC = os.path.join(LIB_DIR, "obj_jpegdec")
 SOURCES_JPEGDEC = ["jpeg_dec.hip"]
 # The kernels of the SyncNet_color handle (tests/kernel_ledger_sync.py is their ledger): a twelfth object directory, its source an
-# entry of SOURCES in the same way.  The 3x3 and 1x1 blocks of that network run on launchers of lib/obj/ (no new instance there).
+# entry of SOURCES in the same way.  Only the two 1x1 blocks and the audio window's transpose run on launchers of lib/obj/ (no new instance there).
 OBJ_DIR_SYNC = os.path.join(LIB_DIR, "obj_sync")
 SOURCES_SYNC = ["syncnet.hip"]
 # The kernels of the bf16 precision of the SyncNet_color handle (tests/kernel_ledger_sync16.py is their ledger): a thirteenth object

@@ -18,8 +18,10 @@
 // section 8k).  The two 1x1 blocks (K = 512) run on the data-parallel ring GEMM (launch_rows_gemm), the audio window goes to NHWC
 // with launch_nchw_to_nhwc: no stream-K, no K split.  No kernel here sums across frames or uses an atomic: frame i of a batch has
 // the bits of that frame forwarded alone.
-// The block table, the handle and what the bf16 precision of this handle (syncnet_bf16.hip) calls of this file are declared in
-// syncnet_common.h; a handle of precision 1 takes sync_run's checks and gate and then that file's pass.
+// The network's order is written once, in sync_blocks<P> / sync_pass<P>; a precision is a policy P (SyncF32, SyncBF16) that names
+// its element type, its launchers and the image its matrices come from.  sync_pass<SyncBF16> is the same walk on bf16
+// activations with the kernels of syncnet_bf16.hip.  The block table, the handle and the stem / to_nchw bodies both objects
+// compile are in syncnet_common.h.
 #include <string.h>
 
 #include <mutex>
@@ -30,67 +32,12 @@
 
 namespace {
 
-__device__ __forceinline__ float relu(float v) { return v > 0.f ? v : 0.f; }
-
 // ------------------------------------------------------------------------------------------------ stem (7x7)
-constexpr int S7_T = 16;            // output tile
-constexpr int S7_IN = S7_T + 6;     // with the halo
-constexpr int S7_LD = S7_IN + 1;    // LDS row stride (odd)
-constexpr int S7_C = 32, S7_K = 147;
-
-// x [B,3,H,W], w [(ky,kx,ci)=147][32], out [B,H,W,32]; one thread per output pixel of the tile, all 32 channels
+// sync_stem7_body (syncnet_common.h) with the fp32 store
 __global__ __launch_bounds__(256) void sync_stem7_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ bias, float* __restrict__ out, int H, int W, int tiles_x,
                                                          int tiles_y) {
-  __shared__ float xs[3][S7_IN][S7_LD];
-  __shared__ __attribute__((aligned(16))) float ws[S7_K * S7_C];
-  const int tid = threadIdx.x;
-  long long t = blockIdx.x;
-  const int tx = (int)(t % tiles_x);
-  t /= tiles_x;
-  const int ty = (int)(t % tiles_y);
-  const long long b = t / tiles_y;
-  const int x0 = tx * S7_T, y0 = ty * S7_T;
-  for (int i = tid; i < S7_K * S7_C / 4; i += 256) reinterpret_cast<f32x4*>(ws)[i] = reinterpret_cast<const f32x4*>(w)[i];
-  for (int i = tid; i < 3 * S7_IN * S7_IN; i += 256) {
-    const int ci = i / (S7_IN * S7_IN), r = i - ci * (S7_IN * S7_IN), ly = r / S7_IN, lx = r - ly * S7_IN;
-    const int iy = y0 + ly - 3, ix = x0 + lx - 3;
-    float v = 0.f;
-    if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = x[((b * 3 + ci) * H + iy) * (long long)W + ix];
-    xs[ci][ly][lx] = v;
-  }
-  __syncthreads();
-  const int px = tid & (S7_T - 1), py = tid / S7_T;
-  float acc[S7_C];
-#pragma unroll
-  for (int c = 0; c < S7_C; ++c) acc[c] = bias[c];
-#pragma unroll 1
-  for (int ky = 0; ky < 7; ++ky) {
-#pragma unroll 1
-    for (int kx = 0; kx < 7; ++kx) {
-#pragma unroll
-      for (int ci = 0; ci < 3; ++ci) {
-        const float in = xs[ci][py + ky][px + kx];
-        const float* wr = ws + ((ky * 7 + kx) * 3 + ci) * S7_C;
-#pragma unroll
-        for (int c4 = 0; c4 < S7_C / 4; ++c4) {
-          const f32x4 wv = *reinterpret_cast<const f32x4*>(wr + c4 * 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {   // the result pinned: no packed FMA around a scalar from the high half of a register pair
-            float a = fmaf(wv[e], in, acc[c4 * 4 + e]);   // (ir_common.h fma4_scalar)
-            asm("" : "+v"(a));
-            acc[c4 * 4 + e] = a;
-          }
-        }
-      }
-    }
-  }
-  const int oy = y0 + py, ox = x0 + px;
-  if (oy >= H || ox >= W) return;
-  float* o = out + ((b * H + oy) * (long long)W + ox) * S7_C;
-#pragma unroll
-  for (int c4 = 0; c4 < S7_C / 4; ++c4)
-    *reinterpret_cast<f32x4*>(o + c4 * 4) = f32x4{relu(acc[c4 * 4]), relu(acc[c4 * 4 + 1]), relu(acc[c4 * 4 + 2]), relu(acc[c4 * 4 + 3])};
+  sync_stem7_body(x, w, bias, out, H, W, tiles_x, tiles_y);
 }
 
 // ------------------------------------------------------------------------------------------------ dense KS x KS conv
@@ -196,16 +143,10 @@ __global__ __launch_bounds__(256) void sync_relu_kernel(float* __restrict__ x, l
 }
 
 // ------------------------------------------------------------------------------------------------ NHWC -> NCHW
-// in [B,HW,C] -> out [B,C,HW] (a debug tap: one element per lane)
+// in [B,HW,C] -> out [B,C,HW]: sync_to_nchw_body (syncnet_common.h) on fp32
 __global__ __launch_bounds__(256) void sync_to_nchw_kernel(const float* __restrict__ in, float* __restrict__ out, long long total, int HW,
                                                            int C) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int p = (int)(idx % HW);
-  const long long r = idx / HW;
-  const int c = (int)(r % C);
-  const long long b = r / C;
-  out[idx] = in[(b * HW + p) * C + c];
+  sync_to_nchw_body(in, out, total, HW, C);
 }
 
 // ------------------------------------------------------------------------------------------------ embedding
@@ -269,15 +210,6 @@ __global__ __launch_bounds__(256) void sync_curve_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-constexpr long long kMaxBytes = 1ll << 31;   // no operand of one launch reaches 2 GiB
-
-int grid_for(long long items, int per_block, unsigned* grid) {
-  const long long g = (items + per_block - 1) / per_block;
-  CASYNC_REQUIRE(g >= 1 && g < (1ll << 31), "sync: grid of %lld blocks", g);
-  *grid = (unsigned)g;
-  return CASYNC_OK;
-}
-
 int launch_sync_stem7(const float* x, const float* w, const float* bias, float* out, int batch, int H, int W, hipStream_t s) {
   CASYNC_REQUIRE(x && w && bias && out, "sync stem7: null pointer");
   CASYNC_REQUIRE(batch > 0 && H >= 1 && W >= 1 && H <= 8192 && W <= 8192, "sync stem7: B=%d %dx%d", batch, H, W);
@@ -285,7 +217,7 @@ int launch_sync_stem7(const float* x, const float* w, const float* bias, float* 
   CASYNC_REQUIRE((long long)batch * H * W * S7_C * 4 < kMaxBytes, "sync stem7: output of 2 GiB or more");
   const int tiles_x = (W + S7_T - 1) / S7_T, tiles_y = (H + S7_T - 1) / S7_T;
   unsigned grid;
-  if (int st = grid_for((long long)batch * tiles_x * tiles_y, 1, &grid)) return st;
+  if (int st = grid_for("sync", (long long)batch * tiles_x * tiles_y, 1, &grid)) return st;
   return casync_launch(sync_stem7_kernel, dim3(grid), dim3(256), 0, s, x, w, bias, out, H, W, tiles_x, tiles_y);
 }
 
@@ -305,7 +237,7 @@ int launch_sync_conv(int ks, const float* in, const float* w, const float* bias,
   const long long M = (long long)batch * Ho * Wo;
   CASYNC_REQUIRE((long long)batch * H * W * cin * 4 < kMaxBytes && M * cout * 4 < kMaxBytes, "sync conv: an operand of 2 GiB or more");
   unsigned grid;
-  if (int st = grid_for(M, CV_BM, &grid)) return st;
+  if (int st = grid_for("sync", M, CV_BM, &grid)) return st;
   const dim3 g(grid, (unsigned)(cout / CV_BN));
   if (ks == 5) return casync_launch(sync_conv_kernel<5>, g, dim3(256), 0, s, in, w, bias, res, out, M, H, W, Ho, Wo, cin, cout, sh, sw, pad);
   return casync_launch(sync_conv_kernel<3>, g, dim3(256), 0, s, in, w, bias, res, out, M, H, W, Ho, Wo, cin, cout, sh, sw, pad);
@@ -315,19 +247,16 @@ int launch_sync_relu(float* x, long long n, hipStream_t s) {
   CASYNC_REQUIRE(x && n > 0 && n % 4 == 0 && (uintptr_t)x % 16 == 0, "sync relu: n=%lld (a multiple of 4, 16-B aligned)", n);
   CASYNC_REQUIRE(n * 4 < kMaxBytes, "sync relu: 2 GiB or more");
   unsigned grid;
-  if (int st = grid_for(n / 4, 256, &grid)) return st;
+  if (int st = grid_for("sync", n / 4, 256, &grid)) return st;
   return casync_launch(sync_relu_kernel, dim3(grid), dim3(256), 0, s, x, n / 4);
 }
 
-}  // namespace
-
-// (declared in syncnet_common.h: the bf16 pass of syncnet_bf16.hip calls these two)
 int launch_sync_to_nchw(const float* in, float* out, int batch, int hw, int c, hipStream_t s) {
   CASYNC_REQUIRE(in && out && batch > 0 && hw >= 1 && c >= 1, "sync to_nchw: B=%d hw=%d c=%d", batch, hw, c);
   const long long total = (long long)batch * hw * c;
   CASYNC_REQUIRE(total * 4 < kMaxBytes, "sync to_nchw: 2 GiB or more");
   unsigned grid;
-  if (int st = grid_for(total, 256, &grid)) return st;
+  if (int st = grid_for("sync", total, 256, &grid)) return st;
   return casync_launch(sync_to_nchw_kernel, dim3(grid), dim3(256), 0, s, in, out, total, hw, c);
 }
 
@@ -337,8 +266,6 @@ int launch_sync_embed(const float* in, float* out, int batch, hipStream_t s) {
   return casync_launch(sync_embed_kernel, dim3((unsigned)batch), dim3(256), 0, s, in, out);
 }
 
-namespace {
-
 int launch_sync_curve(const float* f, const float* a, int n, int d, int max_shift, float* sim, hipStream_t s) {
   CASYNC_REQUIRE(f && a && sim, "sync curve: null pointer");
   CASYNC_REQUIRE(n >= 1 && n <= (1 << 24) && d >= 4 && d % 4 == 0 && d <= (1 << 20) && max_shift >= 0 && max_shift <= 4096,
@@ -346,7 +273,7 @@ int launch_sync_curve(const float* f, const float* a, int n, int d, int max_shif
   CASYNC_REQUIRE((uintptr_t)f % 16 == 0 && (uintptr_t)a % 16 == 0 && (uintptr_t)sim % 4 == 0, "sync curve: alignment");
   const long long pairs = (long long)(2 * max_shift + 1) * n;
   unsigned grid;
-  if (int st = grid_for(pairs, 4, &grid)) return st;
+  if (int st = grid_for("sync", pairs, 4, &grid)) return st;
   return casync_launch(sync_curve_kernel, dim3(grid), dim3(256), 0, s, f, a, sim, pairs, n, d, max_shift);
 }
 
@@ -354,16 +281,27 @@ int launch_sync_curve(const float* f, const float* a, int n, int d, int max_shif
 // (the block table SyncNet, sync_net() and the handle: syncnet_common.h)
 constexpr int kFaceBlocks = kSyncFaceBlocks, kBlocks = kSyncBlocks, kFaceHW = kSyncFaceHW, kMaxPass = kSyncMaxPass;
 
-// the arena of one pass: two activations, each on a 256-B boundary
+// the arena of one pass: two activations of nb * act_floats values of T, each on a 256-B boundary.  In fp32 this is the rule in
+// floats it replaces, round64(n) * 4 == (4 n + 255) / 256 * 256, in bf16 the 128-element rounding, (n + 127) / 128 * 128 * 2 ==
+// (2 n + 255) / 256 * 256: the offsets and the totals are the same.
+template <class T>
 struct SyncWs {
-  float *a, *b;
+  T *a, *b;
   int64_t bytes;
   SyncWs(void* base, int nb, const SyncNet& N) {
-    const int64_t act = round64((int64_t)nb * N.act_floats);
-    a = static_cast<float*>(base), b = base ? a + act : nullptr;
-    bytes = 2 * act * 4;
+    const int64_t act = ((int64_t)nb * N.act_floats * (int64_t)sizeof(T) + 255) / 256 * 256;
+    a = static_cast<T*>(base), b = base ? a + act / (int64_t)sizeof(T) : nullptr;
+    bytes = 2 * act;
   }
 };
+
+// frames of one pass through the network, and the workspace of (mode, precision, batch): 0 for what no handle takes
+int sync_pass_frames(int batch) { return batch < kMaxPass ? batch : kMaxPass; }
+int64_t sync_ws_bytes(int mode, int precision, int batch) {
+  if (!sync_mode_ok(mode) || (precision != 0 && precision != 1) || batch < 1 || batch > 65536) return 0;
+  const int nb = sync_pass_frames(batch);
+  return precision == 1 ? SyncWs<bf16_t>(nullptr, nb, sync_net(mode)).bytes : SyncWs<float>(nullptr, nb, sync_net(mode)).bytes;
+}
 
 #define DT(call)                        \
   do {                                  \
@@ -372,31 +310,66 @@ struct SyncWs {
 
 constexpr int ST_FULL = kBlocks;   // both embeddings
 
-// Blocks first .. last of one encoder on nb frames; x is the encoder's NCHW input.  *res is the NHWC output of block `last`.
-int sync_blocks(const casync_sync* D, int first, int last, const float* x, int nb, const SyncWs& ws, const float** res, hipStream_t s) {
+// A precision of the handle: the element type of the activations, the dtype the audio window is converted to, the image the
+// conv / GEMM matrices are read from, the stem, one dense block (k 1, 3 or 5; f32: the block's output stays fp32) and how a tap
+// leaves.  What the network does is in sync_blocks and sync_pass.
+struct SyncF32 {
+  using T = float;
+  static constexpr int dtype = DT_F32;
+  static constexpr auto stem = launch_sync_stem7;
+  static const T* mats(const casync_sync* D) { return D->pw.w; }
+  static int block(const SyncBlock& b, const T* in, const T* wt, const float* bias, const T* res, T* dst, bool, int nb, int h, int wd,
+                   hipStream_t s) {
+    if (b.k > 1) return launch_sync_conv(b.k, in, wt, bias, res, dst, nb, h, wd, b.cin, b.cout, b.sh, b.sw, b.pad, s);
+    GemmEpilogue epi;   // the two 1x1 blocks: rows GEMM, ReLU pass
+    epi.bias = bias;
+    const int m = nb * h * wd;
+    DT(launch_rows_gemm(in, b.cin, wt, dst, b.cout, m, b.cout, b.cin, epi, s));
+    return launch_sync_relu(dst, (long long)m * b.cout, s);
+  }
+  static int tap_out(const void* src, bool, float* out, int nb, int hw, int c, hipStream_t s) {
+    return launch_sync_to_nchw(static_cast<const float*>(src), out, nb, hw, c, s);
+  }
+};
+
+// the contract: DESIGN section 8l; the last block of each encoder stores fp32, every other tap is widened
+struct SyncBF16 {
+  using T = bf16_t;
+  static constexpr int dtype = DT_BF16;
+  static constexpr auto stem = launch_sync16_stem7;
+  static const T* mats(const casync_sync* D) { return D->pw.w16; }
+  static int block(const SyncBlock& b, const T* in, const T* wt, const float* bias, const T* res, T* dst, bool f32, int nb, int h, int wd,
+                   hipStream_t s) {
+    return launch_sync16_conv(b.k, in, wt, bias, res, dst, f32, nb, h, wd, b.cin, b.cout, b.sh, b.sw, b.pad, s);
+  }
+  static int tap_out(const void* src, bool f32, float* out, int nb, int hw, int c, hipStream_t s) {
+    return f32 ? SyncF32::tap_out(src, f32, out, nb, hw, c, s) : launch_sync16_to_nchw(src, out, nb, hw, c, s);
+  }
+};
+
+bool sync_last_of_encoder(int i) { return i == kFaceBlocks - 1 || i == kBlocks - 1; }   // face.16, audio.13: fp32 out in both precisions
+
+// Blocks first .. last of one encoder on nb frames in the precision P; x is the encoder's fp32 NCHW input.  *res is the NHWC
+// output of block `last`: of P::T, or fp32 when that is the encoder's last block.
+template <class P>
+int sync_blocks(const casync_sync* D, int first, int last, const float* x, int nb, const SyncWs<typename P::T>& ws, const void** res,
+                hipStream_t s) {
+  using T = typename P::T;
   const SyncNet& N = sync_net(D->mode);
-  const float* w = D->pw.w;
-  const float* in = x;
-  float *dst = ws.a, *other = ws.b;
-  if (first != 0) {   // the audio window to NHWC; the stem reads NCHW itself
-    DT(launch_nchw_to_nhwc(x, ws.a, nb, N.audio_c, N.audio_h * N.audio_w, s));
+  const float* w = D->pw.w;   // biases and the stem's weights; wm: the image the matrices come from
+  const T* wm = P::mats(D);
+  const T* in = nullptr;
+  T *dst = ws.a, *other = ws.b;
+  if (first != 0) {   // the audio window to NHWC of T; the stem reads fp32 NCHW itself
+    DT(launch_nchw_to_nhwc(x, ws.a, nb, N.audio_c, N.audio_h * N.audio_w, s, P::dtype));
     in = ws.a, dst = ws.b, other = ws.a;
   }
   for (int i = first; i <= last; ++i) {
     const SyncBlock& b = N.blk[i];
     const int h = N.h_in[i], wd = N.w_in[i];
-    const float *wt = w + N.w_off[i], *bias = w + N.b_off[i];
-    if (b.k == 7) {
-      DT(launch_sync_stem7(in, wt, bias, dst, nb, h, wd, s));
-    } else if (b.k > 1) {   // the residual is added before the ReLU
-      DT(launch_sync_conv(b.k, in, wt, bias, b.res ? in : nullptr, dst, nb, h, wd, b.cin, b.cout, b.sh, b.sw, b.pad, s));
-    } else {
-      GemmEpilogue epi;
-      epi.bias = bias;
-      const int m = nb * h * wd;
-      DT(launch_rows_gemm(in, b.cin, wt, dst, b.cout, m, b.cout, b.cin, epi, s));
-      DT(launch_sync_relu(dst, (long long)m * b.cout, s));
-    }
+    const float* bias = w + N.b_off[i];
+    if (b.k == 7) DT(P::stem(x, w + N.w_off[i], bias, dst, nb, h, wd, s));
+    else DT(P::block(b, in, wm + N.w_off[i], bias, b.res ? in : nullptr, dst, sync_last_of_encoder(i), nb, h, wd, s));   // + x before the ReLU
     in = dst;
     std::swap(dst, other);
   }
@@ -404,20 +377,44 @@ int sync_blocks(const casync_sync* D, int first, int last, const float* x, int n
   return CASYNC_OK;
 }
 
-// One pass of nb frames; stage < kBlocks: that block's output in NCHW order to `out`; ST_FULL: the two embeddings.
-int sync_pass(const casync_sync* D, const float* face, const float* audio, int nb, const SyncWs& ws, int stage, float* out,
+// One pass of nb frames; stage < kBlocks: that block's output in fp32 NCHW order to `out`; ST_FULL: the two embeddings.
+template <class P>
+int sync_pass(const casync_sync* D, const float* face, const float* audio, int nb, const SyncWs<typename P::T>& ws, int stage, float* out,
               float* audio_emb, float* face_emb, hipStream_t s) {
   const SyncNet& N = sync_net(D->mode);
-  const float* res = nullptr;
+  const void* res = nullptr;
   if (stage < kBlocks) {
     const bool is_face = stage < kFaceBlocks;
-    DT(sync_blocks(D, is_face ? 0 : kFaceBlocks, stage, is_face ? face : audio, nb, ws, &res, s));
-    return launch_sync_to_nchw(res, out, nb, N.h_out[stage] * N.w_out[stage], N.blk[stage].cout, s);
+    DT(sync_blocks<P>(D, is_face ? 0 : kFaceBlocks, stage, is_face ? face : audio, nb, ws, &res, s));
+    return P::tap_out(res, sync_last_of_encoder(stage), out, nb, N.h_out[stage] * N.w_out[stage], N.blk[stage].cout, s);
   }
-  DT(sync_blocks(D, 0, kFaceBlocks - 1, face, nb, ws, &res, s));
-  DT(launch_sync_embed(res, face_emb, nb, s));
-  DT(sync_blocks(D, kFaceBlocks, kBlocks - 1, audio, nb, ws, &res, s));
-  return launch_sync_embed(res, audio_emb, nb, s);
+  DT(sync_blocks<P>(D, 0, kFaceBlocks - 1, face, nb, ws, &res, s));
+  DT(launch_sync_embed(static_cast<const float*>(res), face_emb, nb, s));
+  DT(sync_blocks<P>(D, kFaceBlocks, kBlocks - 1, audio, nb, ws, &res, s));
+  return launch_sync_embed(static_cast<const float*>(res), audio_emb, nb, s);
+}
+
+// the checked batch in passes of nb frames at the most, in the arena of the precision P
+template <class P>
+int sync_batches(casync_sync* D, const float* face, const float* audio, int batch, int nb, int stage, float* out, float* audio_emb,
+                 float* face_emb, void* ws_dev, hipStream_t s) {
+  const SyncNet& N = sync_net(D->mode);
+  const SyncWs<typename P::T> ws(ws_dev, nb, N);
+  DeviceGuard guard(D->device);
+  CASYNC_CHECK_HIP(guard.err);
+  std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
+  if (int st = casync_gate_enter(D->device, D, &D->ev_fwd, s, &gate_lock)) return st;
+  const int64_t face_frame = 3ll * kFaceHW * kFaceHW, audio_frame = (int64_t)N.audio_c * N.audio_h * N.audio_w;
+  const int64_t out_frame = stage < kBlocks ? N.out_floats(stage) : 0;
+  // every pass takes the tile choices of its own frame count; the kernels' sums do not depend on it (see the header comment)
+  for (int b0 = 0; b0 < batch; b0 += nb) {
+    const int n = batch - b0 < nb ? batch - b0 : nb;
+    const float *fp = face ? face + (size_t)b0 * face_frame : nullptr, *ap = audio ? audio + (size_t)b0 * audio_frame : nullptr;
+    float* op = out ? out + (size_t)b0 * out_frame : nullptr;
+    float *ae = audio_emb ? audio_emb + (size_t)b0 * EMB_D : nullptr, *fe = face_emb ? face_emb + (size_t)b0 * EMB_D : nullptr;
+    DT(sync_pass<P>(D, fp, ap, n, ws, stage, op, ae, fe, s));
+  }
+  return CASYNC_OK;
 }
 
 int sync_run(casync_sync* D, const float* face, const float* audio, int batch, int stage, float* out, float* audio_emb, float* face_emb,
@@ -433,32 +430,16 @@ int sync_run(casync_sync* D, const float* face, const float* audio, int batch, i
   CASYNC_REQUIRE((uintptr_t)face % 16 == 0 && (uintptr_t)audio % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)audio_emb % 16 == 0 &&
                      (uintptr_t)face_emb % 16 == 0 && (uintptr_t)ws_dev % 256 == 0,
                  "sync forward: alignment");
-  const SyncNet& N = sync_net(D->mode);
-  const int nb = batch < kMaxPass ? batch : kMaxPass;
-  const SyncWs ws(ws_dev, nb, N);
-  const bool bf16 = D->precision == 1;   // its pass (syncnet_bf16.hip) lays out its own, smaller arena
-  const int64_t need = bf16 ? sync16_ws_bytes(nb, N) : ws.bytes;
+  const bool bf16 = D->precision == 1;
+  const int64_t need = sync_ws_bytes(D->mode, D->precision, batch);
   if (ws_bytes < need) {
     casync_set_error("sync forward: workspace %lld bytes, needs %lld", (long long)ws_bytes, (long long)need);
     return CASYNC_ERR_STATE;
   }
   CASYNC_REQUIRE(!bf16 || D->pw.w16, "sync forward: bf16 weight image not made");
-  DeviceGuard guard(D->device);
-  CASYNC_CHECK_HIP(guard.err);
-  std::unique_lock<std::mutex> gate_lock;   // held until this forward is enqueued
-  if (int st = casync_gate_enter(D->device, D, &D->ev_fwd, s, &gate_lock)) return st;
-  const int64_t face_frame = 3ll * kFaceHW * kFaceHW, audio_frame = (int64_t)N.audio_c * N.audio_h * N.audio_w;
-  const int64_t out_frame = stage < kBlocks ? N.out_floats(stage) : 0;
-  // every pass takes the tile choices of its own frame count; the kernels' sums do not depend on it (see the header comment)
-  for (int b0 = 0; b0 < batch; b0 += nb) {
-    const int n = batch - b0 < nb ? batch - b0 : nb;
-    const float *fp = face ? face + (size_t)b0 * face_frame : nullptr, *ap = audio ? audio + (size_t)b0 * audio_frame : nullptr;
-    float* op = out ? out + (size_t)b0 * out_frame : nullptr;
-    float *ae = audio_emb ? audio_emb + (size_t)b0 * EMB_D : nullptr, *fe = face_emb ? face_emb + (size_t)b0 * EMB_D : nullptr;
-    if (bf16) DT(sync16_pass(D, fp, ap, n, ws_dev, stage, op, ae, fe, s));
-    else DT(sync_pass(D, fp, ap, n, ws, stage, op, ae, fe, s));
-  }
-  return CASYNC_OK;
+  const int nb = sync_pass_frames(batch);
+  return bf16 ? sync_batches<SyncBF16>(D, face, audio, batch, nb, stage, out, audio_emb, face_emb, ws_dev, s)
+              : sync_batches<SyncF32>(D, face, audio, batch, nb, stage, out, audio_emb, face_emb, ws_dev, s);
 }
 #undef DT
 }  // namespace
@@ -471,16 +452,8 @@ const char* casync_sync_packed_name(int mode, int i) { return sync_mode_ok(mode)
 int64_t casync_sync_packed_offset(int mode, int i) { return sync_mode_ok(mode) ? sync_net(mode).packed.offset(i) : -1; }
 int64_t casync_sync_packed_size(int mode, int i) { return sync_mode_ok(mode) ? sync_net(mode).packed.size(i) : -1; }
 int64_t casync_sync_packed_total(int mode) { return sync_mode_ok(mode) ? sync_net(mode).packed.total : 0; }
-int64_t casync_sync_workspace_bytes(int mode, int batch) {
-  if (!sync_mode_ok(mode) || batch < 1 || batch > 65536) return 0;
-  return SyncWs(nullptr, batch < kMaxPass ? batch : kMaxPass, sync_net(mode)).bytes;
-}
-
-int64_t casync_syncnet_workspace_bytes_ex(int mode, int precision, int batch) {
-  if (precision == 0) return casync_sync_workspace_bytes(mode, batch);
-  if (precision != 1 || !sync_mode_ok(mode) || batch < 1 || batch > 65536) return 0;
-  return sync16_ws_bytes(batch < kMaxPass ? batch : kMaxPass, sync_net(mode));
-}
+int64_t casync_sync_workspace_bytes(int mode, int batch) { return sync_ws_bytes(mode, 0, batch); }
+int64_t casync_syncnet_workspace_bytes_ex(int mode, int precision, int batch) { return sync_ws_bytes(mode, precision, batch); }
 
 int casync_syncnet_create_ex(int device_id, int mode, int precision, casync_sync_handle* out) {
   CASYNC_REQUIRE(out, "sync_create: null out");

@@ -1,8 +1,9 @@
-// The bf16 precision of the SyncNet_color handle (syncnet.hip is the fp32 one; syncnet_common.h what they share).  Activations
-// are bf16 NHWC, every conv weight but face.0's is read from the handle's bf16 image of the packed buffer, biases stay fp32.
+// The kernels of the bf16 precision of the SyncNet_color handle and their launchers.  The network's walk is sync_pass<SyncBF16> of
+// syncnet.hip, which holds the fp32 kernels; syncnet_common.h is what the two share.  Activations are bf16 NHWC, every conv
+// weight but face.0's is read from the handle's bf16 image of the packed buffer, biases stay fp32.
 //
-//   sync16_stem7_kernel       face.0: sync_stem7_kernel's arithmetic (fp32 weights on the fp32 NCHW input, the same fma order),
-//                             one rounding to bf16 on the store.
+//   sync16_stem7_kernel       face.0: sync_stem7_kernel's body (fp32 weights on the fp32 NCHW input, the same fma order), one
+//                             rounding to bf16 on the store.
 //   sync16_conv_kernel<KS,BN> every other block, KS 1, 3 or 5: relu(conv + bias (+ x)) as an implicit GEMM on
 //                             v_mfma_f32_16x16x32_bf16, fp32 accumulation; the residual (bf16, widened) is added in fp32 before the
 //                             ReLU; one rounding to bf16 on the store, or an fp32 store (the last block of each encoder).
@@ -21,71 +22,12 @@
 
 namespace {
 
-__device__ __forceinline__ float relu(float v) { return v > 0.f ? v : 0.f; }
-
 // ------------------------------------------------------------------------------------------------ stem (7x7)
-constexpr int S7_T = 16;            // output tile
-constexpr int S7_IN = S7_T + 6;     // with the halo
-constexpr int S7_LD = S7_IN + 1;    // LDS row stride (odd)
-constexpr int S7_C = 32, S7_K = 147;
-
-// x [B,3,H,W] fp32, w [(ky,kx,ci)=147][32] fp32, out [B,H,W,32] bf16; one thread per output pixel of the tile, all 32 channels
+// sync_stem7_body (syncnet_common.h) with the bf16 store
 __global__ __launch_bounds__(256) void sync16_stem7_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ bias, bf16_t* __restrict__ out, int H, int W,
                                                            int tiles_x, int tiles_y) {
-  __shared__ float xs[3][S7_IN][S7_LD];
-  __shared__ __attribute__((aligned(16))) float ws[S7_K * S7_C];
-  const int tid = threadIdx.x;
-  long long t = blockIdx.x;
-  const int tx = (int)(t % tiles_x);
-  t /= tiles_x;
-  const int ty = (int)(t % tiles_y);
-  const long long b = t / tiles_y;
-  const int x0 = tx * S7_T, y0 = ty * S7_T;
-  for (int i = tid; i < S7_K * S7_C / 4; i += 256) reinterpret_cast<f32x4*>(ws)[i] = reinterpret_cast<const f32x4*>(w)[i];
-  for (int i = tid; i < 3 * S7_IN * S7_IN; i += 256) {
-    const int ci = i / (S7_IN * S7_IN), r = i - ci * (S7_IN * S7_IN), ly = r / S7_IN, lx = r - ly * S7_IN;
-    const int iy = y0 + ly - 3, ix = x0 + lx - 3;
-    float v = 0.f;
-    if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = x[((b * 3 + ci) * H + iy) * (long long)W + ix];
-    xs[ci][ly][lx] = v;
-  }
-  __syncthreads();
-  const int px = tid & (S7_T - 1), py = tid / S7_T;
-  float acc[S7_C];
-#pragma unroll
-  for (int c = 0; c < S7_C; ++c) acc[c] = bias[c];
-#pragma unroll 1
-  for (int ky = 0; ky < 7; ++ky) {
-#pragma unroll 1
-    for (int kx = 0; kx < 7; ++kx) {
-#pragma unroll
-      for (int ci = 0; ci < 3; ++ci) {
-        const float in = xs[ci][py + ky][px + kx];
-        const float* wr = ws + ((ky * 7 + kx) * 3 + ci) * S7_C;
-#pragma unroll
-        for (int c4 = 0; c4 < S7_C / 4; ++c4) {
-          const f32x4 wv = *reinterpret_cast<const f32x4*>(wr + c4 * 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {   // the result pinned: no packed FMA around a scalar from the high half of a register pair
-            float a = fmaf(wv[e], in, acc[c4 * 4 + e]);   // (ir_common.h fma4_scalar)
-            asm("" : "+v"(a));
-            acc[c4 * 4 + e] = a;
-          }
-        }
-      }
-    }
-  }
-  const int oy = y0 + py, ox = x0 + px;
-  if (oy >= H || ox >= W) return;
-  bf16_t* o = out + ((b * H + oy) * (long long)W + ox) * S7_C;
-#pragma unroll
-  for (int c8 = 0; c8 < S7_C / 8; ++c8) {
-    bf16x8 v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (bf16_t)relu(acc[c8 * 8 + e]);
-    *reinterpret_cast<bf16x8*>(o + c8 * 8) = v;
-  }
+  sync_stem7_body(x, w, bias, out, H, W, tiles_x, tiles_y);
 }
 
 // ------------------------------------------------------------------------------------------------ dense KS x KS conv
@@ -226,30 +168,15 @@ __global__ __launch_bounds__(256) void sync16_conv_kernel(const bf16_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ bf16 NHWC -> fp32 NCHW
-// in [B,HW,C] bf16 -> out [B,C,HW] fp32 (a debug tap: one element per lane)
+// in [B,HW,C] bf16 -> out [B,C,HW] fp32: sync_to_nchw_body (syncnet_common.h) on bf16
 __global__ __launch_bounds__(256) void sync16_to_nchw_kernel(const bf16_t* __restrict__ in, float* __restrict__ out, long long total, int HW,
                                                              int C) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int p = (int)(idx % HW);
-  const long long r = idx / HW;
-  const int c = (int)(r % C);
-  const long long b = r / C;
-  out[idx] = (float)in[(b * HW + p) * C + c];
-}
-
-// ------------------------------------------------------------------------------------------------ launchers
-constexpr long long kMaxBytes = 1ll << 31;   // no operand of one launch reaches 2 GiB
-
-int grid_for(long long items, int per_block, unsigned* grid) {
-  const long long g = (items + per_block - 1) / per_block;
-  CASYNC_REQUIRE(g >= 1 && g < (1ll << 31), "sync16: grid of %lld blocks", g);
-  *grid = (unsigned)g;
-  return CASYNC_OK;
+  sync_to_nchw_body(in, out, total, HW, C);
 }
 
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------ launchers
 int launch_sync16_stem7(const float* x, const float* w, const float* bias, void* out, int batch, int H, int W, hipStream_t s) {
   CASYNC_REQUIRE(x && w && bias && out, "sync16 stem7: null pointer");
   CASYNC_REQUIRE(batch > 0 && H >= 1 && W >= 1 && H <= 8192 && W <= 8192, "sync16 stem7: B=%d %dx%d", batch, H, W);
@@ -257,7 +184,7 @@ int launch_sync16_stem7(const float* x, const float* w, const float* bias, void*
   CASYNC_REQUIRE((long long)batch * H * W * S7_C * 2 < kMaxBytes, "sync16 stem7: output of 2 GiB or more");
   const int tiles_x = (W + S7_T - 1) / S7_T, tiles_y = (H + S7_T - 1) / S7_T;
   unsigned grid;
-  if (int st = grid_for((long long)batch * tiles_x * tiles_y, 1, &grid)) return st;
+  if (int st = grid_for("sync16", (long long)batch * tiles_x * tiles_y, 1, &grid)) return st;
   return casync_launch(sync16_stem7_kernel, dim3(grid), dim3(256), 0, s, x, w, bias, static_cast<bf16_t*>(out), H, W, tiles_x, tiles_y);
 }
 
@@ -280,7 +207,7 @@ int launch_sync16_conv(int ks, const void* in, const void* w, const float* bias,
   CASYNC_REQUIRE((long long)batch * H * W * cin * 2 < kMaxBytes && M * cout * 4 < kMaxBytes && (long long)cout * ks * ks * cin * 2 < kMaxBytes,
                  "sync16 conv: an operand of 2 GiB or more");
   unsigned grid;
-  if (int st = grid_for(M, C16_BM, &grid)) return st;
+  if (int st = grid_for("sync16", M, C16_BM, &grid)) return st;
   const bf16_t *i16 = static_cast<const bf16_t*>(in), *w16 = static_cast<const bf16_t*>(w), *r16 = static_cast<const bf16_t*>(res);
   const int f32 = out_f32 ? 1 : 0;
   const dim3 wide(grid, (unsigned)(cout / 64)), narrow(grid, (unsigned)(cout / 16));
@@ -299,70 +226,9 @@ int launch_sync16_to_nchw(const void* in, float* out, int batch, int hw, int c, 
   const long long total = (long long)batch * hw * c;
   CASYNC_REQUIRE(total * 4 < kMaxBytes, "sync16 to_nchw: 2 GiB or more");
   unsigned grid;
-  if (int st = grid_for(total, 256, &grid)) return st;
+  if (int st = grid_for("sync16", total, 256, &grid)) return st;
   return casync_launch(sync16_to_nchw_kernel, dim3(grid), dim3(256), 0, s, static_cast<const bf16_t*>(in), out, total, hw, c);
 }
-
-// ------------------------------------------------------------------------------------------------ one pass of the network
-namespace {
-#define DT(call)                        \
-  do {                                  \
-    if (int st__ = (call)) return st__; \
-  } while (0)
-
-// elements of one of the two activations of the arena: a 256-B multiple of bf16
-int64_t act16(int nb, const SyncNet& N) { return ((int64_t)nb * N.act_floats + 127) / 128 * 128; }
-
-// Blocks first .. last of one encoder on nb frames; x is the encoder's fp32 NCHW input.  *res is the NHWC output of block `last`:
-// bf16, or fp32 when that is the encoder's last block.
-int sync16_blocks(const casync_sync* D, int first, int last, const float* x, int nb, bf16_t* a, bf16_t* b, const void** res, hipStream_t s) {
-  const SyncNet& N = sync_net(D->mode);
-  const void* in = x;
-  bf16_t *dst = a, *other = b;
-  if (first != 0) {   // the audio window to bf16 NHWC; the stem reads fp32 NCHW itself
-    DT(launch_nchw_to_nhwc(x, a, nb, N.audio_c, N.audio_h * N.audio_w, s, DT_BF16));
-    in = a, dst = b, other = a;
-  }
-  for (int i = first; i <= last; ++i) {
-    const SyncBlock& k = N.blk[i];
-    const float* bias = D->pw.w + N.b_off[i];
-    if (k.k == 7) {
-      DT(launch_sync16_stem7(x, D->pw.w + N.w_off[i], bias, dst, nb, N.h_in[i], N.w_in[i], s));
-    } else {   // the residual is added before the ReLU; the last block of an encoder keeps its fp32 sum
-      const bool f32 = i == kSyncFaceBlocks - 1 || i == kSyncBlocks - 1;
-      DT(launch_sync16_conv(k.k, in, D->pw.w16 + N.w_off[i], bias, k.res ? in : nullptr, dst, f32, nb, N.h_in[i], N.w_in[i], k.cin, k.cout,
-                            k.sh, k.sw, k.pad, s));
-    }
-    in = dst;
-    std::swap(dst, other);
-  }
-  *res = in;
-  return CASYNC_OK;
-}
-}  // namespace
-
-int64_t sync16_ws_bytes(int nb, const SyncNet& N) { return 2 * act16(nb, N) * 2; }
-
-// stage < kSyncBlocks: that block's output in fp32 NCHW order to `out`; kSyncBlocks: the two embeddings
-int sync16_pass(const casync_sync* D, const float* face, const float* audio, int nb, void* ws, int stage, float* out, float* audio_emb,
-                float* face_emb, hipStream_t s) {
-  const SyncNet& N = sync_net(D->mode);
-  bf16_t* a = static_cast<bf16_t*>(ws);
-  bf16_t* b = a + act16(nb, N);
-  const void* res = nullptr;
-  if (stage < kSyncBlocks) {
-    const bool is_face = stage < kSyncFaceBlocks;
-    DT(sync16_blocks(D, is_face ? 0 : kSyncFaceBlocks, stage, is_face ? face : audio, nb, a, b, &res, s));
-    const int hw = N.h_out[stage] * N.w_out[stage], c = N.blk[stage].cout;
-    if (stage == kSyncFaceBlocks - 1 || stage == kSyncBlocks - 1) return launch_sync_to_nchw(static_cast<const float*>(res), out, nb, hw, c, s);
-    return launch_sync16_to_nchw(res, out, nb, hw, c, s);
-  }
-  DT(sync16_blocks(D, 0, kSyncFaceBlocks - 1, face, nb, a, b, &res, s));
-  DT(launch_sync_embed(static_cast<const float*>(res), face_emb, nb, s));
-  DT(sync16_blocks(D, kSyncFaceBlocks, kSyncBlocks - 1, audio, nb, a, b, &res, s));
-  return launch_sync_embed(static_cast<const float*>(res), audio_emb, nb, s);
-}
-#undef DT
 
 // ---- C ABI: one entry per kernel (tests/kernel_ledger_sync16.py) ------------------------------------------------------
 extern "C" {

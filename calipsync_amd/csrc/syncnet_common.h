@@ -1,6 +1,7 @@
-// What the two precisions of the SyncNet_color handle share (syncnet.hip: fp32, syncnet_bf16.hip: bf16): the block table of the
-// network with its packed layout, the handle itself, and the launchers of syncnet.hip that the bf16 pass calls (their kernels
-// stay in lib/obj_sync; the bf16 object instantiates none of them).  Host code only.
+// What the two precisions of the SyncNet_color handle share (syncnet.hip: fp32 and the walk of both, syncnet_bf16.hip: the bf16
+// kernels): the block table of the network with its packed layout, the handle itself, the bf16 launchers the walk calls, and, in
+// the anonymous namespace, the device bodies of the stem and of the NHWC -> NCHW tap with what their launchers need.  The two
+// objects stay independent translation units: each has its own __global__ kernels, under its own names, around these bodies.
 #pragma once
 
 #include <string>
@@ -71,17 +72,110 @@ struct casync_sync {
   hipEvent_t ev_fwd = nullptr;   // forward gate slot
 };
 
-// ---- syncnet.hip (fp32 NHWC) ----
-int launch_sync_to_nchw(const float* in, float* out, int batch, int hw, int c, hipStream_t s);
-int launch_sync_embed(const float* in, float* out, int batch, hipStream_t s);
-
 // ---- syncnet_bf16.hip (pointers named void* are bf16, NHWC) ----
 int launch_sync16_stem7(const float* x, const float* w, const float* bias, void* out, int batch, int H, int W, hipStream_t s);
 // ks 1, 3 or 5 (tile: see the launcher); w [cout][(ky,kx,cin)] bf16; res (optional, bf16) [B Ho Wo][cout] is added before the ReLU; out bf16 or, out_f32, fp32
 int launch_sync16_conv(int ks, const void* in, const void* w, const float* bias, const void* res, void* out, bool out_f32, int batch, int H,
                        int W, int cin, int cout, int sh, int sw, int pad, hipStream_t s, int tile = 0);
 int launch_sync16_to_nchw(const void* in, float* out, int batch, int hw, int c, hipStream_t s);
-// the arena of one bf16 pass of nb frames, and the pass itself (arguments as sync_pass of syncnet.hip; ws 256-B aligned)
-int64_t sync16_ws_bytes(int nb, const SyncNet& N);
-int sync16_pass(const casync_sync* D, const float* face, const float* audio, int nb, void* ws, int stage, float* out, float* audio_emb,
-                float* face_emb, hipStream_t s);
+
+namespace {
+
+__device__ __forceinline__ float relu(float v) { return v > 0.f ? v : 0.f; }
+
+// ------------------------------------------------------------------------------------------------ stem (7x7)
+constexpr int S7_T = 16;            // output tile
+constexpr int S7_IN = S7_T + 6;     // with the halo
+constexpr int S7_LD = S7_IN + 1;    // LDS row stride (odd)
+constexpr int S7_C = 32, S7_K = 147;
+
+// x [B,3,H,W] fp32, w [(ky,kx,ci)=147][32] fp32, out [B,H,W,32] of TO (float: 16-byte stores; bf16_t: one rounding on the store);
+// one thread per output pixel of the tile, all 32 channels.  A workgroup of 256 threads, one tile each.
+template <class TO>
+__device__ __forceinline__ void sync_stem7_body(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                TO* __restrict__ out, int H, int W, int tiles_x, int tiles_y) {
+  __shared__ float xs[3][S7_IN][S7_LD];
+  __shared__ __attribute__((aligned(16))) float ws[S7_K * S7_C];
+  const int tid = threadIdx.x;
+  long long t = blockIdx.x;
+  const int tx = (int)(t % tiles_x);
+  t /= tiles_x;
+  const int ty = (int)(t % tiles_y);
+  const long long b = t / tiles_y;
+  const int x0 = tx * S7_T, y0 = ty * S7_T;
+  for (int i = tid; i < S7_K * S7_C / 4; i += 256) reinterpret_cast<f32x4*>(ws)[i] = reinterpret_cast<const f32x4*>(w)[i];
+  for (int i = tid; i < 3 * S7_IN * S7_IN; i += 256) {
+    const int ci = i / (S7_IN * S7_IN), r = i - ci * (S7_IN * S7_IN), ly = r / S7_IN, lx = r - ly * S7_IN;
+    const int iy = y0 + ly - 3, ix = x0 + lx - 3;
+    float v = 0.f;
+    if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = x[((b * 3 + ci) * H + iy) * (long long)W + ix];
+    xs[ci][ly][lx] = v;
+  }
+  __syncthreads();
+  const int px = tid & (S7_T - 1), py = tid / S7_T;
+  float acc[S7_C];
+#pragma unroll
+  for (int c = 0; c < S7_C; ++c) acc[c] = bias[c];
+#pragma unroll 1
+  for (int ky = 0; ky < 7; ++ky) {
+#pragma unroll 1
+    for (int kx = 0; kx < 7; ++kx) {
+#pragma unroll
+      for (int ci = 0; ci < 3; ++ci) {
+        const float in = xs[ci][py + ky][px + kx];
+        const float* wr = ws + ((ky * 7 + kx) * 3 + ci) * S7_C;
+#pragma unroll
+        for (int c4 = 0; c4 < S7_C / 4; ++c4) {
+          const f32x4 wv = *reinterpret_cast<const f32x4*>(wr + c4 * 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {   // the result pinned: no packed FMA around a scalar from the high half of a register pair
+            float a = fmaf(wv[e], in, acc[c4 * 4 + e]);   // (ir_common.h fma4_scalar)
+            asm("" : "+v"(a));
+            acc[c4 * 4 + e] = a;
+          }
+        }
+      }
+    }
+  }
+  const int oy = y0 + py, ox = x0 + px;
+  if (oy >= H || ox >= W) return;
+  TO* o = out + ((b * H + oy) * (long long)W + ox) * S7_C;
+  if constexpr (sizeof(TO) == 4) {
+#pragma unroll
+    for (int c4 = 0; c4 < S7_C / 4; ++c4)
+      *reinterpret_cast<f32x4*>(o + c4 * 4) = f32x4{relu(acc[c4 * 4]), relu(acc[c4 * 4 + 1]), relu(acc[c4 * 4 + 2]), relu(acc[c4 * 4 + 3])};
+  } else {
+#pragma unroll
+    for (int c8 = 0; c8 < S7_C / 8; ++c8) {
+      bf16x8 v;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (bf16_t)relu(acc[c8 * 8 + e]);
+      *reinterpret_cast<bf16x8*>(o + c8 * 8) = v;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ NHWC -> NCHW
+// in [B,HW,C] of TI -> out [B,C,HW] fp32 (a debug tap: one element per lane)
+template <class TI>
+__device__ __forceinline__ void sync_to_nchw_body(const TI* __restrict__ in, float* __restrict__ out, long long total, int HW, int C) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int p = (int)(idx % HW);
+  const long long r = idx / HW;
+  const int c = (int)(r % C);
+  const long long b = r / C;
+  out[idx] = (float)in[(b * HW + p) * C + c];
+}
+
+// ------------------------------------------------------------------------------------------------ for the launchers
+constexpr long long kMaxBytes = 1ll << 31;   // no operand of one launch reaches 2 GiB
+
+int grid_for(const char* who, long long items, int per_block, unsigned* grid) {   // who: "sync" or "sync16"
+  const long long g = (items + per_block - 1) / per_block;
+  CASYNC_REQUIRE(g >= 1 && g < (1ll << 31), "%s: grid of %lld blocks", who, g);
+  *grid = (unsigned)g;
+  return CASYNC_OK;
+}
+
+}  // namespace

@@ -13,14 +13,17 @@ GPU at import.
 """
 from __future__ import annotations
 
+from typing import Callable, NamedTuple
+
 from kernel_ledger import (C, _abs, _dev, _done, _gen, _lib, _ok, _p, _rel, _Run, _s, _t)
 from kernel_ledger_lmk import _bar4
 
 
-def _rows(n_rows, width, d):
+def _rows(n_rows, width, d, dtype="float32"):
     """a sentinel-filled [n_rows + 2, width] buffer and the pointer of its row 1"""
-    buf = _t().full((n_rows + 2, width), -7.0, device=d)
-    return buf, buf.data_ptr() + width * 4
+    torch = _t()
+    buf = torch.full((n_rows + 2, width), -7.0, device=d, dtype=getattr(torch, dtype))
+    return buf, buf.data_ptr() + width * buf.element_size()
 
 
 def _guards(buf):
@@ -28,12 +31,22 @@ def _guards(buf):
     return 0.0 if bool((buf[0] == -7.0).all() and (buf[-1] == -7.0).all()) else float("inf")
 
 
+class Precision(NamedTuple):
+    """what differs between the fp32 and the bf16 instance of a kernel body both objects compile (csrc/syncnet_common.h)"""
+    tag: str              # "sync" | "sync16": the entry casync_op_<tag>_*, the seed's name and the printed line
+    dtype: str            # torch's name of the type the stem stores and to_nchw reads
+    stem_bar: Callable    # (the stem's output rows, the float64 reference) -> (err, bar)
+
+
+F32 = Precision("sync", "float32", lambda out, ref: (_rel(out, ref), 3e-6))
+
+
 # ------------------------------------------------------------------ stem (7x7, pad 3, 3 -> 32, ReLU)
-def stem7(b, h, w):
-    """casync_op_sync_stem7 on an h x w float NCHW input vs float64"""
+def stem7_of(P, b, h, w):
+    """casync_op_<tag>_stem7 on an h x w float NCHW input vs float64"""
     torch = _t()
     F = torch.nn.functional
-    g = _gen("sync_stem7", b, h, w)
+    g = _gen(f"{P.tag}_stem7", b, h, w)
     d = _dev()
     x = torch.rand(b, 3, h, w, generator=g)
     wt = torch.randn(32, 3, 7, 7, generator=g) / 147 ** 0.5
@@ -41,10 +54,15 @@ def stem7(b, h, w):
     ref = F.relu(F.conv2d(x.double(), wt.double(), bias.double(), 1, 3)).permute(0, 2, 3, 1).reshape(-1, 32)
     wp = wt.permute(2, 3, 1, 0).reshape(147, 32).contiguous().to(d)
     xd, bd = x.to(d), bias.to(d)
-    out, ptr = _rows(b * h * w, 32, d)
+    out, ptr = _rows(b * h * w, 32, d, P.dtype)
     with _Run(0) as r:
-        _ok(_lib().casync_op_sync_stem7(_p(xd), _p(wp), _p(bd), ptr, b, h, w, _s()), "sync_stem7")
-    return _done(r, max(_rel(out[1:-1], ref), _guards(out)), 3e-6, f"sync stem7 {b}x{h}x{w}")
+        _ok(getattr(_lib(), f"casync_op_{P.tag}_stem7")(_p(xd), _p(wp), _p(bd), ptr, b, h, w, _s()), f"{P.tag}_stem7")
+    err, bar = P.stem_bar(out[1:-1], ref)
+    return _done(r, max(err, _guards(out)), bar, f"{P.tag} stem7 {b}x{h}x{w}")
+
+
+def stem7(b, h, w):
+    return stem7_of(F32, b, h, w)
 
 
 # ------------------------------------------------------------------ 5x5, stride 2, pad 1, 32 -> 64, ReLU
@@ -106,18 +124,22 @@ def relu(n):
     return _done(r, 0.0 if ok else float("inf"), 0.0, f"sync relu n={n}")
 
 
-# ------------------------------------------------------------------ NHWC -> NCHW
-def to_nchw(b, hw, c):
+# ------------------------------------------------------------------ NHWC -> NCHW (fp32 out)
+def to_nchw_of(P, b, hw, c):
     torch = _t()
-    g = _gen("sync_to_nchw", b, hw, c)
+    g = _gen(f"{P.tag}_to_nchw", b, hw, c)
     d = _dev()
-    x = torch.randn(b, hw, c, generator=g)
+    x = torch.randn(b, hw, c, generator=g).to(getattr(torch, P.dtype))
     xd = x.to(d)
     out, ptr = _rows(b * c, hw, d)
     with _Run(0) as r:
-        _ok(_lib().casync_op_sync_to_nchw(_p(xd), ptr, b, hw, c, _s()), "sync_to_nchw")
-    ok = bool(torch.equal(out[1:-1].cpu(), x.permute(0, 2, 1).reshape(b * c, hw))) and _guards(out) == 0.0
-    return _done(r, 0.0 if ok else float("inf"), 0.0, f"sync to_nchw {b}x{hw}x{c}")
+        _ok(getattr(_lib(), f"casync_op_{P.tag}_to_nchw")(_p(xd), ptr, b, hw, c, _s()), f"{P.tag}_to_nchw")
+    ok = bool(torch.equal(out[1:-1].cpu(), x.float().permute(0, 2, 1).reshape(b * c, hw))) and _guards(out) == 0.0
+    return _done(r, 0.0 if ok else float("inf"), 0.0, f"{P.tag} to_nchw {b}x{hw}x{c}")
+
+
+def to_nchw(b, hw, c):
+    return to_nchw_of(F32, b, hw, c)
 
 
 # ------------------------------------------------------------------ embedding

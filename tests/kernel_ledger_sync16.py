@@ -17,14 +17,7 @@ Every output goes into a buffer between sentinel rows.  Nothing here touches a G
 from __future__ import annotations
 
 from kernel_ledger import (C, _dev, _done, _gen, _lib, _ok, _p, _Run, _s, _t)
-from kernel_ledger_sync import _guards, _rows
-
-
-def _rows16(n_rows, width, d):
-    """a sentinel-filled bf16 [n_rows + 2, width] buffer and the pointer of its row 1"""
-    torch = _t()
-    buf = torch.full((n_rows + 2, width), -7.0, device=d, dtype=torch.bfloat16)
-    return buf, buf.data_ptr() + width * 2
+from kernel_ledger_sync import Precision, _guards, _rows, stem7_of, to_nchw_of
 
 
 def _ratio(got, ref, tol):
@@ -36,24 +29,20 @@ def _ratio(got, ref, tol):
     return float(((got - ref).abs() / (tol + 1e-300)).max())
 
 
-# ------------------------------------------------------------------ stem (7x7, pad 3, 3 -> 32, ReLU, bf16 store)
+# ------------------------------------------------------------------ stem and to_nchw: kernel_ledger_sync's bodies in bf16
+def _stem_bar(out, ref):
+    return _ratio(out, ref, ref.abs() * 2.0 ** -8 + 3e-6 * float(ref.abs().max())), 1.0
+
+
+BF16 = Precision("sync16", "bfloat16", _stem_bar)
+
+
 def stem7(b, h, w):
-    """casync_op_sync16_stem7 on an h x w float NCHW input vs float64"""
-    torch = _t()
-    F = torch.nn.functional
-    g = _gen("sync16_stem7", b, h, w)
-    d = _dev()
-    x = torch.rand(b, 3, h, w, generator=g)
-    wt = torch.randn(32, 3, 7, 7, generator=g) / 147 ** 0.5
-    bias = torch.randn(32, generator=g) * 0.3
-    ref = F.relu(F.conv2d(x.double(), wt.double(), bias.double(), 1, 3)).permute(0, 2, 3, 1).reshape(-1, 32)
-    tol = ref.abs() * 2.0 ** -8 + 3e-6 * float(ref.abs().max())
-    wp = wt.permute(2, 3, 1, 0).reshape(147, 32).contiguous().to(d)
-    xd, bd = x.to(d), bias.to(d)
-    out, ptr = _rows16(b * h * w, 32, d)
-    with _Run(0) as r:
-        _ok(_lib().casync_op_sync16_stem7(_p(xd), _p(wp), _p(bd), ptr, b, h, w, _s()), "sync16_stem7")
-    return _done(r, max(_ratio(out[1:-1], ref, tol), _guards(out)), 1.0, f"sync16 stem7 {b}x{h}x{w}")
+    return stem7_of(BF16, b, h, w)
+
+
+def to_nchw(b, hw, c):
+    return to_nchw_of(BF16, b, hw, c)
 
 
 # ------------------------------------------------------------------ KS x KS conv, any stride and pad, (+ x), ReLU
@@ -78,7 +67,7 @@ def conv(ks, tile, b, h, w, cin, cout, sh, sw, pad, res):
     xd = x.permute(0, 2, 3, 1).contiguous().to(d)
     wp = wt.permute(0, 2, 3, 1).reshape(cout, K).contiguous().to(d)
     bd, rd = bias.to(d), (r_.contiguous().to(d) if res else None)
-    out, ptr = _rows(ref.shape[0], cout, d) if f32_out else _rows16(ref.shape[0], cout, d)
+    out, ptr = _rows(ref.shape[0], cout, d, "float32" if f32_out else "bfloat16")
     lib = _lib()
     with _Run(0) as r:
         if ks == 1:
@@ -91,20 +80,6 @@ def conv(ks, tile, b, h, w, cin, cout, sh, sw, pad, res):
             _ok(lib.casync_op_sync16_conv3(_p(xd), _p(wp), _p(bd), _p(rd), ptr, b, h, w, cin, cout, sh, sw, pad, tile, _s()), "sync16_conv3")
     what = f"sync16 conv{ks} tile {tile} {b}x{h}x{w} {cin}->{cout} s({sh},{sw}) p{pad} res={res} M={ref.shape[0]} K={K}"
     return _done(r, max(_ratio(out[1:-1], ref, tol), _guards(out)), 1.0, what)
-
-
-# ------------------------------------------------------------------ bf16 NHWC -> fp32 NCHW
-def to_nchw(b, hw, c):
-    torch = _t()
-    g = _gen("sync16_to_nchw", b, hw, c)
-    d = _dev()
-    x = torch.randn(b, hw, c, generator=g).bfloat16()
-    xd = x.to(d)
-    out, ptr = _rows(b * c, hw, d)
-    with _Run(0) as r:
-        _ok(_lib().casync_op_sync16_to_nchw(_p(xd), ptr, b, hw, c, _s()), "sync16_to_nchw")
-    ok = bool(torch.equal(out[1:-1].cpu(), x.float().permute(0, 2, 1).reshape(b * c, hw))) and _guards(out) == 0.0
-    return _done(r, 0.0 if ok else float("inf"), 0.0, f"sync16 to_nchw {b}x{hw}x{c}")
 
 
 # ------------------------------------------------------------------ the ledger of lib/obj_sync16/
