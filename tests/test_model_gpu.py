@@ -521,6 +521,13 @@ def test_workspace_is_reused_across_batch_sizes(net):
     assert torch.equal(net(xt, at), big)
 
 
+def test_a_smaller_batch_in_the_reused_arena_is_exact():
+    """The same history held bit for bit (tests/workspace_contract.py): 4 frames in the arena a 9-frame forward on other frames has
+    just used give, output and every tap, what they give in a zeroed arena."""
+    import workspace_contract as wc
+    wc.check(wc.unet_9_then_4, "stale")
+
+
 def test_two_models_on_two_threads_share_the_stream_pool(net, net_bf16):
     """Round 6: the engine's lane / audio streams are ONE process-wide set per device that every handle borrows.  Two models
     (fp32: two lanes + audio streams; bf16: its three-lane plan) forwarding at the same time from two host threads, each on a
