@@ -271,7 +271,14 @@ _PROTOS = {
     "casync_op_audio_normalize": (C.c_int, [c_f32p, c_i64, C.c_void_p, c_f32p, C.c_void_p]),
 }
 
-EXPORTS = tuple(_PROTOS)
+# include/casync_train.h (additive to ABI 13, a header of its own); rec is HOST memory: [batch][12] int32 = {t, y0, x0, h, w, r, ry0,
+# rx0, rh, rw, 0, 0}
+_PROTOS_TRAIN = {
+    "casync_op_train_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, c_f32p, c_f32p, C.c_void_p]),
+}
+
+EXPORTS = tuple(_PROTOS)                 # what include/casync_hip.h declares
+EXPORTS_TRAIN = tuple(_PROTOS_TRAIN)     # what include/casync_train.h declares
 ABI_VERSION = 13         # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
 
 
@@ -303,7 +310,7 @@ def load() -> C.CDLL:
         except Exception as exc:
             raise RuntimeError(f"{path} is older than calipsync_amd/csrc and could not be rebuilt: {exc}") from exc
     lib = C.CDLL(path)
-    for name, (res, args) in _PROTOS.items():
+    for name, (res, args) in {**_PROTOS, **_PROTOS_TRAIN}.items():
         fn = getattr(lib, name)       # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
