@@ -277,8 +277,46 @@ _PROTOS_TRAIN = {
     "casync_op_train_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, c_f32p, c_f32p, C.c_void_p]),
 }
 
+# include/casync_ploss.h (additive to ABI 13, a header of its own): the trainer's loss, L1 + VGG19 perceptual, with its gradient.
+# partials are float64 on the device; grad_out_dev is a device scalar
+_PROTOS_PLOSS = {
+    "casync_ploss_packed_count": (C.c_int, []),
+    "casync_ploss_packed_name": (C.c_char_p, [C.c_int]),
+    "casync_ploss_packed_offset": (c_i64, [C.c_int]),
+    "casync_ploss_packed_size": (c_i64, [C.c_int]),
+    "casync_ploss_packed_total": (c_i64, []),
+    "casync_ploss_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "casync_ploss_destroy": (None, [C.c_void_p]),
+    "casync_ploss_load_weights_host": (C.c_int, [C.c_void_p, C.c_void_p, c_i64]),
+    "casync_ploss_load_weights_device": (C.c_int, [C.c_void_p, c_f32p, c_i64]),
+    "casync_ploss_saved_bytes": (c_i64, [C.c_int, C.c_int, C.c_int]),
+    "casync_ploss_scratch_bytes": (c_i64, [C.c_int, C.c_int, C.c_int]),
+    "casync_ploss_forward": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, C.c_void_p, c_i64,
+                                       C.c_void_p, c_i64, C.c_void_p]),
+    "casync_ploss_backward": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                        c_i64, C.c_void_p, c_i64, C.c_void_p]),
+    "casync_ploss_tap_floats": (c_i64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "casync_ploss_forward_tap": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p, c_i64, C.c_void_p]),
+    "casync_ploss_backward_tap": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, c_i64,
+                                            C.c_int, c_f32p, C.c_void_p, c_i64, C.c_void_p]),
+    "casync_op_ploss_stem": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_ploss_pool": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_ploss_weight_transform": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_ploss_split": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_int, C.c_void_p]),
+    "casync_op_ploss_combine": (C.c_int, [c_f32p, C.c_int, c_f32p, c_f32p, c_i64, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_ploss_relu_bwd": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_void_p]),
+    "casync_op_ploss_pool_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "casync_op_ploss_stem_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                           C.c_void_p]),
+    "casync_ploss_partials": (C.c_int, [c_i64]),
+    "casync_op_ploss_sqdiff": (C.c_int, [c_f32p, c_f32p, c_f32p, c_i64, C.c_void_p, C.c_void_p]),
+    "casync_op_ploss_absdiff": (C.c_int, [c_f32p, c_f32p, c_i64, C.c_void_p, C.c_void_p]),
+    "casync_op_ploss_finish": (C.c_int, [C.c_void_p, C.c_int, c_i64, C.c_void_p, C.c_int, c_i64, C.c_float, C.c_float, c_f32p, C.c_void_p]),
+}
+
 EXPORTS = tuple(_PROTOS)                 # what include/casync_hip.h declares
 EXPORTS_TRAIN = tuple(_PROTOS_TRAIN)     # what include/casync_train.h declares
+EXPORTS_PLOSS = tuple(_PROTOS_PLOSS)     # what include/casync_ploss.h declares
 ABI_VERSION = 13         # == CASYNC_ABI_VERSION of include/casync_hip.h this file was written against
 
 
@@ -310,7 +348,7 @@ def load() -> C.CDLL:
         except Exception as exc:
             raise RuntimeError(f"{path} is older than calipsync_amd/csrc and could not be rebuilt: {exc}") from exc
     lib = C.CDLL(path)
-    for name, (res, args) in {**_PROTOS, **_PROTOS_TRAIN}.items():
+    for name, (res, args) in {**_PROTOS, **_PROTOS_TRAIN, **_PROTOS_PLOSS}.items():
         fn = getattr(lib, name)       # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -374,6 +412,11 @@ def pfld_layout():
 def s3fd_layout():
     """The layout of the S3FD face-detector engine's packed buffer."""
     return _layout("s3fd_")
+
+
+def ploss_layout():
+    """The layout of the loss handle's packed buffer (include/casync_ploss.h)."""
+    return _layout("ploss_")
 
 
 def sync_layout(mode: str = "hubert"):

@@ -73,9 +73,14 @@ SOURCES_MJPEGDEC = ["jpeg_dec_mjpeg.hip"]
 # shares with frame_ops.hip is csrc/resize_u8.h (both entries of HEADERS).
 OBJ_DIR_TRAIN = os.path.join(LIB_DIR, "obj_train")
 SOURCES_TRAIN = ["train_ops.hip"]
-SOURCES = ["runtime.hip", "gemm.hip", "ops.hip", "ir_fused.hip", "pw_dw.hip", "pw_dw_bf16.hip", "attention.hip", "attention_bf16.hip", "frame_ops.hip", "hubert.hip", "engine.hip"] + SOURCES_DET + SOURCES_DET16 + SOURCES_FACE + SOURCES_NMS + SOURCES_CLIP + SOURCES_JPEG + SOURCES_JPEG420 + SOURCES_JPEGDEC + SOURCES_SYNC + SOURCES_SYNC16 + SOURCES_AUDIO + SOURCES_MJPEGDEC + SOURCES_TRAIN
+# The kernels of the trainer's loss, L1 + VGG19 perceptual with its gradient (tests/kernel_ledger_ploss.py is their ledger): a
+# seventeenth object directory, its source an entry of SOURCES in the same way.  Its entries are declared in
+# include/casync_ploss.h (an entry of HEADERS); its twelve convs run on launchers of lib/obj/ (no new instance there).
+OBJ_DIR_PLOSS = os.path.join(LIB_DIR, "obj_ploss")
+SOURCES_PLOSS = ["ploss.hip"]
+SOURCES = ["runtime.hip", "gemm.hip", "ops.hip", "ir_fused.hip", "pw_dw.hip", "pw_dw_bf16.hip", "attention.hip", "attention_bf16.hip", "frame_ops.hip", "hubert.hip", "engine.hip"] + SOURCES_DET + SOURCES_DET16 + SOURCES_FACE + SOURCES_NMS + SOURCES_CLIP + SOURCES_JPEG + SOURCES_JPEG420 + SOURCES_JPEGDEC + SOURCES_SYNC + SOURCES_SYNC16 + SOURCES_AUDIO + SOURCES_MJPEGDEC + SOURCES_TRAIN + SOURCES_PLOSS
 HEADERS = ["common.h", "handle.h", "ir_common.h", "pw_dw_common.h", "jpeg_enc_common.h", "syncnet_common.h", "jpeg_dec_common.h", "resize_u8.h", os.path.join("..", "..", "include", "casync_hip.h"),
-           os.path.join("..", "..", "include", "casync_train.h")]
+           os.path.join("..", "..", "include", "casync_train.h"), os.path.join("..", "..", "include", "casync_ploss.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 
 
@@ -174,6 +179,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ_DIR_AUDIO, exist_ok=True)
     os.makedirs(OBJ_DIR_MJPEGDEC, exist_ok=True)
     os.makedirs(OBJ_DIR_TRAIN, exist_ok=True)
+    os.makedirs(OBJ_DIR_PLOSS, exist_ok=True)
     # One builder at a time: bench.py --gpus N, torchrun ranks and pytest workers can all reach load() -> build() at
     # once after a checkout; without the lock they compile into the same obj/*.o and link over a library another rank
     # is dlopen-ing.  The link goes to a temporary name and is renamed into place (atomic on one filesystem).
@@ -196,7 +202,8 @@ def _build_locked(force: bool, verbose: bool) -> str:
             OBJ_DIR_DET16 if src in SOURCES_DET16 else OBJ_DIR_FACE if src in SOURCES_FACE else OBJ_DIR_NMS if src in SOURCES_NMS else \
             OBJ_DIR_CLIP if src in SOURCES_CLIP else OBJ_DIR_JPEG if src in SOURCES_JPEG else OBJ_DIR_JPEG420 if src in SOURCES_JPEG420 else \
             OBJ_DIR_JPEGDEC if src in SOURCES_JPEGDEC else OBJ_DIR_SYNC if src in SOURCES_SYNC else OBJ_DIR_SYNC16 if src in SOURCES_SYNC16 else \
-            OBJ_DIR_AUDIO if src in SOURCES_AUDIO else OBJ_DIR_MJPEGDEC if src in SOURCES_MJPEGDEC else OBJ_DIR_TRAIN if src in SOURCES_TRAIN else OBJ_DIR
+            OBJ_DIR_AUDIO if src in SOURCES_AUDIO else OBJ_DIR_MJPEGDEC if src in SOURCES_MJPEGDEC else OBJ_DIR_TRAIN if src in SOURCES_TRAIN else \
+            OBJ_DIR_PLOSS if src in SOURCES_PLOSS else OBJ_DIR
         obj = os.path.join(obj_dir, src.replace(".hip", ".o"))
         path = os.path.join(CSRC, src)
         if not force and not _newer(obj, [path] + _header_paths()):

@@ -296,3 +296,33 @@ def make_syncnet_inputs(batch: int, mode: str = "hubert", seed: int = SYNCNET_IN
         x[b] = uniform01(seed, 0x7000000 + b, x[b].size).astype(np.float32).reshape(x[b].shape)
         a[b] = normal01(seed, 0x8000000 + b, a[b].size).astype(np.float32).reshape(a[b].shape)
     return x, a
+
+
+# ---- the trainer's loss network (calipsync_amd/losses.py) ------------------------------------------------------------
+VGG19_WEIGHT_SEED = 0x1619
+VGG19_INPUT_SEED = 0x161A
+
+
+def make_vgg19_state_dict(seed: int = VGG19_WEIGHT_SEED) -> Dict[str, np.ndarray]:
+    """The fourteen entries of ``vgg19().features[:15]`` under the state dict's own names (features.{0,2,5,7,10,12,14}.{weight,
+    bias}): conv weights N(0, 2 / fan_in) -- the trunk is conv + ReLU throughout, so activations stay O(1) through the seven
+    convs on images in [0, 1] -- and biases N(0, 0.05^2)."""
+    from . import losses
+    sd: Dict[str, np.ndarray] = {}
+    for key, shape in losses.manifest():
+        n = int(np.prod(shape))
+        s = _stream("vgg19." + key)
+        v = normal01(seed, s, n) * (0.05 if key.endswith(".bias") else np.sqrt(2.0 / int(np.prod(shape[1:]))))
+        sd[key] = v.astype(np.float32).reshape(shape)
+    return sd
+
+
+def make_loss_inputs(batch: int, h: int = 160, w: int = 160, seed: int = VGG19_INPUT_SEED) -> Tuple[np.ndarray, np.ndarray]:
+    """(preds, labels) fp32 [B,3,h,w] in [0, 1] as the trainer hands them to its loss: a label of smooth blobs over noise and a
+    prediction that is the label plus a perturbation of a tenth of the range; image b depends only on (seed, b, h, w)."""
+    frames = make_s3fd_inputs(batch, h, w, seed).astype(np.float64) / 255.0
+    labels = np.ascontiguousarray(frames.transpose(0, 3, 1, 2))
+    preds = np.empty_like(labels)
+    for b in range(batch):
+        preds[b] = labels[b] + 0.1 * (uniform01(seed, 0x7000000 + b, 3 * h * w).reshape(3, h, w) - 0.5)
+    return np.clip(preds, 0.0, 1.0).astype(np.float32), labels.astype(np.float32)
