@@ -33,6 +33,7 @@ namespace {
 // ------------------------------------------------------------------ architecture table
 struct IR {  // inverted residual: PW expand -> DW3x3 -> PW project (module/unet.py:8-40)
   const char* prefix;
+  int id;         // its weights: UNetLayout::ir[id] (the two audio encoders' conv1 / conv2 share a slot: a layout holds one of them)
   int cin, cout, stride, res, hw_in;
   int w_in = 0;   // frame width when it differs from the height (AudioConvWenet's 16x32 blocks, stride 1 only); 0 = square
   int cexp() const { return cin * 2; }
@@ -42,106 +43,126 @@ struct IR {  // inverted residual: PW expand -> DW3x3 -> PW project (module/unet
   int wd_out() const { return stride == 1 ? wd() : (wd() + 2 - 3) / 2 + 1; }
 };
 
-const IR kInc = {"inc.inconv.0", 6, 32, 1, 0, 160};
 const IR kDown[4][2] = {
-    {{"down1.maxpool_conv.0.double_conv.0", 32, 64, 2, 0, 160}, {"down1.maxpool_conv.0.double_conv.1", 64, 64, 1, 1, 80}},
-    {{"down2.maxpool_conv.0.double_conv.0", 64, 128, 2, 0, 80}, {"down2.maxpool_conv.0.double_conv.1", 128, 128, 1, 1, 40}},
-    {{"down3.maxpool_conv.0.double_conv.0", 128, 256, 2, 0, 40}, {"down3.maxpool_conv.0.double_conv.1", 256, 256, 1, 1, 20}},
-    {{"down4.maxpool_conv.0.double_conv.0", 256, 512, 2, 0, 20}, {"down4.maxpool_conv.0.double_conv.1", 512, 512, 1, 1, 10}}};
-const IR kAudio[5] = {{"audio_model.conv1", 32, 64, 1, 0, 32},
-                      {"audio_model.conv2", 64, 128, 1, 0, 32},
-                      {"audio_model.conv4", 256, 256, 1, 1, 16},
-                      {"audio_model.conv6", 512, 512, 1, 1, 10},
-                      {"audio_model.conv7", 512, 512, 1, 1, 10}};
+    {{"down1.maxpool_conv.0.double_conv.0", 0, 32, 64, 2, 0, 160}, {"down1.maxpool_conv.0.double_conv.1", 1, 64, 64, 1, 1, 80}},
+    {{"down2.maxpool_conv.0.double_conv.0", 2, 64, 128, 2, 0, 80}, {"down2.maxpool_conv.0.double_conv.1", 3, 128, 128, 1, 1, 40}},
+    {{"down3.maxpool_conv.0.double_conv.0", 4, 128, 256, 2, 0, 40}, {"down3.maxpool_conv.0.double_conv.1", 5, 256, 256, 1, 1, 20}},
+    {{"down4.maxpool_conv.0.double_conv.0", 6, 256, 512, 2, 0, 20}, {"down4.maxpool_conv.0.double_conv.1", 7, 512, 512, 1, 1, 10}}};
+const IR kAudio[5] = {{"audio_model.conv1", 8, 32, 64, 1, 0, 32},
+                      {"audio_model.conv2", 9, 64, 128, 1, 0, 32},
+                      {"audio_model.conv4", 10, 256, 256, 1, 1, 16},
+                      {"audio_model.conv6", 11, 512, 512, 1, 1, 10},
+                      {"audio_model.conv7", 12, 512, 512, 1, 1, 10}};
 // AudioConvWenet (module/unet.py:109-144): conv1 / conv2 are 256 -> 512 -> 256 residual blocks on 16x32 frames; conv4, conv6
 // and conv7 are the HuBERT encoder's blocks of the same names (kAudio[2..4])
-const IR kAudioW[2] = {{"audio_model.conv1", 256, 256, 1, 1, 16, 32}, {"audio_model.conv2", 256, 256, 1, 1, 16, 32}};
+const IR kAudioW[2] = {{"audio_model.conv1", 8, 256, 256, 1, 1, 16, 32}, {"audio_model.conv2", 9, 256, 256, 1, 1, 16, 32}};
 // per-frame floats of the NCHW audio window at the boundary
 inline int64_t audio_frame_floats(int mode) { return mode == CASYNC_AUDIO_WENET ? 256ll * 16 * 32 : 32ll * 32 * 32; }
 inline bool audio_mode_ok(int mode) { return mode == CASYNC_AUDIO_HUBERT || mode == CASYNC_AUDIO_WENET; }
-const IR kFuse[4] = {{"fuse_conv.0.double_conv.0", 1024, 512, 1, 0, 10},
-                     {"fuse_conv.0.double_conv.1", 512, 512, 1, 1, 10},
-                     {"fuse_conv.1.double_conv.0", 512, 256, 1, 0, 10},
-                     {"fuse_conv.1.double_conv.1", 256, 256, 1, 1, 10}};
+const IR kFuse[4] = {{"fuse_conv.0.double_conv.0", 13, 1024, 512, 1, 0, 10},
+                     {"fuse_conv.0.double_conv.1", 14, 512, 512, 1, 1, 10},
+                     {"fuse_conv.1.double_conv.0", 15, 512, 256, 1, 0, 10},
+                     {"fuse_conv.1.double_conv.1", 16, 256, 256, 1, 1, 10}};
 const IR kUp[4][2] = {
-    {{"up1.conv.double_conv.0", 512, 128, 1, 0, 20}, {"up1.conv.double_conv.1", 128, 128, 1, 1, 20}},
-    {{"up2.conv.double_conv.0", 256, 64, 1, 0, 40}, {"up2.conv.double_conv.1", 64, 64, 1, 1, 40}},
-    {{"up3.conv.double_conv.0", 128, 32, 1, 0, 80}, {"up3.conv.double_conv.1", 32, 32, 1, 1, 80}},
-    {{"up4.conv.double_conv.0", 64, 32, 1, 0, 160}, {"up4.conv.double_conv.1", 32, 32, 1, 1, 160}}};
+    {{"up1.conv.double_conv.0", 17, 512, 128, 1, 0, 20}, {"up1.conv.double_conv.1", 18, 128, 128, 1, 1, 20}},
+    {{"up2.conv.double_conv.0", 19, 256, 64, 1, 0, 40}, {"up2.conv.double_conv.1", 20, 64, 64, 1, 1, 40}},
+    {{"up3.conv.double_conv.0", 21, 128, 32, 1, 0, 80}, {"up3.conv.double_conv.1", 22, 32, 32, 1, 1, 80}},
+    {{"up4.conv.double_conv.0", 23, 64, 32, 1, 0, 160}, {"up4.conv.double_conv.1", 24, 32, 32, 1, 1, 160}}};
+constexpr int kIRs = 25;            // inverted residuals of one network
 constexpr int kBlocks = 4;          // attention blocks
 constexpr int kKV = 64 + 512;       // per-block [K | V] projection columns
+const char* const kAttName[kBlocks] = {"attention_blocks.0", "attention_blocks.1", "attention_blocks.2", "attention_blocks.3"};
+const char* const kUpName[4] = {"up1", "up2", "up3", "up4"};
 
 // ------------------------------------------------------------------ packed weights
-void add_ir(PackedLayout& l, const IR& b) {
-  const std::string p = b.prefix;
-  l.add(p + ".pw1.w", (int64_t)b.cexp() * b.cin);
-  l.add(p + ".pw1.b", b.cexp());
-  l.add(p + ".dw.w", 9 * (int64_t)b.cexp());
-  l.add(p + ".dw.b", b.cexp());
-  l.add(p + ".pw2.w", (int64_t)b.cout * b.cexp());
-  l.add(p + ".pw2.b", b.cout);
-}
+// The packed buffer of one audio mode and the offset of every tensor in it, resolved once as the table is built: a forward
+// builds no name and searches nothing (the casync_packed_* accessors read `packed`).
+constexpr int64_t kNoWeight = -1;   // "no such tensor": a bias a GEMM does not add, a tensor the mode does not have
+struct UNetLayout {
+  struct IRW {
+    int64_t pw1_w, pw1_b, dw_w, dw_b, pw2_w, pw2_b;
+    // the first block of an Up stage: the two K-halves of its expand matrix as matrices of their own -- [cexp][cin/2] for the
+    // upsampled input (applied at the low resolution: upsample and 1x1 conv commute) and for the skip
+    int64_t pw1a_w = kNoWeight, pw1b_w = kNoWeight;
+  };
+  struct Att {
+    int64_t p1_w, p1_b, q_w, q_b, p1q_w, p1q_b, gamma, b1_w, b1_b, b1_rs;
+  };
+  PackedLayout packed;
+  IRW ir[kIRs];
+  Att att[kBlocks];
+  int64_t inc, conv3_w, conv3_b, conv5_w, conv5_b, bn7_s = kNoWeight, bn7_t = kNoWeight, fc1_w, fc1_b, fc2_w, fc2_b, fc2_rs, kv_w, kv_b,
+      bn_kx_s, bn_kx_t, outc_w, outc_b;
 
-PackedLayout make_layout(int mode) {
+  explicit UNetLayout(int mode) {
     const bool wenet = mode == CASYNC_AUDIO_WENET;
-    PackedLayout l;
-    l.add("inc.inconv.0.fused", 620);  // [w1T 6x12][b1 12][wd 9x12][bd 12][w2T 12x32][b2 32]
+    auto add = [this](const std::string& n, int64_t size) { return packed.add(n, size); };
+    auto add_ir = [&](const IR& b) {
+      const std::string p = b.prefix;
+      IRW& w = ir[b.id];
+      w.pw1_w = add(p + ".pw1.w", (int64_t)b.cexp() * b.cin);
+      w.pw1_b = add(p + ".pw1.b", b.cexp());
+      w.dw_w = add(p + ".dw.w", 9 * (int64_t)b.cexp());
+      w.dw_b = add(p + ".dw.b", b.cexp());
+      w.pw2_w = add(p + ".pw2.w", (int64_t)b.cout * b.cexp());
+      w.pw2_b = add(p + ".pw2.b", b.cout);
+    };
+    inc = add("inc.inconv.0.fused", 620);  // [w1T 6x12][b1 12][wd 9x12][bd 12][w2T 12x32][b2 32]
     for (auto& st : kDown)
-      for (auto& b : st) add_ir(l, b);
-    add_ir(l, wenet ? kAudioW[0] : kAudio[0]);
-    add_ir(l, wenet ? kAudioW[1] : kAudio[1]);
-    l.add("audio_model.conv3.w", 256ll * 9 * (wenet ? 256 : 128));  // [N][(ky,kx,cin)]
-    l.add("audio_model.conv3.b", 256);
-    add_ir(l, kAudio[2]);
-    l.add("audio_model.conv5.w", 512ll * 9 * 256);
-    l.add("audio_model.conv5.b", 512);
-    add_ir(l, kAudio[3]);
-    add_ir(l, kAudio[4]);
+      for (auto& b : st) add_ir(b);
+    add_ir(wenet ? kAudioW[0] : kAudio[0]);
+    add_ir(wenet ? kAudioW[1] : kAudio[1]);
+    conv3_w = add("audio_model.conv3.w", 256ll * 9 * (wenet ? 256 : 128));  // [N][(ky,kx,cin)]
+    conv3_b = add("audio_model.conv3.b", 256);
+    add_ir(kAudio[2]);
+    conv5_w = add("audio_model.conv5.w", 512ll * 9 * 256);
+    conv5_b = add("audio_model.conv5.b", 512);
+    add_ir(kAudio[3]);
+    add_ir(kAudio[4]);
     if (!wenet) {   // AudioConvWenet ends at conv7: no bn7 / relu7 (module/unet.py:135-144)
-      l.add("audio_model.bn7.s", 512);
-      l.add("audio_model.bn7.t", 512);
+      bn7_s = add("audio_model.bn7.s", 512);
+      bn7_t = add("audio_model.bn7.t", 512);
     }
-    l.add("mlp_fusion.fc1.w", 1024ll * 1024);
-    l.add("mlp_fusion.fc1.b", 1024);
-    l.add("mlp_fusion.fc2.w", 1024ll * 1024);  // bn2 and bn_tx folded in
-    l.add("mlp_fusion.fc2.b", 1024);
-    l.add("mlp_fusion.fc2.rs", 1024);          // bn_tx scale on the cat(x5, a) residual
-    l.add("att.kv.w", (int64_t)kBlocks * kKV * 512);  // rows: blk0 K(64) V(512), blk1 ...
-    l.add("att.kv.b", kBlocks * kKV);
+    fc1_w = add("mlp_fusion.fc1.w", 1024ll * 1024);
+    fc1_b = add("mlp_fusion.fc1.b", 1024);
+    fc2_w = add("mlp_fusion.fc2.w", 1024ll * 1024);  // bn2 and bn_tx folded in
+    fc2_b = add("mlp_fusion.fc2.b", 1024);
+    fc2_rs = add("mlp_fusion.fc2.rs", 1024);         // bn_tx scale on the cat(x5, a) residual
+    kv_w = add("att.kv.w", (int64_t)kBlocks * kKV * 512);  // rows: blk0 K(64) V(512), blk1 ...
+    kv_b = add("att.kv.b", kBlocks * kKV);
     for (int i = 0; i < kBlocks; ++i) {
-      const std::string p = "attention_blocks." + std::to_string(i);
-      l.add(p + ".p1.w", 512ll * 1024);
-      l.add(p + ".p1.b", 512);
-      l.add(p + ".q.w", 64ll * 512);
-      l.add(p + ".q.b", 64);
+      const std::string p = kAttName[i];
+      Att& a = att[i];
+      a.p1_w = add(p + ".p1.w", 512ll * 1024);
+      a.p1_b = add(p + ".p1.b", 512);
+      a.q_w = add(p + ".q.w", 64ll * 512);
+      a.q_b = add(p + ".q.b", 64);
       // rows 0..511 = p_1, rows 512..575 = query_conv o p_1 composed on the host in float64
       // (module/unet.py:201,209,256,264): q comes out of the p_1 GEMM as 64 extra columns
-      l.add(p + ".p1q.w", 576ll * 1024);
-      l.add(p + ".p1q.b", 576);
-      l.add(p + ".gamma", 1);
-      l.add(p + ".b1.w", 1024ll * 512);  // block bn folded in
-      l.add(p + ".b1.b", 1024);
-      l.add(p + ".b1.rs", 1024);         // block bn scale on the tx residual
+      a.p1q_w = add(p + ".p1q.w", 576ll * 1024);
+      a.p1q_b = add(p + ".p1q.b", 576);
+      a.gamma = add(p + ".gamma", 1);
+      a.b1_w = add(p + ".b1.w", 1024ll * 512);  // block bn folded in
+      a.b1_b = add(p + ".b1.b", 1024);
+      a.b1_rs = add(p + ".b1.rs", 1024);        // block bn scale on the tx residual
     }
-    l.add("bn_kx.s", 1024);
-    l.add("bn_kx.t", 1024);
-    for (auto& b : kFuse) add_ir(l, b);
+    bn_kx_s = add("bn_kx.s", 1024);
+    bn_kx_t = add("bn_kx.t", 1024);
+    for (auto& b : kFuse) add_ir(b);
     for (auto& st : kUp)
-      for (auto& b : st) add_ir(l, b);
-    // Up blocks: the two K-halves of the first block's expand matrix as matrices of their own -- [cexp][cin/2] for the
-    // upsampled input (applied at the low resolution: upsample and 1x1 conv commute) and for the skip
+      for (auto& b : st) add_ir(b);
     for (auto& st : kUp) {
-      l.add(std::string(st[0].prefix) + ".pw1a.w", (int64_t)st[0].cexp() * (st[0].cin / 2));
-      l.add(std::string(st[0].prefix) + ".pw1b.w", (int64_t)st[0].cexp() * (st[0].cin / 2));
+      ir[st[0].id].pw1a_w = add(std::string(st[0].prefix) + ".pw1a.w", (int64_t)st[0].cexp() * (st[0].cin / 2));
+      ir[st[0].id].pw1b_w = add(std::string(st[0].prefix) + ".pw1b.w", (int64_t)st[0].cexp() * (st[0].cin / 2));
     }
-    l.add("outc.w", 96);  // [3][32], outc_bn folded in
-    l.add("outc.b", 3);
-    return l;
-}
+    outc_w = add("outc.w", 96);  // [3][32], outc_bn folded in
+    outc_b = add("outc.b", 3);
+  }
+};
 
-// the packed layout of an audio mode (anything but CASYNC_AUDIO_WENET: the HuBERT one)
-const PackedLayout& layout(int mode = CASYNC_AUDIO_HUBERT) {
-  static const PackedLayout L[2] = {make_layout(CASYNC_AUDIO_HUBERT), make_layout(CASYNC_AUDIO_WENET)};
+// the layout of an audio mode (anything but CASYNC_AUDIO_WENET: the HuBERT one)
+const UNetLayout& layout(int mode = CASYNC_AUDIO_HUBERT) {
+  static const UNetLayout L[2] = {UNetLayout(CASYNC_AUDIO_HUBERT), UNetLayout(CASYNC_AUDIO_WENET)};
   return L[mode == CASYNC_AUDIO_WENET ? 1 : 0];
 }
 
@@ -156,34 +177,57 @@ struct Ptr {
   operator const void*() const { return p; }
 };
 
-// Largest expanded (2x) tensor an UN-fused inverted residual of the plan writes, per frame: the E1/E2
-// slots are sized for it.  With the fused kernels on (default) that is up2.0's 40x40x512, not the
-// 160x160x128 of up4.0 the fused kernel keeps in LDS (19.6 MB per frame less workspace).
-bool ir_is_fused(const CasyncOptions& o, const IR& b) {
-  return o.fuse_ir && b.square() && b.hw_in >= o.fuse_min_hw && ir_fused_supported(b.cin, b.cout, b.stride);
+// How one inverted residual computes its expanded (2x) tensor and the depthwise conv behind it.  THE place that decides it:
+// Plan::ir() switches on the answer, the arena sizes E1 / E2 by it and up_mode() asks it what an Up block can take.
+enum class Expand {
+  Fused,    // ir_fused_kernel: the whole block in one launch, E never leaves LDS
+  Rect,     // expand + depthwise in one launch on rectangular frames (AudioConvWenet's 16x32 blocks): whole-frame tiles
+  Square,   // expand GEMM whose output tile is whole frames or strips: the depthwise conv runs on the tile in LDS, E never reaches HBM
+  Gemm,     // expand GEMM into E1, depthwise E1 -> E2
+  None      // bf16 with an upsampled addend that no bf16 kernel takes
+};
+// `frames` per launch; `ups`: the expand conv runs over the skip half (cin / 2 channels) and adds the upsampled G = W1a . lo of
+// an Up block in front of its activation; `extra`: the project GEMM has epilogue work the fused kernel does not do
+Expand expand_path(const CasyncOptions& o, const IR& b, int dtype, int frames, bool ups, bool extra = false) {
+  const bool f32 = dtype == DT_F32, sq = b.square();
+  const int k_in = ups ? b.cin / 2 : b.cin;
+  if (!extra && !ups && o.fuse_ir && sq && b.hw_in >= o.fuse_min_hw && ir_fused_supported(b.cin, b.cout, b.stride)) return Expand::Fused;
+  // the precision's switch (1: below 40x40 only) and the frames per launch from which whole-frame tiles fill the chip (fp32: from
+  // fuse_dw_min = 12, below that they are too few -- B=1 0.92 vs 0.82 ms)
+  const int on = f32 ? o.fuse_dw : o.fuse_dw_bf16, whole = f32 ? o.fuse_dw_min : o.fuse_dw_bf16_min;
+  if (on && !sq && !ups && frames >= whole && (f32 ? pw_dw_rect_supported : pw_dw_bf16_rect_supported)(b.hw_in, b.wd(), k_in, b.cexp(), b.stride))
+    return Expand::Rect;   // (rectangular frames have kernels of their own)
+  if (on && sq && (b.hw_in < 40 || on >= 2)) {
+    // (fp32 below fuse_dw_deep frames per launch -- round 5 -- the stride-1 blocks take its one-frame tiles with a four-stage ring)
+    if (f32 && (pw_dw_deep(b.hw_in, frames, b.stride, ups, k_in) || frames >= (b.hw_in == 40 ? o.fuse_dw_min40 : whole)) &&
+        pw_dw_supported(b.hw_in, k_in, b.cexp(), b.stride))
+      return Expand::Square;
+    if (!f32 && frames >= whole && pw_dw_bf16_supported(b.hw_in, k_in, b.cexp(), b.stride) && (!ups || pw_dw_bf16_takes_ups(b.hw_in, b.stride)))
+      return Expand::Square;
+  }
+  return !f32 && ups ? Expand::None : Expand::Gemm;
 }
+// (neither the precision nor the frame count reaches the fused arm)
+bool ir_is_fused(const CasyncOptions& o, const IR& b) { return expand_path(o, b, DT_F32, 0, false) == Expand::Fused; }
 bool up_is_fused(const CasyncOptions& o, const IR& b0) {
   return o.fuse_ir && o.fuse_up && b0.hw_in >= o.fuse_min_hw && ir_fused_up_supported(b0.cin, b0.cout);
 }
 // How the first inverted residual of an Up stage takes its upsampled half.  ONE predicate for the plan (decode()) and for
-// the workspace (max_unfused_expand()): round 3 had them apart and `fuse_up=0` sent up3.0 / up4.0 down the un-fused chain
-// with E1 / E2 sized for up2.0.
+// the workspace (max_unfused_expand()): apart, `fuse_up=0` sends up3.0 / up4.0 down the un-fused chain with E1 / E2 sized
+// for up2.0.
 enum class UpMode {
   CommuteUnfused,   // G = W1a.lo at the low resolution, then the un-fused chain (pw_dw / GEMM + depthwise) adds up(G)
   CommuteFused,     // G = W1a.lo, then ir_fused_kernel<.., UPS = 2>
   FusedLoad,        // ir_fused_kernel<.., UPS = 1>: bilinear taps while loading the A fragments
   Materialise       // upsample2x into the concat buffer, then the block as any other inverted residual
 };
-// does the bf16 engine's expand + depthwise kernel take this block with its upsampled addend? (`batch` frames per launch)
-bool bf16_commutes(const CasyncOptions& o, const IR& b0, int batch) {
-  return o.ups_commute_bf16 && o.fuse_dw_bf16 && (b0.hw_in < 40 || o.fuse_dw_bf16 >= 2) && batch >= o.fuse_dw_bf16_min &&
-         pw_dw_bf16_takes_ups(b0.hw_in, b0.stride) && pw_dw_bf16_supported(b0.hw_in, b0.cin / 2, b0.cexp(), b0.stride);
-}
 UpMode up_mode(const CasyncOptions& o, const IR& b0, int dtype, int batch = 0) {
   const bool f32 = dtype == DT_F32;
   if (up_is_fused(o, b0)) return f32 && o.ups_commute >= 2 ? UpMode::CommuteFused : UpMode::FusedLoad;
-  // a block the plain fused kernel takes (fuse_up = 0, fuse_ir = 1) keeps it: upsample first, E never leaves LDS
-  if (!ir_is_fused(o, b0) && (f32 ? o.ups_commute != 0 : bf16_commutes(o, b0, batch))) return UpMode::CommuteUnfused;
+  // a block the plain fused kernel takes (fuse_up = 0, fuse_ir = 1) keeps it: upsample first, E never leaves LDS.  bf16 commutes
+  // where its expand + depthwise kernel takes the block with the addend (`batch` frames per launch).
+  if (!ir_is_fused(o, b0) && (f32 ? o.ups_commute != 0 : o.ups_commute_bf16 && expand_path(o, b0, DT_BF16, batch, true) == Expand::Square))
+    return UpMode::CommuteUnfused;
   return UpMode::Materialise;
 }
 constexpr int kMinLaneBatch = 16;
@@ -191,6 +235,9 @@ constexpr int kMinLaneBatch = 16;
 bool skip_early_batch(const CasyncOptions& o, int batch) {
   return o.skip_early > 0 && batch < o.skip_early && batch < kMinLaneBatch * 2;
 }
+// Largest expanded (2x) tensor an UN-fused inverted residual of the plan writes, per frame: the E1/E2
+// slots are sized for it.  With the fused kernels on (default) that is up2.0's 40x40x512, not the
+// 160x160x128 of up4.0 the fused kernel keeps in LDS (19.6 MB per frame less workspace).
 int64_t max_unfused_expand(const CasyncOptions& o) {
   int64_t mx = 0;
   auto see = [&](const IR& b, bool fused) {
@@ -302,11 +349,9 @@ struct casync_engine {
   bool streams_ready = false;
   CasyncOptions opt;         // this handle's switches: process defaults at create, casync_set_option afterwards
   CasyncOptions eff;         // what the forward in progress runs under (run_forward: `opt` + the bf16 large-batch plan)
-  const float* W(const std::string& name) const { return pw.w + layout(mode).off(name); }
+  const float* W(int64_t off) const { return pw.w + off; }   // off: a member of layout(mode)
   // GEMM weight matrix in the engine's storage type
-  const void* WG(const std::string& name) const {
-    return dtype == DT_BF16 ? (const void*)(pw.w16 + layout(mode).off(name)) : (const void*)(pw.w + layout(mode).off(name));
-  }
+  const void* WG(int64_t off) const { return dtype == DT_BF16 ? (const void*)(pw.w16 + off) : (const void*)(pw.w + off); }
 };
 
 namespace {
@@ -369,14 +414,16 @@ struct Runner {
   std::vector<hipEvent_t> ev;
   int status = CASYNC_OK;
 
-  // f() issues one kernel launch (casync_launch): a profiled row is named after the kernel it launched
+  // f() issues one kernel launch (casync_launch): a profiled row is called prefix + suffix (put together only here, when
+  // profiling) and names the kernel it launched
   template <class F>
-  void run(const char* name, double flops, double bytes, F&& f) {
+  void run(const char* prefix, const char* suffix, double flops, double bytes, F&& f) {
     if (status != CASYNC_OK) return;
     if (!profile) {
       status = f();
       return;
     }
+    const std::string name = std::string(prefix) + suffix;
     hipEvent_t a, b;
     (void)hipEventCreate(&a);
     (void)hipEventCreate(&b);
@@ -387,12 +434,12 @@ struct Runner {
     ev.push_back(a);
     ev.push_back(b);
     if (status == CASYNC_OK && casync_launch_note.count != 1) {
-      casync_set_error("profile: %s issued %u kernel launches, not one", name, casync_launch_note.count);
+      casync_set_error("profile: %s issued %u kernel launches, not one", name.c_str(), casync_launch_note.count);
       status = CASYNC_ERR_STATE;
     }
     casync_kernel_time t;
     memset(&t, 0, sizeof(t));
-    strncpy(t.name, name, sizeof(t.name) - 1);
+    strncpy(t.name, name.c_str(), sizeof(t.name) - 1);
     if (status == CASYNC_OK) {
       const char* mangled = hipKernelNameRefByPtr(casync_launch_note.kernel, s);
       strncpy(t.kernel, mangled ? kernel_short_name(mangled).c_str() : "?", sizeof(t.kernel) - 1);
@@ -455,44 +502,63 @@ struct Plan {
   const int* win_idx = nullptr;
   const CasyncOptions& o = e.eff;     // the options of the forward in progress (run_forward)
 
-  // GEMM wrapper with work accounting (algorithmic bytes: A + C once, W once)
+  const UNetLayout& L = layout(e.mode);   // the offsets W() / WG() take
+  using A = Arena;
   int dt() const { return e.dtype; }
+  const float* bias(int64_t off) const { return off == kNoWeight ? nullptr : e.W(off); }
+  // the stream-K scratch of the stream the next launch goes to, where this plan splits K
+  void bind_stream_k(GemmEpilogue& ep) const {
+    if (char* ctx = stream_k ? e.sk_ctx(lane, aux && r.s == aux ? 1 : 0) : nullptr) {
+      ep.sk_ws = reinterpret_cast<float*>(ctx);
+      ep.sk_cnt = reinterpret_cast<unsigned*>(ctx + kStreamKFloats * 4);
+    }
+  }
 
-  void gemm(const std::string& tag, const void* a, int lda, const std::string& wname, void* c,
-            int ldc, long long m, int n, int k, GemmEpilogue epi, const std::string& bname = "",
-            double alg_flops = 0) {
-    const void* w = e.WG(wname);
-    epi.bias = bname == "-" ? nullptr : e.W(bname.empty() ? wname.substr(0, wname.size() - 1) + "b" : bname);   // "-": none
+  // Send what follows to the second stream, behind what this stream holds so far -> false, status set, where that failed ...
+  bool fork_to_aux(hipEvent_t ev, const char* which) {
+    if (hipEventRecord(ev, r.s) != hipSuccess || hipStreamWaitEvent(aux, ev, 0) != hipSuccess) {
+      casync_set_error("forward: fork onto the %s stream failed", which);
+      r.status = CASYNC_ERR_HIP;
+      return false;
+    }
+    r.s = aux;
+    return true;
+  }
+  // ... and come back to `main_s`: `ev` marks the end of the second stream's work for whoever joins it
+  void back_from_aux(hipEvent_t ev, hipStream_t main_s) {
+    if (r.status == CASYNC_OK && hipEventRecord(ev, aux) != hipSuccess) r.status = CASYNC_ERR_HIP;
+    r.s = main_s;
+  }
+
+  // GEMM wrapper with work accounting (algorithmic bytes: A + C once, W once).  w, b: offsets of the weight matrix and of
+  // the bias (kNoWeight: none)
+  void gemm(const char* prefix, const char* suffix, const void* a, int lda, int64_t w, int64_t b, void* c, int ldc, long long m,
+            int n, int k, GemmEpilogue epi, double alg_flops = 0) {
+    epi.bias = bias(b);
     const double es = dtype_size(dt());
     double bytes = es * ((double)m * k + (double)m * n + (double)n * k);
     if (epi.pre_res) bytes += es * m * n;
     if (epi.post_res) bytes += es * m * n;
     if (epi.acc_out) bytes += 2 * es * m * n;
-    if (char* ctx = stream_k ? e.sk_ctx(lane, aux && r.s == aux ? 1 : 0) : nullptr) {
-      epi.sk_ws = reinterpret_cast<float*>(ctx);
-      epi.sk_cnt = reinterpret_cast<unsigned*>(ctx + kStreamKFloats * 4);
-    }
+    bind_stream_k(epi);
     epi.concurrent = concurrent ? 1 : 0;
     epi.stamps = g_gemm_stamps;
-    r.run(tag.c_str(), alg_flops > 0 ? alg_flops : 2.0 * m * n * k, bytes,
-          [&] { return launch_pw_gemm(a, lda, w, c, ldc, (int)m, n, k, epi, r.s, dt()); });
+    r.run(prefix, suffix, alg_flops > 0 ? alg_flops : 2.0 * m * n * k, bytes,
+          [&] { return launch_pw_gemm(a, lda, e.WG(w), c, ldc, (int)m, n, k, epi, r.s, dt()); });
   }
 
   // Dense 3x3 conv + bias + activation (audio conv3 / conv5: LReLU in AudioConvHubert, module/unet.py:161-168; ReLU and
   // conv3's stride (1, 2) in AudioConvWenet, :119-133) as an implicit GEMM: the ring kernel gathers the taps itself (no
   // im2col buffer).
-  void conv3x3(const std::string& tag, Ptr in, const std::string& wname, Ptr out, int h, int w, int cin, int cout,
-               int stride_h, int stride_w, int pad, int act) {
+  void conv3x3(const char* tag, Ptr in, int64_t wt, int64_t b, Ptr out, int h, int w, int cin, int cout, int stride_h, int stride_w,
+               int pad, int act) {
     const int ho = (h + 2 * pad - 3) / stride_h + 1, wo = (w + 2 * pad - 3) / stride_w + 1;
     const long long m = (long long)B * ho * wo;
     GemmEpilogue ep;
     ep.act = act;
-    ep.bias = e.W(wname.substr(0, wname.size() - 1) + "b");
+    ep.bias = bias(b);
     ep.concurrent = concurrent ? 1 : 0;
-    if (char* ctx = stream_k ? e.sk_ctx(lane, aux && r.s == aux ? 1 : 0) : nullptr) {
-      ep.sk_ws = reinterpret_cast<float*>(ctx);
-      ep.sk_cnt = reinterpret_cast<unsigned*>(ctx + kStreamKFloats * 4);
-    }
+    bind_stream_k(ep);
     // fp32: position-major rows and the tap walk of conv_skip (gemm.hip): the table was built by casync_create_mode, and the
     // FLOPs booked are the executed ones -- the share of (tile, tap) pairs the launcher walks.  The bf16 engine keeps frame-major
     // rows (its convs are bound by data movement: measured 0.4 % slower at B = 512 with the rows regrouped, profiles/padwork_ab.txt).
@@ -502,10 +568,10 @@ struct Plan {
     const int plan_st = !by_position ? CASYNC_OK : ep.conv_tab ? conv3x3_plan(B, h, w, cin, cout, stride_h, stride_w, pad, ep.sk_ws != nullptr, concurrent, dt(), &kt_full, &kt_run)
                                     : CASYNC_ERR_HIP;
     const double es = dtype_size(dt());
-    r.run(tag.c_str(), 2.0 * m * cout * 9 * cin * ((double)kt_run / (double)kt_full),
+    r.run(tag, "", 2.0 * m * cout * 9 * cin * ((double)kt_run / (double)kt_full),
           es * ((double)B * h * w * cin + (double)m * cout + 9.0 * cin * cout), [&] {
       if (plan_st) return plan_st;
-      return launch_conv3x3_gemm(in, e.WG(wname), out, cout, B, h, w, cin, cout, stride_h, stride_w, pad, ep, r.s, dt());
+      return launch_conv3x3_gemm(in, e.WG(wt), out, cout, B, h, w, cin, cout, stride_h, stride_w, pad, ep, r.s, dt());
     });
   }
 
@@ -515,80 +581,60 @@ struct Plan {
   // upsample the expand conv adds before its activation.
   void ir(const IR& b, Ptr in, int ld_in, Ptr out, int ld_out, Ptr e1, Ptr e2,
           const GemmEpilogue* extra = nullptr, Ptr ups = Ptr{}) {
-    const std::string p = b.prefix;
+    const UNetLayout::IRW& w = L.ir[b.id];
+    const char* p = b.prefix;
     const long long m_in = (long long)B * b.hw_in * b.wd(), m_out = (long long)B * b.hw_out() * b.wd_out();
     const int k_in = ups.p ? b.cin / 2 : b.cin;
-    const std::string w1name = p + (ups.p ? ".pw1b.w" : ".pw1.w");
-    if (!extra && !ups.p && ir_is_fused(o, b)) {
+    const int64_t w1 = ups.p ? w.pw1b_w : w.pw1_w;
+    const Expand path = expand_path(o, b, dt(), B, ups.p != nullptr, extra != nullptr);
+    if (path == Expand::Fused) {
       const double flops = 2.0 * (m_in * (double)b.cin * b.cexp() + 9.0 * m_out * b.cexp() +
                                   (double)m_out * b.cexp() * b.cout);
-      r.run((p + ".fused").c_str(), flops, dtype_size(dt()) * (m_in * (double)b.cin + (double)m_out * b.cout), [&] {
-        return launch_ir_fused(in, ld_in, e.WG(p + ".pw1.w"), e.W(p + ".pw1.b"), e.W(p + ".dw.w"),
-                               e.W(p + ".dw.b"), e.WG(p + ".pw2.w"), e.W(p + ".pw2.b"), out, ld_out, B,
-                               b.hw_in, b.hw_in, b.cin, b.cout, b.stride, b.res, r.s, dt());
+      r.run(p, ".fused", flops, dtype_size(dt()) * (m_in * (double)b.cin + (double)m_out * b.cout), [&] {
+        return launch_ir_fused(in, ld_in, e.WG(w.pw1_w), e.W(w.pw1_b), e.W(w.dw_w), e.W(w.dw_b), e.WG(w.pw2_w), e.W(w.pw2_b), out,
+                               ld_out, B, b.hw_in, b.hw_in, b.cin, b.cout, b.stride, b.res, r.s, dt());
       });
       return;
     }
-    // the un-fused chain parks the expanded tensor in e1 / e2: they must have been sized for this block (the arena's
-    // predicate and the plan's are the same functions; this catches the day they are not)
+    // the un-fused chain parks the expanded tensor in e1 / e2: they must have been sized for this block (the arena asks
+    // expand_path() as this function does; this catches the day it does not)
     if (ar.per_frame_of(e2) < (int64_t)b.hw_in * b.wd() * b.cexp()) {
       casync_set_error("plan: %s un-fused needs %lld expanded elements per frame, the workspace slot holds %lld", b.prefix,
                        (long long)b.hw_in * b.wd() * b.cexp(), (long long)ar.per_frame_of(e2));
       r.status = CASYNC_ERR_STATE;
       return;
     }
-    // (from fuse_dw_min = 12 frames per launch: below that its whole-frame tiles are too few to fill the chip -- B=1 0.92 vs 0.82 ms)
-    // (below fuse_dw_deep frames per launch -- round 5 -- the stride-1 blocks take its one-frame tiles with a four-stage ring)
-    // (rectangular frames -- AudioConvWenet's 16x32 blocks -- have kernels of their own: whole-frame tiles from fuse_dw_min frames)
-    const bool sq = b.square();
-    const bool deep = sq && pw_dw_deep(b.hw_in, B, b.stride, ups.p != nullptr, k_in);
-    if (dt() == DT_F32 && o.fuse_dw && !sq && !ups.p && B >= o.fuse_dw_min && pw_dw_rect_supported(b.hw_in, b.wd(), k_in, b.cexp(), b.stride)) {
-      r.run((p + ".pw1dw").c_str(), 2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
-            4.0 * (m_in * (double)k_in + (double)b.cexp() * k_in + (double)m_out * b.cexp()), [&] {
-        return launch_pw_dw_rect(in, ld_in, e.W(w1name), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, b.cexp(), B,
-                                 b.hw_in, b.wd(), k_in, b.cexp(), r.s);
-      });
-    } else if (dt() == DT_BF16 && o.fuse_dw_bf16 && !sq && !ups.p && B >= o.fuse_dw_bf16_min &&
-               pw_dw_bf16_rect_supported(b.hw_in, b.wd(), k_in, b.cexp(), b.stride)) {
-      r.run((p + ".pw1dw").c_str(), 2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
-            2.0 * (m_in * (double)k_in + (double)b.cexp() * k_in + (double)m_out * b.cexp()), [&] {
-        return launch_pw_dw_bf16_rect(in, ld_in, e.WG(w1name), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, b.cexp(), B,
-                                      b.hw_in, b.wd(), k_in, b.cexp(), r.s);
-      });
-    } else if (dt() == DT_F32 && o.fuse_dw && sq && (b.hw_in < 40 || o.fuse_dw >= 2) && (deep || B >= (b.hw_in == 40 ? o.fuse_dw_min40 : o.fuse_dw_min)) &&
-        pw_dw_supported(b.hw_in, k_in, b.cexp(), b.stride)) {
-      // expand GEMM whose output tile is whole frames: the depthwise conv runs on the tile in LDS, E never exists
-      // (flops: what this launch executes -- with `ups` the upsampled half was a GEMM at the low resolution)
-      r.run((p + ".pw1dw").c_str(), 2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
-            4.0 * (m_in * (double)k_in + (double)b.cexp() * k_in + (double)m_out * b.cexp()), [&] {
-        return launch_pw_dw(in, ld_in, e.W(w1name), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2,
-                            b.cexp(), B, b.hw_in, b.stride, k_in, b.cexp(), r.s, ups.p, b.cexp());
-      });
-    } else if (dt() == DT_BF16 && o.fuse_dw_bf16 && sq && (b.hw_in < 40 || o.fuse_dw_bf16 >= 2) && B >= o.fuse_dw_bf16_min &&
-               pw_dw_bf16_supported(b.hw_in, k_in, b.cexp(), b.stride) && (!ups.p || pw_dw_bf16_takes_ups(b.hw_in, b.stride))) {
-      // the bf16 engine's counterpart (round 5): 64-channel tiles, bf16 E image in LDS; E never reaches HBM
-      r.run((p + ".pw1dw").c_str(), 2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
-            2.0 * (m_in * (double)k_in + (double)b.cexp() * k_in + (double)m_out * b.cexp()), [&] {
-        return launch_pw_dw_bf16(in, ld_in, e.WG(w1name), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, b.cexp(), B,
-                                 b.hw_in, b.stride, k_in, b.cexp(), r.s, ups.p, b.cexp());
-      });
-    } else if (dt() == DT_BF16 && ups.p) {
-      casync_set_error("plan: %s was planned with the commuted upsample but the bf16 expand + depthwise kernel does not take it", b.prefix);
-      r.status = CASYNC_ERR_STATE;
-      return;
-    } else {
-      GemmEpilogue ep1;
-      ep1.act = 1;
-      if (ups.p) {
-        ep1.ups_src = ups;
-        ep1.ups_ld = b.cexp();
-        ep1.ups_h = ep1.ups_w = b.hw_in;
+    switch (path) {
+      case Expand::Rect:
+      case Expand::Square:
+        // (flops: what this launch executes -- with `ups` the upsampled half was a GEMM at the low resolution)
+        r.run(p, ".pw1dw", 2.0 * (m_in * (double)k_in * b.cexp() + 9.0 * m_out * b.cexp()),
+              dtype_size(dt()) * (m_in * (double)k_in + (double)b.cexp() * k_in + (double)m_out * b.cexp()), [&] {
+          const bool f32 = dt() == DT_F32;
+          if (path == Expand::Rect)
+            return (f32 ? launch_pw_dw_rect : launch_pw_dw_bf16_rect)(in, ld_in, e.WG(w1), e.W(w.pw1_b), e.W(w.dw_w), e.W(w.dw_b), e2,
+                                                                      b.cexp(), B, b.hw_in, b.wd(), k_in, b.cexp(), r.s);
+          return (f32 ? launch_pw_dw : launch_pw_dw_bf16)(in, ld_in, e.WG(w1), e.W(w.pw1_b), e.W(w.dw_w), e.W(w.dw_b), e2, b.cexp(), B,
+                                                          b.hw_in, b.stride, k_in, b.cexp(), r.s, ups.p, b.cexp());
+        });
+        break;
+      case Expand::None:
+        casync_set_error("plan: %s was planned with the commuted upsample but the bf16 expand + depthwise kernel does not take it", b.prefix);
+        r.status = CASYNC_ERR_STATE;
+        return;
+      default: {
+        GemmEpilogue ep1;
+        ep1.act = 1;
+        if (ups.p) {
+          ep1.ups_src = ups;
+          ep1.ups_ld = b.cexp();
+          ep1.ups_h = ep1.ups_w = b.hw_in;
+        }
+        gemm(p, ".pw1", in, ld_in, w1, w.pw1_b, e1, b.cexp(), m_in, b.cexp(), k_in, ep1);
+        r.run(p, ".dw", 2.0 * 9 * m_out * b.cexp(), dtype_size(dt()) * (double)(m_in + m_out) * b.cexp(), [&] {
+          return launch_dw3x3(e1, e.W(w.dw_w), e.W(w.dw_b), e2, B, b.hw_in, b.wd(), b.cexp(), b.stride, r.s, dt());
+        });
       }
-      gemm(p + ".pw1", in, ld_in, w1name, e1, b.cexp(), m_in, b.cexp(), k_in, ep1, p + ".pw1.b");
-      r.run((p + ".dw").c_str(), 2.0 * 9 * m_out * b.cexp(), dtype_size(dt()) * (double)(m_in + m_out) * b.cexp(), [&] {
-        return launch_dw3x3(e1, e.W(p + ".dw.w"), e.W(p + ".dw.b"), e2, B, b.hw_in, b.wd(), b.cexp(),
-                            b.stride, r.s, dt());
-      });
     }
     GemmEpilogue ep2;
     if (extra) ep2 = *extra;
@@ -597,48 +643,40 @@ struct Plan {
       ep2.post_res = in;
       ep2.ld_post = ld_in;
     }
-    gemm(p + ".pw2", e2, b.cexp(), p + ".pw2.w", out, ld_out, m_out, b.cout, b.cexp(), ep2);
+    gemm(p, ".pw2", e2, b.cexp(), w.pw2_w, w.pw2_b, out, ld_out, m_out, b.cout, b.cexp(), ep2);
   }
 
   // att.kv beside the face encoder (kv_early: 1 = in single-lane runs, where the launch chain is the bound; 2 = always;
   // with two lanes the other lane already fills the chip and the extra stream only competes: -0.5 % at B=64)
   bool kv_in_encode = false;          // set by run_forward for all three phases of a forward alike
-  bool kv_early() const { return kv_in_encode; }
   void kv_projection() {
-    gemm("att.kv", ar[Arena::CATA] + 512, 1024, "att.kv.w", ar[Arena::KV], kBlocks * kKV, (long long)B * 100, kBlocks * kKV, 512,
+    gemm("att.kv", "", ar[Arena::CATA] + 512, 1024, L.kv_w, L.kv_b, ar[Arena::KV], kBlocks * kKV, (long long)B * 100, kBlocks * kKV, 512,
          GemmEpilogue());
   }
 
   // Phase 1 of Model.forward: audio encoder || face encoder down to x5 (module/unet.py:315-321).
   void encode(const float* x, const float* audio) {
-    using A = Arena;
     Ptr E1 = ar[A::E1], E2 = ar[A::E2], T0 = ar[A::T0];
     // The audio encoder and the face encoder are independent until the fusion MLP; with a
     // second stream they run concurrently and the many small 10x10 / 16x16 audio launches fill
     // CUs the face encoder leaves idle.  Profiling mode keeps everything on one stream.
     const bool overlap = aux && !r.profile;
     hipStream_t main_s = r.s;
-    if (overlap) {
-      if (hipEventRecord(ev_fork, main_s) != hipSuccess || hipStreamWaitEvent(aux, ev_fork, 0) != hipSuccess) {
-        casync_set_error("forward: fork onto the audio stream failed");
-        r.status = CASYNC_ERR_HIP;
-        return;
-      }
-      r.s = aux;
-    }
+    if (overlap && !fork_to_aux(ev_fork, "audio")) return;
     // ---------------- audio encoder (module/unet.py:177-194; AudioConvWenet :135-144)
     Ptr AE1 = ar[A::AE1], AE2 = ar[A::AE2];
-    if (e.mode == CASYNC_AUDIO_WENET) {
+    const bool wenet = e.mode == CASYNC_AUDIO_WENET;
+    if (wenet) {
       // [B,256,16,32] -> NHWC 16x32 x 256; two residual blocks at 16x32; conv3 (1,2)-strided to 16x16 + ReLU; conv4; conv5
       // + ReLU to 10x10; conv6; conv7 straight into the audio half of cat([x5, a]) (no bn7 / relu7)
-      r.run("audio.nchw_to_nhwc", 0, (4.0 + dtype_size(dt())) * B * 131072,
+      r.run("audio.nchw_to_nhwc", "", 0, (4.0 + dtype_size(dt())) * B * 131072,
             [&] { return launch_nchw_to_nhwc(audio, ar[A::A0], B, 256, 512, r.s, dt()); });
       if (dt() == DT_BF16) {
         // conv1 is a residual block on the network's fp32 input, and the reference keeps that sum in fp32 under bf16 autocast.  The
         // bf16 window A0 feeds the expand conv; the residual add takes the window to 16 mantissa bits, A0 + A0L with A0L =
         // R(x - R(x)): the project GEMM adds A0 behind its activation (post_res), then the running-sum output adds A0L to the fp32
         // value and rounds ONCE into AC1.  (The GEMM's own C output, rounded before A0L, lands in the dead expand slot AE1.)
-        r.run("audio.nchw_to_nhwc_lo", 0, (4.0 + dtype_size(dt())) * B * 131072,
+        r.run("audio.nchw_to_nhwc_lo", "", 0, (4.0 + dtype_size(dt())) * B * 131072,
               [&] { return launch_nchw_to_nhwc(audio, ar[A::A0L], B, 256, 512, r.s, dt(), 1); });
         GemmEpilogue lo;
         lo.acc_in = (const void*)ar[A::A0L];
@@ -649,44 +687,39 @@ struct Plan {
         ir(kAudioW[0], ar[A::A0], 256, ar[A::AC1], 256, AE1, AE2);
       }
       ir(kAudioW[1], ar[A::AC1], 256, ar[A::AC2], 256, AE1, AE2);
-      conv3x3("audio.conv3", ar[A::AC2], "audio_model.conv3.w", ar[A::AC3], 16, 32, 256, 256, 1, 2, 1, 2);
-      ir(kAudio[2], ar[A::AC3], 256, ar[A::AC4], 256, AE1, AE2);
-      conv3x3("audio.conv5", ar[A::AC4], "audio_model.conv5.w", ar[A::AC5], 16, 16, 256, 512, 2, 2, 3, 2);
-      ir(kAudio[3], ar[A::AC5], 512, ar[A::AC6], 512, AE1, AE2);
-      ir(kAudio[4], ar[A::AC6], 512, ar[A::CATA] + 512, 1024, AE1, AE2);
+      conv3x3("audio.conv3", ar[A::AC2], L.conv3_w, L.conv3_b, ar[A::AC3], 16, 32, 256, 256, 1, 2, 1, 2);
     } else {
-    if (win_feat)
-      r.run("audio.window_gather", 0, (4.0 + dtype_size(dt())) * B * 32768,
-            [&] { return launch_audio_window_gather(win_feat, win_steps, win_idx, ar[A::A0], B, r.s, dt()); });
-    else
-      r.run("audio.nchw_to_nhwc", 0, (4.0 + dtype_size(dt())) * B * 32768,
-            [&] { return launch_nchw_to_nhwc(audio, ar[A::A0], B, 32, 1024, r.s, dt()); });
-    ir(kAudio[0], ar[A::A0], 32, ar[A::AC1], 64, AE1, AE2);
-    ir(kAudio[1], ar[A::AC1], 64, ar[A::AC2], 128, AE1, AE2);
-    conv3x3("audio.conv3", ar[A::AC2], "audio_model.conv3.w", ar[A::AC3], 32, 32, 128, 256, 2, 2, 1, 1);
+      if (win_feat)
+        r.run("audio.window_gather", "", 0, (4.0 + dtype_size(dt())) * B * 32768,
+              [&] { return launch_audio_window_gather(win_feat, win_steps, win_idx, ar[A::A0], B, r.s, dt()); });
+      else
+        r.run("audio.nchw_to_nhwc", "", 0, (4.0 + dtype_size(dt())) * B * 32768,
+              [&] { return launch_nchw_to_nhwc(audio, ar[A::A0], B, 32, 1024, r.s, dt()); });
+      ir(kAudio[0], ar[A::A0], 32, ar[A::AC1], 64, AE1, AE2);
+      ir(kAudio[1], ar[A::AC1], 64, ar[A::AC2], 128, AE1, AE2);
+      conv3x3("audio.conv3", ar[A::AC2], L.conv3_w, L.conv3_b, ar[A::AC3], 32, 32, 128, 256, 2, 2, 1, 1);
+    }
+    // from the 16x16 x 256 map on the two encoders are one: conv4, conv5 (ReLU in AudioConvWenet, LReLU in AudioConvHubert),
+    // conv6, conv7; HuBERT fuses relu7(bn7(x + conv(x))) behind conv7's residual add
     ir(kAudio[2], ar[A::AC3], 256, ar[A::AC4], 256, AE1, AE2);
-    conv3x3("audio.conv5", ar[A::AC4], "audio_model.conv5.w", ar[A::AC5], 16, 16, 256, 512, 2, 2, 3, 1);
+    conv3x3("audio.conv5", ar[A::AC4], L.conv5_w, L.conv5_b, ar[A::AC5], 16, 16, 256, 512, 2, 2, 3, wenet ? 2 : 1);
     ir(kAudio[3], ar[A::AC5], 512, ar[A::AC6], 512, AE1, AE2);
-    {
-      GemmEpilogue bn7;  // relu7(bn7(x + conv(x))) fused behind conv7's residual add
-      bn7.aff_s = e.W("audio_model.bn7.s");
-      bn7.aff_t = e.W("audio_model.bn7.t");
-      ir(kAudio[4], ar[A::AC6], 512, ar[A::CATA] + 512, 1024, AE1, AE2, &bn7);
+    GemmEpilogue bn7;
+    if (!wenet) {
+      bn7.aff_s = e.W(L.bn7_s);
+      bn7.aff_t = e.W(L.bn7_t);
     }
-    }
+    ir(kAudio[4], ar[A::AC6], 512, ar[A::CATA] + 512, 1024, AE1, AE2, wenet ? nullptr : &bn7);
     // K and V projections of the audio features for all four attention blocks in one GEMM (module/unet.py:202-203,
     // 210, 214).  They depend on the audio branch alone, so they run HERE, on the audio stream beside the face encoder,
     // instead of between the fusion MLP and the first attention block (one launch less on the serial chain: at B=8,
     // the reference's own batch, 24 us of 1.26 ms).
-    if (kv_early()) kv_projection();
-    if (overlap) {
-      if (r.status == CASYNC_OK && hipEventRecord(ev_join, aux) != hipSuccess) r.status = CASYNC_ERR_HIP;
-      r.s = main_s;
-    }
+    if (kv_in_encode) kv_projection();
+    if (overlap) back_from_aux(ev_join, main_s);
     // ---------------- face encoder (module/unet.py:315-319)
-    r.run("inc", 2.0 * B * 25600 * (72 + 108 + 384),
+    r.run("inc", "", 2.0 * B * 25600 * (72 + 108 + 384),
           (double)B * 25600 * (6 * 4 + 32 * dtype_size(dt())), [&] {
-      return launch_inc(x, e.W("inc.inconv.0.fused"), ar[A::CAT4] + 32, 64, B, r.s, dt());
+      return launch_inc(x, e.W(L.inc), ar[A::CAT4] + 32, 64, B, r.s, dt());
     });
     struct Skip { Ptr p; int ld; };
     const Skip sk[5] = {{ar[A::CAT4] + 32, 64},   {ar[A::CAT3] + 64, 128}, {ar[A::CAT2] + 128, 256},
@@ -704,7 +737,6 @@ struct Plan {
   // Phase 2: the 10x10 trunk -- fusion MLP, four attention blocks, fuse_conv (module/unet.py:323-337).
   // All of it is [B*100, C] GEMMs (+ the attention core and four small depthwise convs).
   void trunk() {
-    using A = Arena;
     Ptr E1 = ar[A::E1], E2 = ar[A::E2], T0 = ar[A::T0];
     // ---------------- skip_early: W1b . skip + b of up1.0 / up2.0 depend on the encoder alone.  At small batch the
     // forward is one launch chain, so they leave it: they run on the second stream beside the
@@ -714,29 +746,14 @@ struct Plan {
     if (skip_early) {
       const bool fork = aux && !r.profile;
       hipStream_t main_s = r.s;
-      if (fork) {
-        if (hipEventRecord(ev_fork2, main_s) != hipSuccess || hipStreamWaitEvent(aux, ev_fork2, 0) != hipSuccess) {
-          casync_set_error("forward: fork onto the second stream failed");
-          r.status = CASYNC_ERR_HIP;
-          return;
-        }
-        r.s = aux;
-      }
-      const Arena::Id ep[2] = {A::EP1, A::EP2};
-      const Arena::Id cat[2] = {A::CAT1, A::CAT2};
-      int hw = 20, c = 256;
+      if (fork && !fork_to_aux(ev_fork2, "second")) return;
       for (int i = 0; i < 2; ++i) {
         const IR& b0 = kUp[i][0];
-        const std::string p = b0.prefix;
-        gemm(p + ".pw1b", ar[cat[i]] + c, 2 * c, p + ".pw1b.w", ar[ep[i]], b0.cexp(), (long long)B * hw * hw, b0.cexp(), c, GemmEpilogue(),
-             p + ".pw1.b");
-        hw *= 2;
-        c = kUp[i][1].cout;
+        const int c = b0.cin / 2;   // the skip half of the concatenated input
+        gemm(b0.prefix, ".pw1b", ar[i ? A::CAT2 : A::CAT1] + c, 2 * c, L.ir[b0.id].pw1b_w, L.ir[b0.id].pw1_b, ar[i ? A::EP2 : A::EP1], b0.cexp(),
+             (long long)B * b0.hw_in * b0.hw_in, b0.cexp(), c, GemmEpilogue());
       }
-      if (fork) {
-        if (r.status == CASYNC_OK && hipEventRecord(ev_skip, aux) != hipSuccess) r.status = CASYNC_ERR_HIP;
-        r.s = main_s;
-      }
+      if (fork) back_from_aux(ev_skip, main_s);
     }
     // ---------------- fusion (module/unet.py:323-326): tx = bn_tx(cat + mlp(cat))
     const long long M10 = (long long)B * 100;
@@ -744,54 +761,53 @@ struct Plan {
     {
       GemmEpilogue ep;
       ep.act = 1;
-      gemm("mlp.fc1", CATA, 1024, "mlp_fusion.fc1.w", ar[A::H], 1024, M10, 1024, 1024, ep);
+      gemm("mlp.fc1", "", CATA, 1024, L.fc1_w, L.fc1_b, ar[A::H], 1024, M10, 1024, 1024, ep);
       GemmEpilogue ep2;
       ep2.pre_res = CATA;
       ep2.ld_pre = 1024;
-      ep2.pre_scale = e.W("mlp_fusion.fc2.rs");
-      gemm("mlp.fc2", ar[A::H], 1024, "mlp_fusion.fc2.w", ar[A::TX], 1024, M10, 1024, 1024, ep2);
+      ep2.pre_scale = e.W(L.fc2_rs);
+      gemm("mlp.fc2", "", ar[A::H], 1024, L.fc2_w, L.fc2_b, ar[A::TX], 1024, M10, 1024, 1024, ep2);
     }
-    if (!kv_early()) kv_projection();
+    if (!kv_in_encode) kv_projection();
     // ---------------- attention blocks (module/unet.py:331-336)
     Ptr ox[4] = {ar[A::OX0], ar[A::OX1], ar[A::OX2], ar[A::OX3]};
-    Ptr prev = ar[A::TX];
     for (int i = 0; i < kBlocks; ++i) {
-      const std::string p = "attention_blocks." + std::to_string(i);
+      const Ptr prev = i ? ox[i - 1] : ar[A::TX];
+      const UNetLayout::Att& w = L.att[i];
+      const char* p = kAttName[i];
       // ox = p_1(x) lands in columns 0..511 of P1Q (ld 576); q = query_conv(ox) in columns 512..575:
       // either as 64 extra output columns of the same GEMM (weights composed on the host, default) or
       // by the reference's own second GEMM on ox
       Ptr P1 = ar[A::P1Q], Qp = ar[A::P1Q] + 512;
       int ldq = 576;
       if (o.fuse_q) {
-        gemm(p + ".p1q", prev, 1024, p + ".p1q.w", P1, 576, M10, 576, 1024, GemmEpilogue(), "",
-             2.0 * M10 * (1024.0 * 512 + 512.0 * 64));
+        gemm(p, ".p1q", prev, 1024, w.p1q_w, w.p1q_b, P1, 576, M10, 576, 1024, GemmEpilogue(), 2.0 * M10 * (1024.0 * 512 + 512.0 * 64));
       } else {
-        gemm(p + ".p1", prev, 1024, p + ".p1.w", P1, 576, M10, 512, 1024, GemmEpilogue());
-        gemm(p + ".q", P1, 576, p + ".q.w", ar[A::Q], 64, M10, 64, 512, GemmEpilogue());
+        gemm(p, ".p1", prev, 1024, w.p1_w, w.p1_b, P1, 576, M10, 512, 1024, GemmEpilogue());
+        gemm(p, ".q", P1, 576, w.q_w, w.q_b, ar[A::Q], 64, M10, 64, 512, GemmEpilogue());
         Qp = ar[A::Q];
         ldq = 64;
       }
       Ptr kv = ar[A::KV] + i * kKV;
-      r.run((p + ".attn").c_str(), 2.0 * M10 * 100 * (64 + 512),
+      r.run(p, ".attn", 2.0 * M10 * 100 * (64 + 512),
             dtype_size(dt()) * (double)M10 * (64 + kKV + 1024), [&] {
         return launch_cross_attention(Qp, ldq, kv, kBlocks * kKV, kv + 64, kBlocks * kKV, P1, 576,
-                                      e.W(p + ".gamma"), ar[A::AO], 512, B, r.s, dt());
+                                      e.W(w.gamma), ar[A::AO], 512, B, r.s, dt());
       });
       GemmEpilogue ep;  // lrelu(bn(b_1(ox) + tx)); kx += ox; last block also lrelu(bn_kx(kx))
       ep.pre_res = ar[A::TX];
       ep.ld_pre = 1024;
-      ep.pre_scale = e.W(p + ".b1.rs");
+      ep.pre_scale = e.W(w.b1_rs);
       ep.act = 1;
       ep.acc_in = i == 0 ? (const void*)ar[A::TX] : (const void*)ar[A::KX];
       ep.acc_out = i == kBlocks - 1 ? (void*)ar[A::KXF] : (void*)ar[A::KX];
       ep.ld_acc = 1024;
       if (i == kBlocks - 1) {
-        ep.aff_s = e.W("bn_kx.s");
-        ep.aff_t = e.W("bn_kx.t");
+        ep.aff_s = e.W(L.bn_kx_s);
+        ep.aff_t = e.W(L.bn_kx_t);
         ep.aff_on_acc = 1;
       }
-      gemm(p + ".b1", ar[A::AO], 512, p + ".b1.w", ox[i], 1024, M10, 1024, 512, ep);
-      prev = ox[i];
+      gemm(p, ".b1", ar[A::AO], 512, w.b1_w, w.b1_b, ox[i], 1024, M10, 1024, 512, ep);
     }
     // ---------------- fuse_conv (module/unet.py:337)
     ir(kFuse[0], ar[A::KXF], 1024, T0, 512, E1, E2);
@@ -802,84 +818,69 @@ struct Plan {
 
   // Phase 3: decoder + head (module/unet.py:338-344).
   void decode(float* out) {
-    using A = Arena;
     Ptr E1 = ar[A::E1], E2 = ar[A::E2], T0 = ar[A::T0];
     // ---------------- decoder (module/unet.py:338-341)
-    Ptr lo = ar[A::F];
     Ptr cat[4] = {ar[A::CAT1], ar[A::CAT2], ar[A::CAT3], ar[A::CAT4]};
     Ptr uo[4] = {ar[A::U1], ar[A::U2], ar[A::U3], ar[A::U4]};
-    int hw = 10, c = 256;
     for (int i = 0; i < 4; ++i) {
-      const int cc = 2 * c;  // concat width
       const IR& b0 = kUp[i][0];
+      const Ptr lo = i ? uo[i - 1] : ar[A::F];
+      const int hw = b0.hw_in / 2, c = b0.cin / 2, cc = b0.cin;   // the low resolution, its channels (= the skip's), the concat width
+      const double m = (double)B * b0.hw_in * b0.hw_in;           // rows of the stage
+      const UNetLayout::IRW& w = L.ir[b0.id];
+      const char* p = b0.prefix;
       const UpMode mode = up_mode(o, b0, dt(), B);
+      // upsample and 1x1 conv commute: the upsampled half of the expand conv runs on the LOW-resolution tensor
+      // (a quarter of the pixels: 37.5 % of this GEMM's multiply-adds never happen), the consumer adds its bilinear
+      // x2 upsample before the activation.  Every launch books the flops it executes.
+      if (mode == UpMode::CommuteUnfused || mode == UpMode::CommuteFused)
+        gemm(p, ".pw1a", lo, c, w.pw1a_w, kNoWeight, ar[A::UG], b0.cexp(), (long long)B * hw * hw, b0.cexp(), c, GemmEpilogue());
       if (mode == UpMode::CommuteUnfused) {
-        // upsample and 1x1 conv commute: the upsampled half of the expand conv runs on the LOW-resolution tensor
-        // (a quarter of the pixels: 37.5 % of this GEMM's multiply-adds never happen), the consumer adds its bilinear
-        // x2 upsample before the activation.  Every launch books the flops it executes.
-        gemm(std::string(b0.prefix) + ".pw1a", lo, c, std::string(b0.prefix) + ".pw1a.w", ar[A::UG], b0.cexp(),
-             (long long)B * hw * hw, b0.cexp(), c, GemmEpilogue(), "-", 2.0 * B * hw * hw * (double)c * b0.cexp());
         if (skip_early && i < 2) {
           // the skip half is already there (trunk()): depthwise over LReLU(pre + up(G)), then the project GEMM
-          const std::string p = b0.prefix;
-          const long long m = (long long)B * 4 * hw * hw;
           if (i == 0 && aux && !r.profile && hipStreamWaitEvent(r.s, ev_skip, 0) != hipSuccess) {
             casync_set_error("forward: join of the second stream failed");
             r.status = CASYNC_ERR_HIP;
             return;
           }
           const float* pre = (const float*)ar[i == 0 ? A::EP1 : A::EP2].p;
-          r.run((p + ".dwups").c_str(), 2.0 * 9 * m * b0.cexp(),
-                4.0 * ((double)m * b0.cexp() * 2 + (double)m / 4 * b0.cexp()), [&] {
-            return launch_dw3x3_ups(pre, (const float*)ar[A::UG].p, b0.cexp(), e.W(p + ".dw.w"), e.W(p + ".dw.b"), (float*)E2.p, B,
-                                    2 * hw, 2 * hw, b0.cexp(), r.s);
+          r.run(p, ".dwups", 2.0 * 9 * m * b0.cexp(), 4.0 * (m * b0.cexp() * 2 + m / 4 * b0.cexp()), [&] {
+            return launch_dw3x3_ups(pre, (const float*)ar[A::UG].p, b0.cexp(), e.W(w.dw_w), e.W(w.dw_b), (float*)E2.p, B, 2 * hw, 2 * hw,
+                                    b0.cexp(), r.s);
           });
           GemmEpilogue ep2;
           ep2.act = 1;
-          gemm(p + ".pw2", E2, b0.cexp(), p + ".pw2.w", T0, b0.cout, m, b0.cout, b0.cexp(), ep2);
+          gemm(p, ".pw2", E2, b0.cexp(), w.pw2_w, w.pw2_b, T0, b0.cout, (long long)m, b0.cout, b0.cexp(), ep2);
         } else {
           ir(b0, cat[i] + c, cc, T0, b0.cout, E1, E2, nullptr, ar[A::UG]);
         }
       } else if (mode == UpMode::CommuteFused) {
-        // the same commutation inside the fused kernel: G = W1a * lo by a GEMM at the low resolution, the fused
-        // block runs its expand over the skip half only and adds up(G) chunk by chunk from LDS
-        const std::string p = b0.prefix;
-        const double m = (double)B * 4 * hw * hw;
-        gemm(p + ".pw1a", lo, c, p + ".pw1a.w", ar[A::UG], b0.cexp(), (long long)B * hw * hw, b0.cexp(), c, GemmEpilogue(), "-",
-             2.0 * B * hw * hw * (double)c * b0.cexp());
-        r.run((p + ".upfused").c_str(), 2.0 * m * (c * b0.cexp() + 9.0 * b0.cexp() + b0.cexp() * b0.cout),
+        // the same commutation inside the fused kernel: the fused block runs its expand over the skip half only and adds
+        // up(G) chunk by chunk from LDS
+        r.run(p, ".upfused", 2.0 * m * (c * b0.cexp() + 9.0 * b0.cexp() + b0.cexp() * b0.cout),
               4.0 * (m / 4 * b0.cexp() + m * c + m * b0.cout), [&] {
-                return launch_ir_fused_upg((const float*)ar[A::UG].p, b0.cexp(), (const float*)(cat[i] + c).p, cc,
-                                           e.W(p + ".pw1b.w"), e.W(p + ".pw1.b"), e.W(p + ".dw.w"), e.W(p + ".dw.b"),
-                                           e.W(p + ".pw2.w"), e.W(p + ".pw2.b"), (float*)T0.p, b0.cout, B, 2 * hw,
-                                           2 * hw, b0.cin, b0.cout, r.s);
+                return launch_ir_fused_upg((const float*)ar[A::UG].p, b0.cexp(), (const float*)(cat[i] + c).p, cc, e.W(w.pw1b_w),
+                                           e.W(w.pw1_b), e.W(w.dw_w), e.W(w.dw_b), e.W(w.pw2_w), e.W(w.pw2_b), (float*)T0.p, b0.cout, B,
+                                           2 * hw, 2 * hw, b0.cin, b0.cout, r.s);
               });
       } else if (mode == UpMode::FusedLoad) {
         // bilinear x2 folded into the fused block's input load: up(x) is never materialised
-        const std::string p = b0.prefix;
-        const double m = (double)B * 4 * hw * hw;
-        r.run((p + ".upfused").c_str(), 2.0 * m * (b0.cin * b0.cexp() + 9.0 * b0.cexp() + b0.cexp() * b0.cout),
+        r.run(p, ".upfused", 2.0 * m * (b0.cin * b0.cexp() + 9.0 * b0.cexp() + b0.cexp() * b0.cout),
               dtype_size(dt()) * (m / 4 * c + m * c + m * b0.cout), [&] {
-                return launch_ir_fused_up(lo, c, c, cat[i], cc, e.WG(p + ".pw1.w"), e.W(p + ".pw1.b"),
-                                          e.W(p + ".dw.w"), e.W(p + ".dw.b"), e.WG(p + ".pw2.w"),
-                                          e.W(p + ".pw2.b"), T0, b0.cout, B, 2 * hw, 2 * hw, b0.cin, b0.cout, r.s,
-                                          dt());
+                return launch_ir_fused_up(lo, c, c, cat[i], cc, e.WG(w.pw1_w), e.W(w.pw1_b), e.W(w.dw_w), e.W(w.dw_b), e.WG(w.pw2_w),
+                                          e.W(w.pw2_b), T0, b0.cout, B, 2 * hw, 2 * hw, b0.cin, b0.cout, r.s, dt());
               });
       } else {
-        r.run(("up" + std::to_string(i + 1) + ".bilinear").c_str(), 0,
-              dtype_size(dt()) * (double)B * hw * hw * c * 5, [&] {
+        r.run(kUpName[i], ".bilinear", 0, dtype_size(dt()) * (double)B * hw * hw * c * 5, [&] {
           return launch_upsample2x(lo, cat[i], cc, B, hw, hw, c, r.s, dt());
         });
         ir(b0, cat[i], cc, T0, b0.cout, E1, E2);
       }
       ir(kUp[i][1], T0, kUp[i][1].cin, uo[i], kUp[i][1].cout, E1, E2);
-      lo = uo[i];
-      hw *= 2;
-      c = kUp[i][1].cout;
     }
     // ---------------- head (module/unet.py:342-344)
-    r.run("outc", 2.0 * B * 25600 * 96, (double)B * 25600 * (32 * dtype_size(dt()) + 12), [&] {
-      return launch_outc(ar[A::U4], 32, e.W("outc.w"), e.W("outc.b"), out, B, r.s, dt());
+    r.run("outc", "", 2.0 * B * 25600 * 96, (double)B * 25600 * (32 * dtype_size(dt()) + 12), [&] {
+      return launch_outc(ar[A::U4], 32, e.W(L.outc_w), e.W(L.outc_b), out, B, r.s, dt());
     });
   }
 };
@@ -968,19 +969,17 @@ void casync_gate_forget(int device, const void* owner, hipEvent_t* ev) {
 extern "C" {
 
 int casync_abi_version(void) { return CASYNC_ABI_VERSION; }
-int casync_packed_count(void) { return layout().count(); }
-const char* casync_packed_name(int i) { return layout().name(i); }
-int64_t casync_packed_offset(int i) { return layout().offset(i); }
-int64_t casync_packed_size(int i) { return layout().size(i); }
-int64_t casync_packed_total(void) { return layout().total; }
-int casync_packed_count_m(int mode) { return audio_mode_ok(mode) ? layout(mode).count() : 0; }
-const char* casync_packed_name_m(int mode, int i) { return audio_mode_ok(mode) ? layout(mode).name(i) : nullptr; }
-int64_t casync_packed_offset_m(int mode, int i) { return audio_mode_ok(mode) ? layout(mode).offset(i) : -1; }
-int64_t casync_packed_size_m(int mode, int i) { return audio_mode_ok(mode) ? layout(mode).size(i) : -1; }
-int64_t casync_packed_total_m(int mode) { return audio_mode_ok(mode) ? layout(mode).total : -1; }
-int64_t casync_workspace_bytes(int batch) {
-  return batch > 0 ? Arena::bytes(casync_default_options(), batch, 4) : -1;
-}
+int casync_packed_count(void) { return layout().packed.count(); }
+const char* casync_packed_name(int i) { return layout().packed.name(i); }
+int64_t casync_packed_offset(int i) { return layout().packed.offset(i); }
+int64_t casync_packed_size(int i) { return layout().packed.size(i); }
+int64_t casync_packed_total(void) { return layout().packed.total; }
+int casync_packed_count_m(int mode) { return audio_mode_ok(mode) ? layout(mode).packed.count() : 0; }
+const char* casync_packed_name_m(int mode, int i) { return audio_mode_ok(mode) ? layout(mode).packed.name(i) : nullptr; }
+int64_t casync_packed_offset_m(int mode, int i) { return audio_mode_ok(mode) ? layout(mode).packed.offset(i) : -1; }
+int64_t casync_packed_size_m(int mode, int i) { return audio_mode_ok(mode) ? layout(mode).packed.size(i) : -1; }
+int64_t casync_packed_total_m(int mode) { return audio_mode_ok(mode) ? layout(mode).packed.total : -1; }
+int64_t casync_workspace_bytes(int batch) { return casync_workspace_bytes_dt(batch, DT_F32); }
 int64_t casync_workspace_bytes_dt(int batch, int dtype) {
   return batch > 0 && (dtype == DT_F32 || dtype == DT_BF16)
              ? Arena::bytes(casync_default_options(), batch, dtype_size(dtype)) : -1;
@@ -1074,12 +1073,12 @@ void casync_destroy(casync_handle h) {
 
 int casync_load_weights_host(casync_handle h, const float* packed, int64_t n_floats) {
   CASYNC_REQUIRE(h, "load_weights: null");
-  return h->pw.load_host("load_weights", h->device, packed, n_floats, layout(h->mode).total, h->dtype == DT_BF16);
+  return h->pw.load_host("load_weights", h->device, packed, n_floats, layout(h->mode).packed.total, h->dtype == DT_BF16);
 }
 
 int casync_load_weights_device(casync_handle h, const float* packed_dev, int64_t n_floats) {
   CASYNC_REQUIRE(h, "load_weights_device: null");
-  return h->pw.adopt_device("load_weights_device", h->device, packed_dev, n_floats, layout(h->mode).total, h->dtype == DT_BF16);
+  return h->pw.adopt_device("load_weights_device", h->device, packed_dev, n_floats, layout(h->mode).packed.total, h->dtype == DT_BF16);
 }
 
 // The engine's own streams are PROCESS-WIDE, one set per device, created as they are first needed (lane streams before

@@ -7,10 +7,15 @@ test, never the in-tree library:
     CASYNC_LIB=/tmp/parent/calipsync_amd/lib/libcasync_hip.so python tools/record_walk_bits.py --family sync --commit <parent commit>
 
 --family names the handles recorded and thereby the file (the test's GOLDEN): `walk` is S3FD and HuBERT in walk_bits.json, `sync`
-SyncNet_color in walk_bits_sync.json.  Each file has its own parent commit; recording one leaves the other as it is.
+SyncNet_color in walk_bits_sync.json, `unet` the U-Net plan in walk_bits_unet.json.  Each file has its own parent commit;
+recording one leaves the others as they are.
 
 The case table and the run are the test's own (imported from it), so the two cannot drift apart.  Every case runs twice: a
-recording with an output that is not finite, or with a case that does not repeat itself, is refused."""
+recording with an output that is not finite, or with a case that does not repeat itself, is refused.
+
+The `unet` family runs every case three times.  Kernels, profiled rows and workspace sizes have to repeat in every case, and so
+have the hashes of every `sk0` case (gemm_streamk=0): otherwise nothing is written.  A `default` case whose hashes do not repeat
+keeps the rest; its hashes are written as null beside the reason, and the count of such cases is printed."""
 import argparse
 import json
 import os
@@ -24,7 +29,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--commit", required=True, help="id of the commit CASYNC_LIB was built from")
-    ap.add_argument("--family", required=True, choices=("walk", "sync"), help="the handles to record: the file of that family is written")
+    ap.add_argument("--family", required=True, choices=("walk", "sync", "unet"), help="the handles to record: the file of that family is written")
     ap.add_argument("--out", help="another place for the file")
     args = ap.parse_args()
     if not os.environ.get("CASYNC_LIB"):
@@ -37,6 +42,8 @@ def main():
         hipcc = "unknown"
     cases, unstable = {}, []
     out = args.out or T.GOLDEN[args.family]
+    if args.family == "unet":
+        return record_unet(T, args.commit, hipcc, out)
     for name in (n for n in T.CASES if T.family(n) == args.family):
         cases[name] = T.record(name)
         if T.record(name) != cases[name]:
@@ -48,6 +55,35 @@ def main():
         json.dump({"parent_commit": args.commit, "hipcc_version": hipcc, "cases": cases}, f, indent=1)
         f.write("\n")
     print("wrote", out)
+
+
+def record_unet(T, commit, hipcc, out):
+    cases, refused, no_hashes = {}, [], []
+    for name in (n for n in T.CASES if T.family(n) == "unet"):
+        runs = [T.record(name) for _ in range(3)]
+        rec = cases[name] = runs[0]
+        hashed = ("out", "taps")
+        if any({k: v for k, v in r.items() if k not in hashed} != {k: v for k, v in rec.items() if k not in hashed} for r in runs[1:]):
+            refused.append(name + " (kernels, rows or workspace)")
+        elif any(r != rec for r in runs[1:]):
+            differ = sorted({"out" for r in runs[1:] if r["out"] != rec["out"]} | {t for r in runs[1:] for t in rec["taps"] if r["taps"][t] != rec["taps"][t]})
+            if T.CASES[name][5] != "default":
+                refused.append(f"{name} ({', '.join(differ)})")
+            no_hashes.append(name)
+            rec.update(out=None, taps={t: None for t in rec["taps"]}, unstable=f"differed between three runs of commit {commit[:12]}: {', '.join(differ)}")
+        print(f"{name}: workspace {rec['workspace']}  {(rec.get('out') or '-')[:16]}  {len(rec.get('rows', []))} rows  {rec.get('unstable', '')}")
+    if refused:
+        sys.exit(f"cases that have to repeat themselves on this library and do not (nothing written): {refused}")
+    write_unet(T, out, commit, hipcc, cases)
+    print(f"wrote {out}: {len(cases)} cases, {len(no_hashes)} `default` cases without hashes: {no_hashes}")
+
+
+def write_unet(T, out, commit, hipcc, cases):
+    tables, packed = T.unet_pack(cases)
+    with open(out, "w") as f:     # one table and one case per line
+        f.write(json.dumps({"parent_commit": commit, "hipcc_version": hipcc}, indent=1)[:-2] + ",\n")
+        f.write("".join(f' {json.dumps(k)}: {json.dumps(v, separators=(",", ":"))},\n' for k, v in tables.items()))
+        f.write(' "cases": {\n' + ",\n".join(f'  {json.dumps(n)}: {json.dumps(r, separators=(",", ":"))}' for n, r in packed.items()) + "\n }\n}\n")
 
 
 if __name__ == "__main__":
